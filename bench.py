@@ -85,6 +85,10 @@ def parse():
     ap.add_argument("--roofline-steps", type=int, default=12,
                     help="denoiser steps of the profiled roofline leg (HIP events around every GEMM launch)")
     ap.add_argument("--roofline-warm", type=int, default=10, help="un-profiled steps before them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0: the gathered waveforms, or "
+                         "the tokens with --transformer-only) as DIR/<name>.npy in float32, at most 64 MB (a fixed, seeded "
+                         "sample of the clips when the batch is larger), so that two builds can be compared output for output")
     return ap.parse_args()
 
 
@@ -517,6 +521,30 @@ def run_side_legs(legs, world, rank, line):
     return in_step
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, name, out, limit=DUMP_LIMIT_BYTES):
+    """`out` (the last timed step's result, clips along dim 0) -> out_dir/<name>.npy in float32.  When it is larger than
+    `limit`, a fixed sample of clips (torch.Generator seeded with 0, sorted) is written instead, and the clip indices
+    beside it as out_dir/<name>_clip_index.npy (float64).  Returns {file name: shape}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    x = out.detach().float().cpu()
+    n = x.shape[0]
+    per_clip = max(1, x[0].numel() * 4)
+    keep = min(n, (limit - 8 * n) // per_clip)
+    written = {}
+    if keep < n:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        x = x[idx]
+        np.save(os.path.join(out_dir, name + "_clip_index.npy"), idx.numpy().astype(np.float64))
+        written[name + "_clip_index.npy"] = [int(keep)]
+    np.save(os.path.join(out_dir, name + ".npy"), x.numpy().astype(np.float32))
+    written[name + ".npy"] = list(x.shape)
+    return written
+
+
 def result_line(args, world, elapsed, n_total):
     """The driver's one-line JSON contract (whole-job aggregate over all ranks)."""
     value = n_total * args.steps / elapsed
@@ -633,6 +661,8 @@ def main():
 
     # ---- the measurement is done: from here on only side legs, each of which may fail without costing the line ----------
     line = result_line(args, world, elapsed, n_total) if rank == 0 else {}
+    if args.dump_outputs and rank == 0:        # rank 0 holds the gathered batch of the last timed step
+        line["dumped_outputs"] = dump_outputs(args.dump_outputs, "tokens" if args.transformer_only else "waveform", w)
     bare = json.dumps(dict(line, incomplete="side legs did not finish"))
 
     def emit(reason=None):

@@ -619,17 +619,13 @@ def signatures():
     print("wrote signatures.json (%d callables)" % len(out))
 
 
-def bpe_closed_vocab():
-    """text-to-sound-synthesis_amd/data/bpe_closed_vocab.json (package data, not a golden vector: it is input of the
-    tokenizer, consumed by bench.py's timed region): the part of CLIP's merge table that the synthetic-caption word list
-    (text_to_sound_synthesis_amd.synth._WORDS) exercises -- every merge the FULL table applies to one of those words, with
-    its original rank, plus the ids of the resulting tokens and the two specials.  Checked here against the reference's
-    own tokenizer on 3000 random captions over the word list.  (The GPU box has no copy of the full table.)"""
-    from text_to_sound_synthesis_amd import synth as sy
+def _write_closed_table(path, words):
+    """A closed-vocabulary merge table (the format of text-to-sound-synthesis_amd/data/bpe_closed_vocab.json) for the
+    byte-level pre-token `words`: every merge the FULL CLIP table applies to one of them, with its original rank, plus
+    the ids of the resulting tokens and the two specials."""
     from text_to_sound_synthesis_amd import tokenizer as tz
     full = tz.SimpleTokenizer(bpe_path=os.path.join(rh.REF_ROOT, "sound_synthesis", "modeling", "modules", "clip",
                                                     "bpe_simple_vocab_16e6.txt.gz"))
-    words = sorted(set(sy._WORDS))
     merges, tokens = set(), set()
     for w in words:
         syms = list(w[:-1]) + [w[-1] + "</w>"]
@@ -651,9 +647,21 @@ def bpe_closed_vocab():
     enc = {t: full.encoder[t] for t in sorted(tokens)}
     for sp in ("<|startoftext|>", "<|endoftext|>"):
         enc[sp] = full.encoder[sp]
-    path = tz.CLOSED_VOCAB_PATH
     with open(path, "w") as f:
         json.dump({"words": words, "merges": sorted(merges, key=lambda m: m[2]), "encoder": enc}, f)
+    return words, merges, enc
+
+
+def bpe_closed_vocab():
+    """text-to-sound-synthesis_amd/data/bpe_closed_vocab.json (package data, not a golden vector: it is input of the
+    tokenizer, consumed by bench.py's timed region): the part of CLIP's merge table that the synthetic-caption word list
+    (text_to_sound_synthesis_amd.synth._WORDS) exercises -- every merge the FULL table applies to one of those words, with
+    its original rank, plus the ids of the resulting tokens and the two specials.  Checked here against the reference's
+    own tokenizer on 3000 random captions over the word list.  (The GPU box has no copy of the full table.)"""
+    from text_to_sound_synthesis_amd import synth as sy
+    from text_to_sound_synthesis_amd import tokenizer as tz
+    path = tz.CLOSED_VOCAB_PATH
+    words, merges, enc = _write_closed_table(path, sorted(set(sy._WORDS)))
     closed = tz.SimpleTokenizer(bpe_path=path)
     caps = sy.synth_captions(3000, seed=5)
     ref = rh.reference_tokenize(caps)["token"]
@@ -663,8 +671,154 @@ def bpe_closed_vocab():
           % (len(words), len(merges), len(enc)))
 
 
+def _crosscheck_inputs():
+    """The random inputs of tests/test_oracle_live_reference.py, drawn in the same order with the same generators (the test
+    imports nothing from here: it re-draws them and checks the fingerprints stored beside the reference's outputs)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_oracle_live_reference as tc
+    return tc
+
+
+@torch.no_grad()
+def crosscheck():
+    """tests/golden/oracle_crosscheck.npz: the reference's outputs on the randomised inputs of
+    tests/test_oracle_live_reference.py -- schedules of other sizes, q_posterior / Gumbel / q_sample at every timestep of a
+    T = 10 model, the truncation wrappers, the training loss in other loss settings, the vocoder at other lengths, the
+    denoiser on random states, the decoder on random tokens.  Weights are the synth weights by name (build_dalle /
+    build_vocoder), which the test rebuilds with the package's own modules.  Large outputs are kept as tc.digest(): a
+    seeded sample of their elements and the sums of fixed chunks of all of them."""
+    tc = _crosscheck_inputs()
+    rh.install()
+    from sound_synthesis.modeling.transformers import diffusion_transformer as D
+    arrs = {}
+    for T, N in tc.SCHEDULE_SIZES:
+        at, bt, ct, att, btt, ctt = D.alpha_schedule(T, N=N)
+        lg = lambda x: torch.log(torch.tensor(x.astype("float64")))
+        want = {"log_at": lg(at), "log_bt": lg(bt), "log_ct": lg(ct), "log_cumprod_at": lg(att),
+                "log_cumprod_bt": lg(btt), "log_cumprod_ct": lg(ctt)}
+        want["log_1_min_ct"] = D.log_1_min_a(want["log_ct"])
+        want["log_1_min_cumprod_ct"] = D.log_1_min_a(want["log_cumprod_ct"])
+        arrs.update({"sched_T%d_N%d_%s" % (T, N, k): v.float() for k, v in want.items()})
+
+    m10 = rh.build_dalle(n_layer=1, diffusion_step=10, n_embed=256)
+    dt = m10.transformer
+    for case in tc.posterior_cases():
+        t_val, mask_frac, x_t, log_x0, u = case["t"], case["mask_frac"], case["x_t"], case["log_x0"], case["u"]
+        t = torch.full((x_t.shape[0],), t_val, dtype=torch.long)
+        log_x_t = D.index_to_log_onehot(x_t, 257)
+        one, zero = log_x_t.max(), log_x_t.min()             # the reference's log-one-hot holds exactly these two values
+        assert torch.equal(log_x_t, torch.where(torch.nn.functional.one_hot(x_t, 257).permute(0, 2, 1).bool(), one, zero))
+        arrs["log_onehot_one"], arrs["log_onehot_zero"] = one, zero
+        want = dt.q_posterior(log_x_start=log_x0, log_x_t=log_x_t, t=t)
+        with InjectNoise(lambda shp: u):
+            tok = D.log_onehot_to_index(dt.log_sample_categorical(want))
+        arrs.update(tc.digest("post_%s" % case["name"], want))
+        arrs["post_%s_tokens" % case["name"]] = tok.to(torch.int16)
+        # positions where the Gumbel-perturbed top two are within 2 x the test's tolerance of each other
+        top2 = (want + tc.gumbel_noise(u)).topk(2, dim=1).values
+        arrs["post_%s_near_tie" % case["name"]] = np.packbits((top2[:, 0] - top2[:, 1] < 2 * 2e-5).numpy())
+        arrs["post_%s_fp" % case["name"]] = case["fp"]
+    for case in tc.q_sample_cases():
+        with InjectNoise(lambda shp: case["u"]):
+            want = dt.q_sample(log_x_start=D.index_to_log_onehot(case["x0"], 257), t=case["t"])
+        arrs["qs_%d_tokens" % case["t_val"]] = D.log_onehot_to_index(want).to(torch.int16)
+        arrs["qs_%d_fp" % case["t_val"]] = case["fp"]
+    cases = tc.truncation_cases()
+    for st in tc.SAMPLE_TYPES:
+        for i, lp in enumerate(cases):
+            m10.this_save_path = None       # the reference's top-k branch reads this attribute (dalle_spec.py:150)
+            want = m10.predict_start_with_truncation(lambda: lp, st)()
+            keep = want > -70
+            assert torch.equal(want, torch.where(keep, lp, torch.full_like(lp, -70.0)))   # kept entries are lp's own
+            n_kept = keep.sum(1)
+            if i == len(cases) - 1:     # the tied case: which of the tied classes survive is the reference's own choice
+                arrs["trunc_%s_%d_keep" % (st, i)] = np.packbits(keep.numpy())
+            else:                       # distinct values: the survivors are the n_kept largest of their column
+                assert torch.equal(keep, tc.keep_largest(lp, n_kept))
+            arrs["trunc_%s_%d_n_kept" % (st, i)] = n_kept.to(torch.int16)
+    arrs["trunc_fp"] = tc.fingerprint(*cases)
+
+    for i, (aux, adaptive, mask_w, ts) in enumerate(tc.LOSS_CONFIGS):
+        m = rh.build_dalle(n_layer=1, diffusion_step=100, n_embed=256)
+        d = m.transformer
+        d.auxiliary_loss_weight, d.adaptive_auxiliary_loss, d.mask_weight = aux, adaptive, mask_w
+        x0, cond, t, pt, u = tc.loss_inputs(ts)
+        d.sample_time = lambda b, device, method="uniform": (t, pt)
+        with InjectNoise(lambda shp: u), torch.enable_grad():
+            out = d({"content_token": x0, "condition_embed_token": cond, "condition_token": None}, return_loss=True,
+                    return_logits=True)
+        arrs["loss_%d" % i] = np.float64(float(out["loss"]))
+        arrs.update(tc.digest("loss_%d_logits" % i, out["logits"].detach()))
+
+    voc = rh.build_vocoder()
+    for B, T in tc.VOCODER_SIZES:
+        arrs.update(tc.digest("voc_%d_%d" % (B, T), voc(tc.vocoder_mel(B, T))))
+    m2 = rh.build_dalle(n_layer=2, diffusion_step=100, n_embed=256)
+    for case in tc.denoiser_cases():
+        arrs.update(tc.digest("tf_%s" % case["name"], m2.transformer.transformer(case["x"], case["cond"], case["t"])))
+        arrs["tf_%s_fp" % case["name"]] = case["fp"]
+    tok = tc.decoder_tokens()
+    arrs.update(tc.digest("dec", m10.decode_to_img(tok, (2, 256, 5, 53))))
+    save("oracle_crosscheck", **arrs)
+
+    # the package's modules carry the same synth weights as the reference models above, name for name
+    from text_to_sound_synthesis_amd.modeling.vocoder import Generator
+    for ref_model, n_layer, T in ((m10, 1, 10), (m, 1, 100), (m2, 2, 100)):
+        sd = tc.package_sd(n_layer, T)
+        for k, v in ref_model.state_dict().items():
+            if not k.startswith(("content_codec.encoder.", "content_codec.quant_conv.", "content_codec.loss.",
+                                 "transformer.Lt_")):       # (the loss statistics its forward(return_loss) just updated)
+                assert k in sd and torch.equal(sd[k], v), k
+    g = synth.synth_init_(Generator(80, 32, 3), seed=0)
+    for k, v in voc.state_dict().items():
+        assert torch.equal(g.state_dict()[k], v), k
+
+
+def _pre_tokens(texts):
+    """The byte-level pre-tokens SimpleTokenizer.encode hands to its BPE loop for `texts` (its own cleaning and split)."""
+    import html
+    from text_to_sound_synthesis_amd import tokenizer as tz
+    out = set()
+    for text in texts:
+        text = " ".join(html.unescape(html.unescape(text)).strip().split()).lower()
+        for piece in tz._PAT.findall(text):
+            if piece not in ("<|startoftext|>", "<|endoftext|>"):
+                out.add("".join(tz._byte_alphabet()[b] for b in piece.encode("utf-8")))
+    return sorted(out)
+
+
+def tokenizer_crosscheck():
+    """tests/golden/tokenizer_random_captions.npz: the reference tokenizer's ids and masks for the 2 000 random captions
+    of tests/test_text_stage.py, plus a digest of the captions.  And tests/golden/bpe_test_vocab.json: the closed-vocabulary
+    part of CLIP's merge table (_write_closed_table) for every word of those captions and of tests/golden/captions.json,
+    the merge table the tokenizer tests run on; checked here to give the reference's ids on both caption sets."""
+    import hashlib
+    from text_to_sound_synthesis_amd import tokenizer as tz
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_text_stage as ts
+    rh.install()
+    caps = ts.random_captions()
+    with open(os.path.join(OUT, "captions.json")) as f:
+        golden_caps = json.load(f)
+    path = os.path.join(OUT, "bpe_test_vocab.json")
+    words, merges, enc = _write_closed_table(path, _pre_tokens(caps + golden_caps))
+    closed = tz.SimpleTokenizer(bpe_path=path)
+    for c in (caps, golden_caps):
+        ref = rh.reference_tokenize(c)
+        got = tz.tokenize(c, context_length=77, add_start_and_end=True, tokenizer=closed)
+        assert torch.equal(ref["token"], got["token"]) and torch.equal(ref["mask"], got["mask"])
+    print("wrote bpe_test_vocab.json (%d words, %d merges, %d tokens)" % (len(words), len(merges), len(enc)))
+    tk = rh.reference_tokenize(caps)
+    save("tokenizer_random_captions", tokens=tk["token"].to(torch.int32), mask=tk["mask"],
+         captions_sha256=np.array(hashlib.sha256("\n".join(caps).encode()).hexdigest()))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
+    if "--crosscheck-only" in sys.argv:
+        return crosscheck()
+    if "--tokenizer-crosscheck-only" in sys.argv:
+        return tokenizer_crosscheck()
     if "--bpe-only" in sys.argv:
         return bpe_closed_vocab()
     if "--signatures-only" in sys.argv:
@@ -791,6 +945,8 @@ def main():
     dalle_sample()
     signatures()
     bpe_closed_vocab()
+    crosscheck()
+    tokenizer_crosscheck()
     traj_full()
     traj_k512()
     traj_b64()

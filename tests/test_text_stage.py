@@ -10,12 +10,13 @@ import diffsound_oracle as O
 from conftest import GOLDEN, golden
 
 NO_GRAD = True          # tests/conftest.py: every test of this module runs under torch.no_grad()
-_REF_BPE = "/root/reference/Diffsound/sound_synthesis/modeling/modules/clip/bpe_simple_vocab_16e6.txt.gz"
+# the part of CLIP's merge table that the words of these tests exercise, with the original ranks and token ids
+# (oracle/make_golden.py tokenizer_crosscheck(); the same format as the package's data/bpe_closed_vocab.json)
+_TEST_BPE = os.path.join(GOLDEN, "bpe_test_vocab.json")
 
 
 def _bpe_path():
-    p = os.environ.get("DIFFSOUND_BPE_PATH") or _REF_BPE
-    return p if os.path.exists(p) else None
+    return _TEST_BPE
 
 
 def clip_sd():
@@ -24,7 +25,6 @@ def clip_sd():
         return synth_state_dict(json.load(f))
 
 
-@pytest.mark.skipif(_bpe_path() is None, reason="CLIP BPE merge table not available on this box")
 def test_tokenizer_matches_reference_ids():
     from text_to_sound_synthesis_amd.tokenizer import Tokenize
     caps = json.load(open(os.path.join(GOLDEN, "captions.json")))
@@ -62,23 +62,10 @@ def test_clip_state_dict_contract():
     assert sd == want
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Diffsound/sound_synthesis"),
-                    reason="cross-check against the live reference tokenizer: reference tree not on this box")
-def test_tokenizer_matches_live_reference_on_random_captions():
-    """2 000 random captions (words, digits, punctuation, apostrophes, HTML entities, odd spacing, upper case, a few
-    non-ASCII letters, over-long captions) through the reference's own SimpleTokenizer / clip.tokenize call path
-    (tokenize.py:59-69) and through this package's tokenizer: identical ids and masks."""
+def random_captions():
+    """2 000 random captions: words, digits, punctuation, apostrophes, HTML entities, odd spacing, upper case, a few
+    non-ASCII letters, over-long captions (oracle/make_golden.py tokenizer_crosscheck() ran the reference on them)."""
     import random
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "oracle"))
-    import ref_harness as rh
-    rh.install()
-    from sound_synthesis.modeling.codecs.text_codec.tokenize import Tokenize as RefTokenize
-    from text_to_sound_synthesis_amd.tokenizer import Tokenize
-    kw = dict(context_length=77, add_start_and_end=True, with_mask=True, pad_value=0)
-    ref = RefTokenize(tokenizer_config={"target": "sound_synthesis.modeling.modules.clip.simple_tokenizer.SimpleTokenizer",
-                                        "params": {"end_idx": 49152}}, **kw)
-    mine = Tokenize(tokenizer_config={"params": {"end_idx": 49152}}, bpe_path=_bpe_path(), **kw)
     rng = random.Random(20260925)
     words = ["dog", "barks", "rain", "thunder", "engine", "a", "the", "while", "birds", "chirping", "loudly", "car",
              "passes", "by", "woman", "speaks", "and", "then", "laughs", "keyboard", "typing", "whoosh", "sizzling",
@@ -92,11 +79,26 @@ def test_tokenizer_matches_live_reference_on_random_captions():
         toks = [w.upper() if rng.random() < 0.1 else w.capitalize() if rng.random() < 0.1 else w for w in toks]
         sep = rng.choice((" ", " ", "  ", "\t", " \n "))
         caps.append(("  " if rng.random() < 0.2 else "") + sep.join(toks) + (" " if rng.random() < 0.2 else ""))
+    return caps
+
+
+def test_tokenizer_matches_live_reference_on_random_captions():
+    """The 2 000 random captions of random_captions() through this package's tokenizer: ids and masks identical to what
+    the reference's own SimpleTokenizer / clip.tokenize call path (tokenize.py:59-69) gave for them
+    (tests/golden/tokenizer_random_captions.npz)."""
+    import hashlib
+    import numpy as np
+    from text_to_sound_synthesis_amd.tokenizer import Tokenize
+    caps = random_captions()
+    with np.load(os.path.join(GOLDEN, "tokenizer_random_captions.npz")) as z:
+        assert hashlib.sha256("\n".join(caps).encode()).hexdigest() == str(z["captions_sha256"])
+        ref = {"token": torch.from_numpy(z["tokens"]).long(), "mask": torch.from_numpy(z["mask"])}
+    kw = dict(context_length=77, add_start_and_end=True, with_mask=True, pad_value=0)
+    mine = Tokenize(tokenizer_config={"params": {"end_idx": 49152}}, bpe_path=_bpe_path(), **kw)
     for i in range(0, len(caps), 250):
-        a, b = ref.get_tokens(caps[i:i + 250]), mine.get_tokens(caps[i:i + 250])
-        assert torch.equal(a["token"], b["token"]), [c for c, x, y in zip(caps[i:i + 250], a["token"], b["token"])
-                                                     if not torch.equal(x, y)][:3]
-        assert torch.equal(a["mask"], b["mask"])
+        a, b = ref["token"][i:i + 250], mine.get_tokens(caps[i:i + 250])
+        assert torch.equal(a, b["token"]), [c for c, x, y in zip(caps[i:i + 250], a, b["token"]) if not torch.equal(x, y)][:3]
+        assert torch.equal(ref["mask"][i:i + 250], b["mask"])
 
 
 def test_closed_vocabulary_merge_table_matches_goldens_and_refuses_other_words():
