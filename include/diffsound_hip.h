@@ -282,8 +282,15 @@ int ds_rows_times_matrix(const float* x, const float* W, float* part, int G, int
  * the AdaLN backward's d linear.weight = (d modulation)^T silu(emb(t_b)) for all modules in one output-bound pass (what
  * autograd computes for AdaLayerNorm.linear.weight, transformer_utils.py:145-147). */
 int ds_rows_outer(const float* a, const float* s, float* out, int G, int B, int N, int D, ds_stream_t stream);
-/* d emb[tokens[m]] += dx[m] (atomic) */
+/* d emb[r] += sum over the m with tokens[m] == r of dx[m], in a fixed order (bit-reproducible; no atomics); tokens outside
+ * [0, rows) are skipped.  D % 4 == 0, 16-byte aligned dx / demb.  One workgroup per row and 256 columns walks all positions. */
 int ds_embed_bwd(const float* dx, const int64_t* tokens, float* demb, int M, int D, int rows, ds_stream_t stream);
+/* The same sum with the positions split into chunks of 256 whose partial tables (work: ds_embed_bwd_work_floats(M, D, rows)
+ * floats, 16-byte aligned) ds_colsum adds in chunk order: a long list (the [MASK] row at high t) spread over many workgroups.
+ * The training step's entry. */
+long long ds_embed_bwd_work_floats(int M, int D, int rows);
+int ds_embed_bwd_ws(const float* dx, const int64_t* tokens, float* demb, int M, int D, int rows, float* work, long long work_floats,
+                    ds_stream_t stream);
 /* fused AdamW update (torch.optim.AdamW semantics), step >= 1 */
 int ds_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
              float weight_decay, int step, ds_stream_t stream);

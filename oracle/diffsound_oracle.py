@@ -140,10 +140,11 @@ def initial_log_z(batch, num_classes=257, length=265):
     return torch.log(z)
 
 
-def predict_start(logits):
+def predict_start(logits, dtype=torch.float32):
     """diffusion_transformer.py:285-289: float64 log_softmax over classes, append a -70 row
-    for [MASK], clamp to [-70, 0].  `logits` is the transformer output [B, K, L]."""
-    lp = F.log_softmax(logits.double(), dim=1).float()
+    for [MASK], clamp to [-70, 0].  `logits` is the transformer output [B, K, L].  dtype: of the result (the
+    reference's fp32; float64 for an all-float64 run of the oracle)."""
+    lp = F.log_softmax(logits.double(), dim=1).to(dtype)
     lp = torch.cat((lp, torch.full_like(lp[:, :1, :], -70.0)), dim=1)
     return lp.clamp(-70.0, 0.0)
 
@@ -200,7 +201,7 @@ def q_posterior(sched, log_x_start, log_x_t, t):
         # mask row -> log(1e-30); where x_t is [MASK]: classes -> per_t, mask row -> 0
         log_q = torch.cat((log_q[:, :-1], lz), dim=1)
         alt = torch.cat((per_t.view(-1, 1, 1).expand(-1, Kp1 - 1, 1),
-                         torch.zeros(log_q.shape[0], 1, 1)), dim=1)
+                         torch.zeros(log_q.shape[0], 1, 1, dtype=log_q.dtype)), dim=1)
         return torch.where(is_mask, alt.expand_as(log_q), log_q)
 
     log_qt = fix(_q_pred(sched, log_x_t, t, T), sched["log_cumprod_ct"][t])
@@ -303,18 +304,25 @@ def sample_loop_repeat(sd, cond_emb, noise_fn, rate, rng, num_timesteps=100, tru
 
 # --------------------------------------------------------------------------- scope row 8f-3 (oracle only so far)
 def train_loss(sd, x0, cond_emb, t, pt, u, num_timesteps=100, n_head=16, mask_weight=(1.0, 1.0),
-               auxiliary_loss_weight=5.0e-4, adaptive_auxiliary_loss=True):
+               auxiliary_loss_weight=5.0e-4, adaptive_auxiliary_loss=True, xt=None):
     """DiffusionTransformer._train_loss + the normalisation of forward(), diffusion_transformer.py:408-476,571-574:
     x_t ~ q(x_t | x_0) (uniforms u injected), the network's p(x_0 | x_t), the KL between the true and the modelled
     posterior (decoder NLL at t = 0), re-weighted by 1/pt, plus the auxiliary KL(x_0 || p(x_0|x_t)) term.
     x0 i64[B, L] tokens, t i64[B] and pt f32[B] as sample_time() returned them.  No truncation wrapper is installed
-    in training.  Returns (log_model_prob [B, K+1, L], vb_loss [B], loss scalar, Lt2 [B] = kl_loss^2 for Lt_history)."""
+    in training.  Returns (log_model_prob [B, K+1, L], vb_loss [B], loss scalar, Lt2 [B] = kl_loss^2 for Lt_history).
+    The computation runs in the dtype of the state dict (float64 weights: the schedule's fp32 values, the log-one-hot
+    states and the log-softmax are taken to float64 as well).  xt: i64[B, L] given x_t instead of q_sample's (u is then
+    unused) -- a float64 run of the Gumbel argmax can resolve a near-tie differently from an fp32 one."""
     K = sd["transformer.transformer.to_logits.1.weight"].shape[0]
-    sched = make_schedule(num_timesteps, K + 1)
-    log_x_start = log_onehot(x0, K + 1)
-    log_xt = q_sample(sched, x0, t, u, K + 1)
-    xt = log_xt.argmax(1)
-    log_x0_recon = predict_start(transformer_forward(sd, xt, cond_emb, t, n_head=n_head))
+    dtype = sd["transformer.transformer.to_logits.1.weight"].dtype
+    sched = {k: v.to(dtype) for k, v in make_schedule(num_timesteps, K + 1).items()}
+    log_x_start = log_onehot(x0, K + 1).to(dtype)
+    if xt is None:
+        log_xt = q_sample(sched, x0, t, u, K + 1).to(dtype)
+        xt = log_xt.argmax(1)
+    else:
+        log_xt = log_onehot(xt, K + 1).to(dtype)
+    log_x0_recon = predict_start(transformer_forward(sd, xt, cond_emb, t, n_head=n_head), dtype)
     log_model_prob = q_posterior(sched, log_x0_recon, log_xt, t)
     log_true_prob = q_posterior(sched, log_x_start, log_xt, t)
     kl_of = lambda a, b: (a.exp() * (a - b)).sum(dim=1)                       # multinomial_kl, :237-239

@@ -349,6 +349,38 @@ def test_k512_chain_100_steps_vs_reference(model_k512, voc):
     assert mel_err < MEL_TOL and wave_rms < WAVE_RMS_TOL
 
 
+def test_k512_teacher_forced_batch64_padded_rows(model_k512):
+    """configs[3]'s sampling shard: BASELINE configs[3] samples 64 clips per GPU at K = 512, i.e. in padded-row mode with the
+    N = 512 logits layer and 513 classes.  The 8 reference captions of traj_T100_L19_k512 replicated 8 times, 100
+    teacher-forced steps: disagreements only at the reference's own near-ties (at most MAX_FLIPS["f16x2"] per replica set),
+    and the 8 replicas of a caption identical."""
+    g = golden("traj_T100_L19_k512")
+    set_precision(model_k512, "f16x2")
+    dt = model_k512.transformer
+    assert dt.transformer.row_padding
+    R = 8
+    cond = g["cond_emb"].float().cuda().repeat(R, 1, 1)
+    trace = g["step_tokens"].long()
+    B0 = trace.shape[1]
+    B = R * B0
+    kv = dt.transformer.condition_kv(cond, dt._schedule_table())
+    flips, replica_mismatch = [], 0
+    for i in range(100):
+        t = 99 - i
+        x_t = (torch.full((B0, 265), 512, dtype=torch.long) if i == 0 else trace[i - 1]).repeat(R, 1)
+        u = noise(t, (B0, 513, 265)).repeat(R, 1, 1)
+        tok = dt.p_sample_tokens(x_t.cuda(), kv, torch.full((B,), t, dtype=torch.long).cuda(), u.cuda(), initial=(i == 0)).cpu()
+        replica_mismatch += int((tok.view(R, B0, 265) != tok.view(R, B0, 265)[:1]).sum())
+        for b, p in (tok != trace[i].repeat(R, 1)).nonzero().tolist():
+            flips.append({"t": t, "clip": b % B0, "replica": b // B0, "pos": p, "gap": float(g["gap"][i, b % B0, p]),
+                          "tmargin": float(g["tmargin"][i, b % B0, p])})
+    report("f16x2", "k512_teacher_forced_batch64_padded_rows", {"decisions": 100 * B * 265, "flips": len(flips),
+                                                                "replica_mismatches": replica_mismatch, "detail": flips[:16]})
+    unexplained = [f for f in flips if not (f["tmargin"] < CUT_TIE or f["gap"] < GAP_TIE)]
+    assert not unexplained, "K = 512: token disagreements away from any near-tie: %s" % unexplained[:4]
+    assert len(flips) <= MAX_FLIPS["f16x2"] * R and replica_mismatch == 0
+
+
 def test_batch64_distinct_captions_first_10_steps_vs_reference(model):
     """The benchmarked batch (64 distinct captions, padded-row mode, per-sample GEMM program) teacher-forced on the
     reference's own first 10 reverse steps: 169 600 decisions against the reference itself, no replicas."""

@@ -460,20 +460,92 @@ extern "C" int ds_softmax_bwd_rows(const float* P, float* dP, int rows, int n, i
     return 0;
 }
 
-// ---- embedding backward: d emb[token[m]][:] += dx[m][:]  (fp32 atomics; the content embedding has 257 rows) ------------
-__global__ __launch_bounds__(256) void ds_embed_bwd_kernel(const float* __restrict__ dx, const int64_t* __restrict__ tok,
-                                                           float* __restrict__ demb, int M, int D, int rows) {
-    const int m = blockIdx.x;
-    long long tk = tok[m];
-    if (tk < 0 || tk >= rows) return;
-    for (int c = threadIdx.x; c < D; c += 256) atomicAdd(demb + (size_t)tk * D + c, dx[(size_t)m * D + c]);
+// ---- embedding backward: d emb[r][:] += the sum, in position order, of dx[m][:] over the m with tokens[m] == r ----------
+// No float atomics: at high t almost every position is [MASK] and thousands of rows add into that one table row, whose sum
+// then depended on the order the hardware delivered them (and serialised on one address).  The positions are cut into chunks
+// of EB_CHUNK; workgroup (r, s, column block) lists, in position order, the positions of its chunks whose token is r (a wave
+// ballot per 64 positions) and adds their dx rows -- wave w takes every fourth entry of a chunk's list, eight loads in flight,
+// and the four wave sums are added in wave order.  ds_embed_bwd_ws: one chunk per workgroup into part[s][r], ds_colsum adds the
+// chunks in order -- a long list (the [MASK] row) is spread over ceil(M / EB_CHUNK) x ceil(D / 256) workgroups.  ds_embed_bwd
+// (no workspace): one workgroup walks all chunks of its row and adds into d emb itself; the same fixed order, but the [MASK]
+// row's list is walked by ceil(D / 256) workgroups alone.  Every dx row is read once, by the workgroups of its row.
+#define EB_CHUNK 256
+__global__ __launch_bounds__(256) void ds_embed_bwd_part_kernel(const float* __restrict__ dx, const int64_t* __restrict__ tok,
+                                                                float* __restrict__ out, int M, int D, int rows, int nchunk,
+                                                                int accumulate) {
+    __shared__ int list[EB_CHUNK];
+    __shared__ int wcount[4];
+    __shared__ f32x4 red[4][64];
+    const int r = blockIdx.x;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int c = (blockIdx.z * 64 + lane) * 4;
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < nchunk; ++k) {
+        const int m = (blockIdx.y * nchunk + k) * EB_CHUNK + threadIdx.x;
+        const bool hit = m < M && tok[m] == (int64_t)r;       // (a token outside [0, rows) matches no row: skipped)
+        const unsigned long long bal = __ballot(hit);
+        if (lane == 0) wcount[w] = __popcll(bal);
+        __syncthreads();
+        if (hit) {
+            int off = __popcll(bal & ((1ull << lane) - 1));
+            for (int v = 0; v < w; ++v) off += wcount[v];
+            list[off] = m;
+        }
+        const int n = wcount[0] + wcount[1] + wcount[2] + wcount[3];
+        __syncthreads();
+        if (c < D) {
+            int j = w;
+            for (; j + 4 * 7 < n; j += 4 * 8) {
+                f32x4 v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[u] = *(const f32x4*)(dx + (size_t)list[j + 4 * u] * D + c);
+#pragma unroll
+                for (int u = 0; u < 8; ++u) acc += v[u];
+            }
+            for (; j < n; j += 4) acc += *(const f32x4*)(dx + (size_t)list[j] * D + c);
+        }
+        __syncthreads();                                      // (list / wcount are rewritten by the next chunk)
+    }
+    red[w][lane] = acc;
+    __syncthreads();
+    if (w == 0 && c < D) {
+        const f32x4 t = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+        f32x4* o = (f32x4*)(out + ((size_t)blockIdx.y * rows + r) * D + c);
+        *o = accumulate ? *o + t : t;
+    }
+}
+
+extern "C" long long ds_embed_bwd_work_floats(int M, int D, int rows) {
+    return M > 0 && D > 0 && rows > 0 ? (long long)((M + EB_CHUNK - 1) / EB_CHUNK) * rows * D : 0;
+}
+
+static int ds_embed_bwd_check(const float* dx, const int64_t* tokens, const float* demb, int M, int D, int rows) {
+    DS_CHECK_ARG(dx && tokens && demb && M > 0 && D > 0 && D % 4 == 0 && rows > 0, "bad arguments (D % 4 == 0)");
+    DS_CHECK_ARG(((((uintptr_t)dx) | ((uintptr_t)demb)) & 15) == 0, "dx / demb must be 16-byte aligned");
+    DS_CHECK_ARG((M + EB_CHUNK - 1) / EB_CHUNK <= 65535 && (long long)rows * D <= 0x7fffffffLL, "grid limits");
+    return 0;
 }
 
 extern "C" int ds_embed_bwd(const float* dx, const int64_t* tokens, float* demb, int M, int D, int rows, ds_stream_t stream) {
-    DS_CHECK_ARG(dx && tokens && demb && M > 0 && D > 0 && rows > 0, "bad arguments");
-    hipLaunchKernelGGL(ds_embed_bwd_kernel, dim3(M), dim3(256), 0, (hipStream_t)stream, dx, tokens, demb, M, D, rows);
+    const int rc = ds_embed_bwd_check(dx, tokens, demb, M, D, rows);
+    if (rc) return rc;
+    hipLaunchKernelGGL(ds_embed_bwd_part_kernel, dim3(rows, 1, (D + 255) / 256), dim3(256), 0, (hipStream_t)stream, dx, tokens, demb,
+                       M, D, rows, (M + EB_CHUNK - 1) / EB_CHUNK, 1);
     DS_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int ds_embed_bwd_ws(const float* dx, const int64_t* tokens, float* demb, int M, int D, int rows, float* work,
+                               long long work_floats, ds_stream_t stream) {
+    const int rc = ds_embed_bwd_check(dx, tokens, demb, M, D, rows);
+    if (rc) return rc;
+    DS_CHECK_ARG(work && (((uintptr_t)work) & 15) == 0, "work must be 16-byte aligned");
+    DS_CHECK_ARG(work_floats >= ds_embed_bwd_work_floats(M, D, rows), "work: ds_embed_bwd_work_floats(M, D, rows) floats");
+    const int S = (M + EB_CHUNK - 1) / EB_CHUNK;
+    hipLaunchKernelGGL(ds_embed_bwd_part_kernel, dim3(rows, S, (D + 255) / 256), dim3(256), 0, (hipStream_t)stream, dx, tokens, work,
+                       M, D, rows, 1, 0);
+    DS_CHECK_LAUNCH();
+    return ds_colsum(work, demb, 1, S, rows * D, (long long)rows * D, 0, 1, stream);
 }
 
 // ---- AdamW (torch.optim.AdamW semantics: decoupled weight decay, bias-corrected moments), one fused pass ----------------

@@ -69,6 +69,28 @@ def _colsum(x, G=1, R=None, accumulate_into=None):
     return out
 
 
+_ROWS_MAX = 32      # rows per launch of ds_rows_outer / ds_rows_times_matrix
+
+
+def _rows_outer(a, s):
+    """out[g] = a[g]^T s[g] for a [G][B][N], s [G][B][D] (contiguous) by ds_rows_outer; past 32 samples, one launch per 32 and
+    the partial results added in chunk order (bit-reproducible)"""
+    G, B, N = a.shape
+    D = s.shape[2]
+    out = torch.empty(G, N, D, device=a.device)
+    tmp = None
+    for b0 in range(0, B, _ROWS_MAX):
+        nb = min(B - b0, _ROWS_MAX)
+        ab = a if nb == B else a[:, b0:b0 + nb].contiguous()
+        sb = s if nb == B else s[:, b0:b0 + nb].contiguous()
+        if b0 and tmp is None:
+            tmp = torch.empty_like(out)
+        L_.check(L_.lib().ds_rows_outer(L_.ptr(ab), L_.ptr(sb), L_.ptr(tmp if b0 else out), G, nb, N, D, L_.stream()))
+        if b0:
+            out += tmp
+    return out
+
+
 PACK_PLAIN, PACK_GELU2, PACK_GELU2_BWD = 0, 1, 2
 
 
@@ -903,19 +925,26 @@ class TrainStep:
             dmod = torch.stack([both for _, both, _, _ in ada]) * inv                               # [G][B][2D]
             E = ada_E if order == list(range(len(lns))) else torch.stack([ada_E[i] for i in order])   # [G][B][D]
             sg = torch.sigmoid(E)
-            dw = torch.empty(G, 2 * D, D, device=dev)                                              # dW[g] = dmod[g]^T silu(e_b[g]):
-            silu_e = (E * sg).contiguous()                                                         # B outer products per module
-            L_.check(L_.lib().ds_rows_outer(L_.ptr(dmod), L_.ptr(silu_e), L_.ptr(dw), G, B, 2 * D, D, L_.stream()))
+            silu_e = (E * sg).contiguous()                                                         # dW[g] = dmod[g]^T silu(e_b[g]):
+            dw = _rows_outer(dmod, silu_e)                                                         # B outer products per module
             # dmod[g] W[g]: B rows against the row-major weights where they lie (ds_rows_times_matrix: no transposed copy of the
             # 38 matrices -- 0.38 ms per iteration -- and no tile program that is mostly padding rows); ada_W is in forward order
             Wg = ada_W if order == list(range(len(lns))) else torch.stack([ada_W[i] for i in order])
             KS = (2 * D) // 256
-            part = torch.empty(KS, G, B, D, device=dev)
-            L_.check(L_.lib().ds_rows_times_matrix(L_.ptr(dmod), L_.ptr(Wg), L_.ptr(part), G, B, 2 * D, D, L_.stream()))
             ds_ = torch.empty(G, B, D, device=dev)
-            L_.check(L_.lib().ds_colsum(L_.ptr(part), L_.ptr(ds_), 1, KS, G * B * D, G * B * D, 0, 0, L_.stream()))
-            de = torch.zeros(G, T, D, device=dev)
-            de.index_add_(1, t, ds_ * (sg * (1.0 + E * (1.0 - sg))))                               # samples that share a timestep add up
+            for b0 in range(0, B, _ROWS_MAX):               # (the kernel takes <= 32 rows; every row's result is its own)
+                nb = min(B - b0, _ROWS_MAX)
+                xb = dmod if nb == B else dmod[:, b0:b0 + nb].contiguous()
+                part = torch.empty(KS, G, nb, D, device=dev)
+                L_.check(L_.lib().ds_rows_times_matrix(L_.ptr(xb), L_.ptr(Wg), L_.ptr(part), G, nb, 2 * D, D, L_.stream()))
+                ob = ds_ if nb == B else torch.empty(G, nb, D, device=dev)
+                L_.check(L_.lib().ds_colsum(L_.ptr(part), L_.ptr(ob), 1, KS, G * nb * D, G * nb * D, 0, 0, L_.stream()))
+                if nb != B:
+                    ds_[:, b0:b0 + nb] = ob
+            # de[g][tau] = sum over the b with t_b = tau of ds_[g][b] silu'(e_b): the same sum of outer products with one-hot rows
+            # (samples that share a timestep add up in sample order -- index_add_'s atomics made that order the hardware's)
+            onehot = (t[:, None] == torch.arange(T, device=dev)).float().expand(G, B, T).contiguous()   # [G][B][T]
+            de = _rows_outer(onehot, (ds_ * (sg * (1.0 + E * (1.0 - sg)))).contiguous())
             dbias = dmod.sum(1)                                                                    # [G][2D]
             for i, (_, _, _, pfx) in enumerate(ada):
                 g[pfx + ".emb.weight"], g[pfx + ".linear.weight"], g[pfx + ".linear.bias"] = de[i], dw[i], dbias[i]
@@ -968,7 +997,9 @@ class TrainStep:
         hand_over([pfx + sfx for _, _, _, pfx in ada for sfx in (".linear.weight", ".emb.weight")])
         # ---- embedding
         demb = torch.zeros_like(emb.emb.weight)
-        L_.check(L_.lib().ds_embed_bwd(L_.ptr(dx), L_.ptr(xt), L_.ptr(demb), M, D, demb.shape[0], L_.stream()))
+        nw = L_.lib().ds_embed_bwd_work_floats(M, D, demb.shape[0])
+        ework = torch.empty(nw, device=dev)
+        L_.check(L_.lib().ds_embed_bwd_ws(L_.ptr(dx), L_.ptr(xt), L_.ptr(demb), M, D, demb.shape[0], L_.ptr(ework), nw, L_.stream()))
         g["transformer.content_emb.emb.weight"] = demb
         dpos = torch.empty(Lx, D, device=dev)
         L_.check(L_.lib().ds_colsum(L_.ptr(dx), L_.ptr(dpos), Lx, B, D, Lx * D, D, 0, L_.stream()))
