@@ -17,14 +17,16 @@ seeded random-init tensors of the reference's exact shapes (no checkpoints exist
 Multi-GPU: captions shard across ranks (weak scaling, fixed B per GPU); rank 0 scatters the caption
 token ids and gathers the waveforms over RCCL inside the timed region.
 
-Prints ONE JSON line on rank 0 (see README/DESIGN.md for the fields).  `roofline` is measured live:
-HIP events around every denoiser GEMM launch in a separate profiled batch (ds_profile_*), algorithmic
-flops 2*M*N*K per launch.  `cpu_baseline` times the reference itself (when /root/reference exists) or the CPU oracle (a
-restatement of the reference path) on a bounded sample on this box's host cores, thread count swept.
+Prints ONE JSON line on rank 0 (see README/DESIGN.md for the fields).  A plain run does only what that line's headline
+needs: set up, warm up, time the K steps, write --dump-outputs, print.  Everything else the benchmark measures runs only
+with --full, as side legs after the timed region: `host_copy`, `roofline`, `stage_ms`, `rccl` (N > 1), `train` and
+`cpu_baseline`.  `roofline` is measured live: HIP events around every denoiser GEMM launch in a separate profiled batch
+(ds_profile_*), algorithmic flops 2*M*N*K per launch.  `cpu_baseline` times the reference itself (when it is present) or
+the CPU oracle (a restatement of the reference path) on a bounded sample on the host's cores, thread count swept.
 
-Everything after the timed region is a side leg (run_side_legs): a leg that raises is filed as {"error": ...} under its
-name, and a leg that hangs -- N ranks, one of them gone inside a collective -- is cut off by HeadlineGuard after
---side-leg-limit seconds (N > 1 only): the line is printed with what it has ("incomplete": reason) and every rank exits 0.
+A side leg (run_side_legs) that raises is filed as {"error": ...} under its name, and a leg that hangs -- N ranks, one of
+them gone inside a collective -- is cut off by HeadlineGuard after --side-leg-limit seconds (N > 1 only): the line is
+printed with what it has ("incomplete": reason) and every rank exits 0.
 """
 import argparse
 import ctypes
@@ -62,16 +64,21 @@ def parse():
                          "can flip); torch: torch.rand per step, the reference's own draw")
     ap.add_argument("--transformer-only", action="store_true",
                     help="BASELINE configs[1]: CLIP + sampling loop only (no decode / vocoder); not the default metric")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the side legs: host copy, roofline, stage split, communicator check "
+                         "(N > 1), training leg and CPU baseline (each can still be left out with its --no-* option); a plain "
+                         "run prints the headline line alone")
     ap.add_argument("--no-train-leg", action="store_true",
-                    help="skip the BASELINE configs[4] leg (the training iteration from the reference's batch, B = 20 per GPU, 19 "
-                         "layers: mel + captions -> BPE + CLIP + VQ encode -> loss + hand-written backward + all-reduce + clip + "
-                         "AdamW + EMA; 5 + --train-steps iterations AFTER the sampling measurement, outside its timed region), "
-                         "reported as the \"train\" object of the JSON line (text_to_sound_synthesis_amd/train_bench.py)")
+                    help="with --full: skip the BASELINE configs[4] leg (the training iteration from the reference's batch, "
+                         "B = 20 per GPU, 19 layers: mel + captions -> BPE + CLIP + VQ encode -> loss + hand-written "
+                         "backward + all-reduce + clip + AdamW + EMA; 5 + --train-steps iterations AFTER the sampling "
+                         "measurement, outside its timed region), reported as the \"train\" object of the JSON line "
+                         "(text_to_sound_synthesis_amd/train_bench.py)")
     ap.add_argument("--no-train-prefetch", action="store_true",
                     help="training leg: run every batch's BPE / CLIP / VQ-encode prologue in line instead of prefetching the next "
-                         "batch's on a side stream beside the replay in flight (GraphSolver.prefetch; +2.7 % measured)")
+                         "batch's on a side stream beside the replay in flight (GraphSolver.prefetch; +2.7 %% measured)")
     ap.add_argument("--train-steps", type=int, default=200, help="timed iterations of the training leg (sustained rate; ~15 s)")
-    ap.add_argument("--train-leg", action="store_true", help=argparse.SUPPRESS)   # (round-4 spelling; the leg is on by default)
+    ap.add_argument("--train-leg", action="store_true", help=argparse.SUPPRESS)   # (round-4 spelling; --full runs the leg)
     ap.add_argument("--collectives-selftest", action="store_true",
                     help="rendezvous + the path's collectives only (all-reduce of ones, caption scatter, waveform gather, one "
                          "gradient bucket) on stand-in tensors, no HIP kernels: backend nccl on GPUs, gloo without -- what "
@@ -79,9 +86,9 @@ def parse():
     ap.add_argument("--side-leg-limit", type=float, default=480.0,
                     help="N > 1: seconds the legs AFTER the timed region may take (roofline, stage split, communicator check, "
                          "training leg) before the line is printed without what is missing (HeadlineGuard)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--stage-times", action="store_true", help="print a per-stage split to stderr")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline leg")
+    ap.add_argument("--stage-times", action="store_true", help="with --full: print the per-stage split to stderr")
     ap.add_argument("--roofline-steps", type=int, default=12,
                     help="denoiser steps of the profiled roofline leg (HIP events around every GEMM launch)")
     ap.add_argument("--roofline-warm", type=int, default=10, help="un-profiled steps before them")
@@ -814,13 +821,13 @@ def main():
     def leg_cpu_baseline():
         line["cpu_baseline"] = cpu_baseline(args.n_layer, args.codes, T)
 
-    # (name the error is filed under, the leg, who runs it, whether it contains collectives)
+    # (name the error is filed under, the leg, who runs it, whether it contains collectives); a plain run has none
     legs = [("host_copy", leg_host_copy, rank == 0 and world == 1 and not args.transformer_only, False),
             ("roofline", leg_roofline, rank == 0 and not args.no_roofline, False),
             ("stage_ms", leg_stage_split, not args.transformer_only, True),
             ("rccl", leg_communicator, world > 1, True),
             ("train", leg_train, not args.no_train_leg, True),
-            ("cpu_baseline", leg_cpu_baseline, rank == 0 and world == 1 and not args.no_cpu_baseline, False)]
+            ("cpu_baseline", leg_cpu_baseline, rank == 0 and world == 1 and not args.no_cpu_baseline, False)] if args.full else []
     in_step = run_side_legs(legs, world, rank, line)
     if not guard.finish():
         time.sleep(3600)                          # the guard's timer is printing the line and ends the process

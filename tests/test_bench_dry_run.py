@@ -63,7 +63,7 @@ def test_bench_main_prints_one_line_when_every_device_leg_fails(monkeypatch, cap
     spec.loader.exec_module(bench)
     bench.torch = _TorchProxy()
     monkeypatch.setattr(sys, "argv", ["bench.py", "--batch", str(B), "--n-layer", "2", "--steps", "2", "--warmup", "1",
-                                      "--no-cpu-baseline", "--side-leg-limit", "600"])
+                                      "--full", "--no-cpu-baseline", "--side-leg-limit", "600"])
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         monkeypatch.delenv(k, raising=False)
     grad = torch.is_grad_enabled()
@@ -175,19 +175,15 @@ def _main_worker(rank, world, port, outdir, extra):
     sys.stderr.flush()
 
 
-@pytest.mark.parametrize("train_leg", [True, False])
-def test_bench_main_two_ranks_print_one_line_and_exit_0(tmp_path, train_leg):
-    """The N-rank control flow of main() on CPU (gloo): timed loop with scatter / gather, the stage split's all-reduce, the
-    communicator check, then (train_leg) a collective leg that fails on both ranks -- each rank skips what is collective after
-    it, rank 0 prints the ONE line, both exit 0 without tearing the process group down -- or (--no-train-leg) the normal end:
-    the line, then destroy_process_group."""
+def _two_ranks(tmp_path, extra):
+    """`bench.py --gpus 2` + extra on two gloo ranks (_main_worker): both must exit 0 and rank 0 alone print ONE line.
+    Returns (that line, rank 1's stderr)."""
     import socket
     import torch.multiprocessing as mp
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     ctx = mp.get_context("spawn")
-    extra = [] if train_leg else ["--no-train-leg"]
     procs = [ctx.Process(target=_main_worker, args=(r, 2, port, str(tmp_path), extra)) for r in range(2)]
     for p in procs:
         p.start()
@@ -197,14 +193,70 @@ def test_bench_main_two_ranks_print_one_line_and_exit_0(tmp_path, train_leg):
     out0, out1 = (open(os.path.join(str(tmp_path), "out%d" % r)).read() for r in range(2))
     lines = [l for l in out0.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and not [l for l in out1.splitlines() if l.startswith("{")]
-    line = json.loads(lines[0])
+    return json.loads(lines[0]), open(os.path.join(str(tmp_path), "err1")).read()
+
+
+@pytest.mark.parametrize("train_leg", [True, False])
+def test_bench_main_two_ranks_print_one_line_and_exit_0(tmp_path, train_leg):
+    """The N-rank control flow of main() --full on CPU (gloo): timed loop with scatter / gather, the stage split's all-reduce,
+    the communicator check, then (train_leg) a collective leg that fails on both ranks -- each rank skips what is collective
+    after it, rank 0 prints the ONE line, both exit 0 without tearing the process group down -- or (--no-train-leg) the
+    normal end: the line, then destroy_process_group."""
+    line, err1 = _two_ranks(tmp_path, ["--full"] if train_leg else ["--full", "--no-train-leg"])
     assert line["n_gpus"] == 2 and line["config"]["global_batch"] == 4 and line["value"] > 0 and "incomplete" not in line
     assert line["rccl"]["rccl_ranks"] == 2 and line["rccl"]["backend"] == "gloo" and "ms_per_step_per_rank" in line["rccl"]
     assert "max_over_ranks" in line["stage_ms"]
     assert line["roofline"]["error"].startswith("DiffsoundHipError")      # rank 0's local leg: costs nothing collective
     assert "host_copy" not in line and "cpu_baseline" not in line          # one-GPU legs
-    err1 = open(os.path.join(str(tmp_path), "err1")).read()
     if train_leg:
         assert line["train"]["error"].startswith("RuntimeError: No HIP GPUs") and "side leg 'train' failed on rank 1" in err1
     else:
         assert "train" not in line and "side leg" not in err1
+
+
+HEADLINE_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                 "vs_baseline", "dtype", "data", "config"}
+
+
+def test_bench_plain_run_prints_the_headline_alone(monkeypatch, capsys):
+    """Without --full: warm-up, the timed steps and the line -- no side leg runs, whatever the --no-* options say: no extra
+    step after the timed ones (stage split), no training leg, no CPU baseline, no other key in the line."""
+    from text_to_sound_synthesis_amd import train_bench
+    from text_to_sound_synthesis_amd.modeling import dalle, diffusion, vocoder
+    B, calls, legs = 2, [], []
+
+    def fwd(self, mel, **kw):
+        calls.append(None)
+        return torch.zeros(mel.shape[0], 1, 217088)
+    monkeypatch.setattr(diffusion.DiffusionTransformer, "sample",
+                        lambda self, **kw: {"content_token": torch.zeros(kw["condition_token"].shape[0], 265, dtype=torch.long)})
+    monkeypatch.setattr(dalle.DALLE, "decode_to_img", lambda self, index, zshape, stage="first": torch.zeros(index.shape[0], 1, 80, 848))
+    monkeypatch.setattr(vocoder.Generator, "forward", fwd)
+    monkeypatch.setattr(train_bench, "run", lambda **kw: legs.append("train"))
+    bench = _load_bench()
+    bench.torch = _TorchProxy()
+    bench.cpu_baseline = lambda *a: legs.append("cpu_baseline")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--batch", str(B), "--n-layer", "2", "--steps", "3", "--warmup", "2"])
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    grad = torch.is_grad_enabled()
+    try:
+        bench.main()
+    finally:
+        torch.set_grad_enabled(grad)
+    out, err = capsys.readouterr()
+    lines = [l for l in out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out
+    line = json.loads(lines[0])
+    assert set(line) == HEADLINE_KEYS, sorted(set(line) ^ HEADLINE_KEYS)
+    assert line["n_gpus"] == 1 and line["steps"] == 3 and line["warmup"] == 2 and line["value"] > 0
+    assert len(calls) == 5 and legs == [] and "side leg" not in err      # 2 warm-up + 3 timed steps, nothing after them
+
+
+def test_bench_plain_run_two_ranks_prints_the_headline_alone(tmp_path):
+    """Without --full on two gloo ranks: the timed loop's scatter / gather, then the line -- no stage split, communicator
+    check or training leg -- and both ranks end normally."""
+    line, err1 = _two_ranks(tmp_path, [])
+    assert set(line) == HEADLINE_KEYS, sorted(set(line) ^ HEADLINE_KEYS)
+    assert line["n_gpus"] == 2 and line["config"]["global_batch"] == 4 and line["value"] > 0
+    assert "side leg" not in err1

@@ -15,5 +15,5 @@ d = json.load(open("$O/bench_train_100_hi$hi.json"))
 print("monitor hi $hi:", {k: d[k] for k in ("value", "recaptures", "monitor_log2", "loss_scale_exp", "loss", "grad_norm")})
 PY
 done 2>&1 | tee $O/monitor_ab.txt
-timeout 300 python bench.py > $O/bench_default.json 2> $O/bench.err
+timeout 300 python bench.py --full > $O/bench_default.json 2> $O/bench.err
 cut -c1-600 $O/bench_default.json

@@ -7,7 +7,7 @@ O=gpurun_out/${1:-r06g}
 mkdir -p $O
 export PYTHONUNBUFFERED=1
 run() {   # name, lib, mode
-  DIFFSOUND_LIB=$2 DS_LNFOLD_PROBE=$3 timeout 300 python bench.py --no-train-leg --no-cpu-baseline --steps 4 --warmup 2 > $O/bench_$1.json 2> $O/bench_$1.err
+  DIFFSOUND_LIB=$2 DS_LNFOLD_PROBE=$3 timeout 300 python bench.py --full --no-train-leg --no-cpu-baseline --steps 4 --warmup 2 > $O/bench_$1.json 2> $O/bench_$1.err
   python - <<PY
 import json
 d = json.load(open("$O/bench_$1.json"))

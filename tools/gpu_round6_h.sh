@@ -9,7 +9,7 @@ timeout 600 python -m pytest tests/test_hip_train_batch.py tests/test_hip_rccl.p
 tail -3 $O/train_batch_tests.log
 bash tools/profile_round.sh $T > $O/profile_round.log 2>&1; echo "profile_round rc=$?" | tee -a $O/rc.txt
 cut -c1-3000 $O/${T}_bench_default.json
-timeout 600 python bench.py --steps 20 --warmup 2 --no-cpu-baseline > $O/bench_steps20.json 2> $O/bench_steps20.err; echo "bench20 rc=$?" | tee -a $O/rc.txt
+timeout 600 python bench.py --full --steps 20 --warmup 2 --no-cpu-baseline > $O/bench_steps20.json 2> $O/bench_steps20.err; echo "bench20 rc=$?" | tee -a $O/rc.txt
 cut -c1-400 $O/bench_steps20.json
 bash tools/gpu_round6_g.sh $T 2>&1 | tee $O/ln_fold_probe.txt
 du -sh $O

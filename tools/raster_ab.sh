@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for V in product gm8 gm2; do
     if [ $V = product ]; then unset DIFFSOUND_LIB; else export DIFFSOUND_LIB=$ROOT/gpurun_ab_$V.so; fi
-    python "$ROOT/bench.py" --steps 2 --warmup 1 --no-train-leg --no-cpu-baseline > "$OUT/bench_$V.json" 2> "$OUT/bench_$V.err"
+    python "$ROOT/bench.py" --full --steps 2 --warmup 1 --no-train-leg --no-cpu-baseline > "$OUT/bench_$V.json" 2> "$OUT/bench_$V.err"
     for SET in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do
         NAME=$(echo "$SET" | tr ' ' '_')
         timeout 300 rocprofv3 --pmc $SET --kernel-trace -d "$OUT/pmc_$V/$NAME" -o p --output-format csv -- python "$ROOT/tools/pmc_step.py" > "$OUT/pmc_${V}_$NAME.log" 2>&1
