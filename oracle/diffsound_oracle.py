@@ -409,6 +409,14 @@ def codebook_gather(sd, tokens, hw=(5, 53), pfx="content_codec."):
 
 
 # --------------------------------------------------------------------------- A13 / A14
+def _rec(record, name, a):
+    """record[name] = (max |a|, median |a|): the operand of a conv whose HIP counterpart splits it into two fp16 planes"""
+    if record is not None:
+        m = a.detach().abs().flatten()
+        record[name] = (float(m.max()), float(m.median()))
+    return a
+
+
 def _gn_swish(sd, name, x):
     """Normalize = GroupNorm(32, C, eps 1e-6) (model.py:34-35) then swish (:29-31)."""
     h = F.group_norm(x, 32, sd[name + ".weight"], sd[name + ".bias"], eps=1e-6)
@@ -419,10 +427,10 @@ def _conv2d(sd, name, x, pad):
     return F.conv2d(x, sd[name + ".weight"], sd[name + ".bias"], padding=pad)
 
 
-def _res_block(sd, pfx, x):
+def _res_block(sd, pfx, x, record=None):
     """ResnetBlock.forward with temb=None, model.py:131-151."""
-    h = _conv2d(sd, pfx + "conv1", _gn_swish(sd, pfx + "norm1", x), 1)
-    h = _conv2d(sd, pfx + "conv2", _gn_swish(sd, pfx + "norm2", h), 1)
+    h = _conv2d(sd, pfx + "conv1", _rec(record, pfx + "conv1", _gn_swish(sd, pfx + "norm1", x)), 1)
+    h = _conv2d(sd, pfx + "conv2", _rec(record, pfx + "conv2", _gn_swish(sd, pfx + "norm2", h)), 1)
     if (pfx + "nin_shortcut.weight") in sd:
         x = _conv2d(sd, pfx + "nin_shortcut", x, 0)
     return x + h
@@ -441,26 +449,27 @@ def _attn_block(sd, pfx, x):
 
 
 def vq_decode(sd, quant, pfx="content_codec.", num_resolutions=5, num_res_blocks=2,
-              taps=None):
+              taps=None, record=None):
     """VQModel.decode (spec_codec/vqgan.py:62-65) = post_quant_conv + Decoder.forward
     (specvqgan/modules/diffusionmodules/model.py:640-671).  `taps` (a dict) receives
-    intermediate activations for debugging the HIP path."""
+    intermediate activations for debugging the HIP path; `record` (a dict) receives (max, median) of |operand| of
+    every conv whose HIP counterpart splits its operand into fp16 planes (keyed by the conv's state-dict name)."""
     d = pfx + "decoder."
     h = _conv2d(sd, pfx + "post_quant_conv", quant, 0)
-    h = _conv2d(sd, d + "conv_in", h, 1)
-    h = _res_block(sd, d + "mid.block_1.", h)
+    h = _conv2d(sd, d + "conv_in", _rec(record, d + "conv_in", h), 1)
+    h = _res_block(sd, d + "mid.block_1.", h, record)
     h = _attn_block(sd, d + "mid.attn_1.", h)
-    h = _res_block(sd, d + "mid.block_2.", h)
+    h = _res_block(sd, d + "mid.block_2.", h, record)
     if taps is not None:
         taps["mid"] = h
     for lvl in reversed(range(num_resolutions)):
         for ib in range(num_res_blocks + 1):
-            h = _res_block(sd, d + "up.%d.block.%d." % (lvl, ib), h)
+            h = _res_block(sd, d + "up.%d.block.%d." % (lvl, ib), h, record)
             if (d + "up.%d.attn.%d.norm.weight" % (lvl, ib)) in sd:
                 h = _attn_block(sd, d + "up.%d.attn.%d." % (lvl, ib), h)
         if lvl != 0:
             h = F.interpolate(h, scale_factor=2.0, mode="nearest")    # Upsample, model.py:48-52
-            h = _conv2d(sd, d + "up.%d.upsample.conv" % lvl, h, 1)
+            h = _conv2d(sd, d + "up.%d.upsample.conv" % lvl, _rec(record, d + "up.%d.upsample.conv" % lvl, h), 1)
         if taps is not None:
             taps["up%d" % lvl] = h
     h = _gn_swish(sd, d + "norm_out", h)
@@ -473,25 +482,25 @@ def decode_tokens(sd, tokens, pfx="content_codec."):
 
 
 # --------------------------------------------------------------------------- scope row 8f-2
-def vq_encoder(sd, x, pfx="content_codec.", num_resolutions=5, num_res_blocks=2):
+def vq_encoder(sd, x, pfx="content_codec.", num_resolutions=5, num_res_blocks=2, record=None):
     """Encoder.forward (specvqgan/modules/diffusionmodules/model.py:467-500) + quant_conv
     (spec_codec/vqgan.py:54-56): mel image [B, 1, 80, 848] -> pre-quantisation latent [B, 256, 5, 53].
     Downsample = zero pad (0,1,0,1) then 3x3 stride-2 conv (:60-77); attention only where the blocks carry it
-    (the 53-wide level)."""
+    (the 53-wide level).  `record`: as vq_decode's."""
     e = pfx + "encoder."
     h = _conv2d(sd, e + "conv_in", x, 1)
     for lvl in range(num_resolutions):
         for ib in range(num_res_blocks):
-            h = _res_block(sd, e + "down.%d.block.%d." % (lvl, ib), h)
+            h = _res_block(sd, e + "down.%d.block.%d." % (lvl, ib), h, record)
             if (e + "down.%d.attn.%d.norm.weight" % (lvl, ib)) in sd:
                 h = _attn_block(sd, e + "down.%d.attn.%d." % (lvl, ib), h)
         if lvl != num_resolutions - 1:
             name = e + "down.%d.downsample.conv" % lvl
-            h = F.conv2d(F.pad(h, (0, 1, 0, 1)), sd[name + ".weight"], sd[name + ".bias"], stride=2)
-    h = _res_block(sd, e + "mid.block_1.", h)
+            h = F.conv2d(F.pad(_rec(record, name, h), (0, 1, 0, 1)), sd[name + ".weight"], sd[name + ".bias"], stride=2)
+    h = _res_block(sd, e + "mid.block_1.", h, record)
     h = _attn_block(sd, e + "mid.attn_1.", h)
-    h = _res_block(sd, e + "mid.block_2.", h)
-    h = _conv2d(sd, e + "conv_out", _gn_swish(sd, e + "norm_out", h), 1)
+    h = _res_block(sd, e + "mid.block_2.", h, record)
+    h = _conv2d(sd, e + "conv_out", _rec(record, e + "conv_out", _gn_swish(sd, e + "norm_out", h)), 1)
     return _conv2d(sd, pfx + "quant_conv", h, 0)
 
 
@@ -547,25 +556,25 @@ def _wn(sd, name):
     return g * v / n
 
 
-def melgan_generator(sd, mel, pfx="model.", ratios=(8, 8, 2, 2), n_res=3):
+def melgan_generator(sd, mel, pfx="model.", ratios=(8, 8, 2, 2), n_res=3, record=None):
     """Generator.forward, vocoder/modules.py:88-130.  mel [B, 80, T] in [0,1] ->
-    waveform [B, 1, 256*T]."""
+    waveform [B, 1, 256*T].  `record`: as vq_decode's (every layer but the exact-fp32 final conv)."""
     lrelu = lambda x: F.leaky_relu(x, 0.2)
     i = 1
-    x = F.conv1d(F.pad(mel, (3, 3), mode="reflect"), _wn(sd, pfx + "1"), sd[pfx + "1.bias"])
+    x = F.conv1d(F.pad(_rec(record, pfx + "1", mel), (3, 3), mode="reflect"), _wn(sd, pfx + "1"), sd[pfx + "1.bias"])
     i = 2
     for r in ratios:
         # LeakyReLU at i, WNConvTranspose1d at i+1: k=2r, s=r, p=r//2+r%2, out_pad=r%2
-        x = F.conv_transpose1d(lrelu(x), _wn(sd, pfx + "%d" % (i + 1)), sd[pfx + "%d.bias" % (i + 1)],
-                               stride=r, padding=r // 2 + r % 2, output_padding=r % 2)
+        x = F.conv_transpose1d(_rec(record, pfx + "%d" % (i + 1), lrelu(x)), _wn(sd, pfx + "%d" % (i + 1)),
+                               sd[pfx + "%d.bias" % (i + 1)], stride=r, padding=r // 2 + r % 2, output_padding=r % 2)
         i += 2
         for j in range(n_res):
             b = pfx + "%d." % i
             dil = 3 ** j
-            h = F.pad(lrelu(x), (dil, dil), mode="reflect")
+            h = F.pad(_rec(record, b + "block.2", lrelu(x)), (dil, dil), mode="reflect")
             h = F.conv1d(h, _wn(sd, b + "block.2"), sd[b + "block.2.bias"], dilation=dil)
-            h = F.conv1d(lrelu(h), _wn(sd, b + "block.4"), sd[b + "block.4.bias"])
-            x = F.conv1d(x, _wn(sd, b + "shortcut"), sd[b + "shortcut.bias"]) + h
+            h = F.conv1d(_rec(record, b + "block.4", lrelu(h)), _wn(sd, b + "block.4"), sd[b + "block.4.bias"])
+            x = F.conv1d(_rec(record, b + "shortcut", x), _wn(sd, b + "shortcut"), sd[b + "shortcut.bias"]) + h
             i += 1
     x = F.pad(lrelu(x), (3, 3), mode="reflect")
     x = F.conv1d(x, _wn(sd, pfx + "%d" % (i + 2)), sd[pfx + "%d.bias" % (i + 2)])

@@ -10,9 +10,12 @@
 // result is fp32-class; tests/test_hip_split_gemm.py measures both against float64.
 // fp16's narrow exponent range is handled with exact power-of-two scaling: the weights are
 // pre-multiplied by 2^s (s per matrix, max |W'| in [2^13, 2^14)), which puts w1 = fp16(W' - w0) in the
-// normal range, and the epilogue multiplies by out_scale = 2^-s.  Activations are used unscaled: they
-// must stay below 65504 (true for this network: LayerNorm outputs, attention outputs, GELU2 outputs);
-// an a1 that falls into the fp16 subnormal range keeps an absolute precision of 2^-25.
+// normal range, and the epilogue multiplies by out_scale = 2^-s.  Activations are used unscaled, so the split is
+// fp32-class only for |a| in about [2^-3, 65504].  Above 65504 both planes saturate (anything past 131008 becomes
+// 131008).  Below 2^-3 a1 is an fp16 subnormal and a keeps an absolute precision of 2^-25: the error of a dot
+// product is then at most 2^-25 * sum |w| on top of the fp32-class term.  The denoiser's operands are normalised
+// (LayerNorm, attention and GELU2 outputs).  The codec's and the vocoder's raw-stream operands are not: VQModel.decode
+// and Generator.forward check them against 65504 and recompute past it in the strict fp32 mode.
 //
 // 256 threads = 4 waves (2x2), block tile BM x BN x 32, two fp16 planes per operand, unpadded 64-byte LDS
 // rows with an XOR chunk swizzle (conflict-free ds_read_b128 and ds_write_b128), double-buffered LDS (one barrier per k-tile), two register sets

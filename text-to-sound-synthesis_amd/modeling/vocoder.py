@@ -16,11 +16,25 @@ the fp32-class 3-pass split (`conv_precision = "f16x2"`, default) or as gather-G
 The whole batch goes through at once (the reference vocodes sample by sample,
 evaluation/generate_samples_batch.py:183-187).
 """
+import math
+import warnings
+
 import numpy as np
 import torch
 from torch import nn
 
 from .. import _lib
+
+
+# The f16x2 layers split their fp32 operand into fp16 hi + lo without scaling it: fp32-class only for |a| <= 65504.  forward()
+# checks every split operand against this limit and recomputes the call in the strict mode past it (DESIGN.md).
+SPLIT_LIMIT = 65504.0
+# A stage whose stream peaks below QUIET_PEAK on the pack-time probe (a fixed mel in [0, 1]) would split operands whose lo plane
+# is an fp16 subnormal (2^-25 absolute precision).  Its stream is carried scaled by an exact power of two instead, so that the
+# probe's peak lands in [2^3, 2^4): the stage is positively homogeneous (LeakyReLU commutes with a positive scale), so scaling
+# its transposed conv's weights and bias and its blocks' biases by 2^k and the next layer's weights by 2^-k is exact.
+QUIET_PEAK = 0.25
+QUIET_TARGET_LOG2 = 3
 
 
 class _WN(nn.Module):
@@ -79,6 +93,8 @@ class Generator(nn.Module):
         # mode, every layer as a gather-GEMM on the exact-fp32 MFMA (three launches per ResnetBlock, polyphase GEMMs for the
         # transposed convs) -- also what the f16x2 mode falls back to for a shape none of its kernels is built for
         self.conv_precision = "f16x2"
+        # calls recomputed in the strict mode because a split operand exceeded SPLIT_LIMIT (forward)
+        self.range_fallbacks = 0
         self._pk = None
         self._register_load_state_dict_pre_hook(lambda *a, **k: setattr(self, "_pk", None))
 
@@ -119,6 +135,7 @@ class Generator(nn.Module):
         last = layers[i + 2]
         wl = last.folded()                                       # [1, 32, 7] -> [7 taps][32]
         pk["last"] = (wl[0].permute(1, 0).contiguous(), float(last.bias.item()))
+        self._rescale_quiet_stages(pk)
         # fp16 split planes of every GEMM weight (W * 2^s as hi + lo, out_scale = 2^-s) for conv_precision = "f16x2"
         sp = lambda w: _lib.split_f16x2(w.reshape(-1, w.shape[-1]))
         pk["first_s"] = sp(pk["first"][0])
@@ -138,8 +155,41 @@ class Generator(nn.Module):
                 c = rb["c3"][0].shape[0]
                 rb["c3_q"] = _lib.pack_conv_weights(rb["c3_s"][0], c, c, 3) if c % 128 == 0 else None
                 rb["tail_b"] = (rb["c1"][1] + rb["sc"][1]).contiguous()
+                # |h1| <= max row-L1(W3) * max|x| + max|b3|: the bound on the k3 output the single-pass kernel keeps in registers
+                rb["h1_bound"] = (rb["c3"][0].abs().sum(1).max().item(), rb["c3"][1].abs().max().item())
         self._pk = pk
         return pk
+
+    @torch.no_grad()
+    def _rescale_quiet_stages(self, pk):
+        """Fold a power of two 2^k per stage into the fp32 weights (before their split planes exist; pk["stage_log2"]).  k is
+        chosen from one strict-mode pass over a fixed probe mel [1, 80, 64] in [0, 1] that records each stage's peak |stream|
+        (transposed-conv output, block inputs and k3 outputs); k = 0 unless that peak is below QUIET_PEAK.  In the strict mode
+        the result is unchanged: every product and sum is scaled by an exact power of two."""
+        dev = pk["first"][0].device
+        ns = len(pk["stages"])
+        t = torch.arange(64.0, device=dev)[None, None, :]
+        c = torch.arange(80.0, device=dev)[None, :, None]
+        probe = (0.5 + 0.5 * torch.sin(0.37 * c + 0.11 * t * (1.0 + c / 40.0))).contiguous()
+        peak = torch.zeros(ns, device=dev)
+        mode, self.conv_precision = self.conv_precision, "fp32"
+        try:
+            self._forward(probe, 1.0, 0.0, None, pk=pk, stage_peak=peak)
+        finally:
+            self.conv_precision = mode
+        ks = []
+        for m in peak.cpu().tolist():
+            ks.append(QUIET_TARGET_LOG2 - math.floor(math.log2(m)) if 0.0 < m < QUIET_PEAK else 0)
+        prev = 0
+        for st, k in zip(pk["stages"], ks):
+            w, b = st["ct"]
+            st["ct"] = ((w * 2.0 ** (k - prev)).contiguous(), (b * 2.0 ** k).contiguous())
+            for rb in st["res"]:
+                for name in ("c3", "c1", "sc"):
+                    rb[name] = (rb[name][0], (rb[name][1] * 2.0 ** k).contiguous())
+            prev = k
+        pk["last"] = ((pk["last"][0] * 2.0 ** -prev).contiguous(), pk["last"][1])
+        pk["stage_log2"] = ks
 
     def _mm(self, A, w, ws, out, M, N, K, **kw):
         """One gather-GEMM of the stack in the selected arithmetic (w: fp32 weights, ws: their split planes + scale)."""
@@ -152,8 +202,49 @@ class Generator(nn.Module):
     @torch.no_grad()
     def forward(self, x, scale=1.0, shift=0.0):
         """x f32[B, 80, T] -> f32[B, 1, 256 T].  (scale, shift) lets the caller fold the
-        (mel + 1) / 2 of generate_samples_batch.py:182 into the layout change."""
-        pk = self._packed()
+        (mel + 1) / 2 of generate_samples_batch.py:182 into the layout change.  In the f16x2 mode the call records max |operand|
+        of every split layer (one host read at the end); if any exceeds SPLIT_LIMIT, it is recomputed in the strict mode and
+        range_fallbacks counts it."""
+        if self.conv_precision != "f16x2":
+            return self._forward(x, scale, shift, None)
+        amax = torch.zeros(64, device=x.device)
+        bounds = []
+        out = self._forward(x, scale, shift, (amax, bounds, [0]))
+        a = amax.cpu().tolist()
+        peak = max(g * a[i] + o for i, g, o in bounds)
+        if peak <= SPLIT_LIMIT:
+            return out
+        if not self.range_fallbacks:
+            warnings.warn("Generator: a split-fp16 operand reaches %.4g > %g; this call and any other such call runs in the "
+                          "strict fp32 mode (counted in range_fallbacks)" % (peak, SPLIT_LIMIT))
+        self.range_fallbacks += 1
+        self.conv_precision = "fp32"
+        try:
+            return self._forward(x, scale, shift, None)
+        finally:
+            self.conv_precision = "f16x2"
+
+    def _forward(self, x, scale, shift, guard, pk=None, stage_peak=None):
+        """guard = (zeroed device float[64], [], [0]) or None: each split operand tensor gets a slot of max |.| (the third
+        item counts the slots used), and the list receives (slot, gain, offset) per bound: gain * amax[slot] + offset >= max
+        |operand|.  pk: the packed weights to use (default: self._packed()); stage_peak (strict mode only): a zeroed device
+        float[stages] that receives each stage's peak |stream|."""
+        def probe(t, gain=1.0, off=0.0, slot=None):
+            if guard is None:
+                return None
+            if slot is None:
+                slot = guard[2][0]
+                guard[2][0] += 1
+                assert slot < guard[0].numel()
+                _lib.check(_lib.lib().ds_amax(_lib.ptr(t), t.numel(), _lib.ptr_off(guard[0], slot), _lib.stream()))
+            guard[1].append((slot, gain, off))
+            return slot
+
+        def peak(t, s):
+            if stage_peak is not None:
+                _lib.check(_lib.lib().ds_amax(_lib.ptr(t), t.numel(), _lib.ptr_off(stage_peak, s), _lib.stream()))
+        if pk is None:
+            pk = self._packed()
         B, Cm, T = x.shape
         dev = x.device
         x = x.contiguous().float()
@@ -161,15 +252,17 @@ class Generator(nn.Module):
         h = torch.empty(B, T, cpad, device=dev)
         _lib.check(_lib.lib().ds_mel_to_cl(_lib.ptr(x), _lib.ptr(h), B, Cm, T, cpad, float(scale), float(shift),
                                            _lib.stream()))
+        probe(h)
         w, b = pk["first"]
         c = w.shape[0]
         y = torch.empty(B, T, c, device=dev)
-        self._mm(h, w, pk["first_s"], y, B * T, c, 7 * cpad, bias=b, loader=_lib.LOAD_CONV1D, Cin=cpad, Wd=T, taps=7, dil=1)
+        self._mm(h, w, pk.get("first_s"), y, B * T, c, 7 * cpad, bias=b, loader=_lib.LOAD_CONV1D, Cin=cpad, Wd=T, taps=7, dil=1)
         h = y
-        for st in pk["stages"]:
+        for si, st in enumerate(pk["stages"]):
             r, cin, cout = st["r"], st["cin"], st["cout"]
             w, b = st["ct"]
             y = torch.empty(B, T * r, cout, device=dev)
+            probe(h)                                             # |LReLU(h)| <= |h|
             if self.conv_precision == "f16x2" and st["ct_q"] is not None:
                 _lib.check(_lib.lib().ds_convt1d_f16x2(_lib.ptr(h), _lib.ptr(st["ct_q"]), st["ct_q"].numel(), st["ct_s"][1], _lib.ptr(b),
                                                        _lib.ptr(y), B, T, cin, cout, r, r // 2 + r % 2, 1, _lib.stream()))
@@ -177,14 +270,16 @@ class Generator(nn.Module):
                 _lib.check(_lib.lib().ds_melgan_convt2(_lib.ptr(h), _lib.ptr(st["ct_s"][0]), r * cout * 2 * cin, st["ct_s"][1], _lib.ptr(b),
                                                        _lib.ptr(y), B, T, cin, cout, _lib.stream()))
             else:
-                self._mm(h, w, st["ct_s"], y, B * T, cout, 2 * cin, bias=b, ldc=cout, loader=_lib.LOAD_CONVT1D,
+                self._mm(h, w, st.get("ct_s"), y, B * T, cout, 2 * cin, bias=b, ldc=cout, loader=_lib.LOAD_CONVT1D,
                          pro=_lib.PRO_LRELU, store=_lib.STORE_CONVT, groups=r, w_gstride=cout * 2 * cin, Cin=cin, Wd=T,
                          ct_r=r, ct_p=r // 2 + r % 2, ct_tin=T)
             h, T = y, T * r
+            peak(h, si)
             for rb in st["res"]:
                 M = B * T
                 sc = torch.empty(B, T, cout, device=dev)
                 if self.conv_precision == "f16x2":
+                    xs = probe(h)                                # the k3 conv's and the tail's x operand
                     # the whole block behind one entry: ONE kernel where it is built (h1 = None), else the dilated k3 conv
                     # into h1, then [LReLU(h1) | h] x [W2 | Ws]^T
                     one_pass = _lib.lib().ds_melgan_resblock_fused_ok(T, cout, rb["dil"])
@@ -196,6 +291,7 @@ class Generator(nn.Module):
                         L = _lib.lib()
                         _lib.check(L.ds_conv1d_k3_f16x2(_lib.ptr(h), _lib.ptr(rb["c3_q"]), rb["c3_q"].numel(), s3, _lib.ptr(rb["c3"][1]),
                                                         _lib.ptr(h1), B, T, cout, cout, rb["dil"], 1, _lib.stream()))
+                        probe(h1)
                         _lib.check(L.ds_melgan_resblock_tail(_lib.ptr(h1), _lib.ptr(h), _lib.ptr(w2), cout * 2 * cout, osc,
                                                              _lib.ptr(rb["tail_b"]), _lib.ptr(sc), M, cout, _lib.stream()))
                         h = sc
@@ -203,12 +299,18 @@ class Generator(nn.Module):
                     _lib.check(_lib.lib().ds_melgan_resblock(_lib.ptr(h), _lib.ptr(w3), cout * 3 * cout, s3, _lib.ptr(rb["c3"][1]),
                                                              _lib.ptr(w2), cout * 2 * cout, osc, _lib.ptr(rb["tail_b"]), _lib.ptr(h1),
                                                              _lib.ptr(sc), B, T, cout, rb["dil"], _lib.stream()))
+                    if one_pass:
+                        probe(None, *rb["h1_bound"], slot=xs)    # h1 never leaves the kernel: bounded from x
+                    else:
+                        probe(h1)
                 else:
                     h1 = torch.empty(B, T, cout, device=dev)
-                    self._mm(h, rb["c3"][0], rb["c3_s"], h1, M, cout, 3 * cout, bias=rb["c3"][1], loader=_lib.LOAD_CONV1D,
+                    self._mm(h, rb["c3"][0], rb.get("c3_s"), h1, M, cout, 3 * cout, bias=rb["c3"][1], loader=_lib.LOAD_CONV1D,
                              pro=_lib.PRO_LRELU, Cin=cout, Wd=T, taps=3, dil=rb["dil"])
-                    self._mm(h, rb["sc"][0], rb["sc_s"], sc, M, cout, cout, bias=rb["sc"][1])
-                    self._mm(h1, rb["c1"][0], rb["c1_s"], sc, M, cout, cout, bias=rb["c1"][1], R=sc, pro=_lib.PRO_LRELU)
+                    self._mm(h, rb["sc"][0], rb.get("sc_s"), sc, M, cout, cout, bias=rb["sc"][1])
+                    self._mm(h1, rb["c1"][0], rb.get("c1_s"), sc, M, cout, cout, bias=rb["c1"][1], R=sc, pro=_lib.PRO_LRELU)
+                    peak(h1, si)
+                    peak(sc, si)
                 h = sc
         wl, bl = pk["last"]
         out = torch.empty(B, 1, T, device=dev)

@@ -12,6 +12,9 @@ while staging its A tile together with swish; nearest-2x upsampling is index mat
 loader; the 512-channel spatial attention runs as two batched GEMMs around a row softmax.
 """
 
+import math
+import warnings
+
 import numpy as np
 import torch
 from torch import nn
@@ -21,6 +24,12 @@ from ..config import instantiate_from_config
 
 
 HALO_MIN_ROWS = 5      # smallest image height the halo-tiled 3x3 kernel takes (the 5 x 53 token grid)
+# The f16x2 convs split their fp32 operand a into fp16 hi + lo without scaling it: fp32-class only for |a| <= 65504 (fp16's
+# largest finite value; above it the split saturates).  decode() checks its split operands against this limit.
+SPLIT_LIMIT = 65504.0
+# post_quant_conv's output -- conv_in's operand -- is rescaled by an exact power of two chosen at pack time so that the
+# codebook's image lands in [2^9, 2^10): far from the subnormal lo plane, 64x headroom below SPLIT_LIMIT
+PQ_TARGET_LOG2 = 9
 
 
 def Normalize(c):
@@ -237,6 +246,8 @@ class VQModel(nn.Module):
         # ~15 GB live at 64) and the 32-bit element indices inside the kernels ([B][80][848][128] < 2^31 up to B=247);
         # measured at B=64: 0.287 / 0.247 / 0.224 / 0.208 s for chunks of 8 / 16 / 32 / 64 (tools/decode_ab.py)
         self.decode_chunk = 64
+        # decode chunks recomputed in the strict mode because a split operand exceeded SPLIT_LIMIT (_decode_guarded)
+        self.range_fallbacks = 0
         self._register_load_state_dict_pre_hook(lambda *a, **k: (setattr(self, "_pk", None), setattr(self, "_pke", None)))
         if ckpt_path is not None:
             self.init_from_ckpt(ckpt_path, ignore_keys)
@@ -257,14 +268,29 @@ class VQModel(nn.Module):
             return self._pk
         d = self.decoder
         pk = {"pq": _pack_conv1(self.post_quant_conv), "conv_in": _pack_conv3(d.conv_in)}
+        # f16x2 mode: post_quant_conv * 2^k and conv_in's out_scale * 2^-k (exact; the strict mode keeps the plain pair)
+        wq_, bq_ = pk["pq"]
+        img = (self.quantize.embedding.weight.detach().float() @ wq_.t() + bq_).abs().max().item()
+        k = 0 if img == 0.0 else PQ_TARGET_LOG2 - math.floor(math.log2(img))
+        if pk["conv_in"][0].shape[0] % 4:
+            k = 0             # _conv3 would run conv_in on the exact-fp32 weights, which know nothing of out_scale
+        pk["pq_f16x2"] = ((wq_ * 2.0 ** k).contiguous(), (bq_ * 2.0 ** k).contiguous())
+        w_, b_, w2_, sc_, wqq_ = pk["conv_in"]
+        pk["conv_in_f16x2"] = (w_, b_, w2_, sc_ * 2.0 ** -k, wqq_)
+        pk["pq_log2"] = k
+        # GroupNorm-prologue operands never reach HBM: |gamma (x - mu) / sigma + beta| <= max|gamma| sqrt(n - 1) + max|beta|
+        # for a group of n values, and swish does not increase |.|.  (max|gamma|, max|beta|, channels, pixels / H W)
+        pk["gn_bounds"] = []
 
-        def res(b):
+        def res(b, area=1):
             r = {"n1": (b.norm1.weight.detach().float().contiguous(), b.norm1.bias.detach().float().contiguous()),
                  "c1": _pack_conv3(b.conv1),
                  "n2": (b.norm2.weight.detach().float().contiguous(), b.norm2.bias.detach().float().contiguous()),
                  "c2": _pack_conv3(b.conv2), "cin": b.in_channels, "cout": b.out_channels}
             if b.in_channels != b.out_channels:
                 r["nin"] = _pack_conv1(b.nin_shortcut)
+            for n, c in ((r["n1"], b.in_channels), (r["n2"], b.out_channels)):
+                pk["gn_bounds"].append((n[0].abs().max().item(), n[1].abs().max().item(), c, area))
             return r
 
         def att(a):
@@ -278,7 +304,8 @@ class VQModel(nn.Module):
         pk["up"] = []
         for lvl in range(d.num_resolutions):
             u = d.up[lvl]
-            pk["up"].append({"block": [res(b) for b in u.block], "attn": [att(a) for a in u.attn],
+            area = 4 ** (d.num_resolutions - 1 - lvl)
+            pk["up"].append({"block": [res(b, area) for b in u.block], "attn": [att(a) for a in u.attn],
                              "upsample": _pack_conv3(u.upsample.conv) if lvl != 0 else None})
         pk["norm_out"] = (d.norm_out.weight.detach().float().contiguous(), d.norm_out.bias.detach().float().contiguous())
         w = d.conv_out.weight.detach().float()  # [1, C, 3, 3] -> [9 taps][C]
@@ -397,13 +424,21 @@ class VQModel(nn.Module):
                   a_gstride=P * Pp, w_gstride=Cc * Pp, c_gstride=P * Cc)
         return self._conv1(O, B * P, Cc, a["proj"], R=x).view(B, H, W, Cc)
 
+    def gn_operand_bound(self, H, W):
+        """Largest |operand| any GroupNorm-prologue conv of decode() can split on an H x W latent grid (no data needed)."""
+        return max(g * math.sqrt(c / 32 * area * H * W) + b for g, b, c, area in self._packed()["gn_bounds"])
+
     @torch.no_grad()
-    def _decode_cl(self, q, B, H, W):
-        """q: channels-last quant [B, H, W, C] -> mel [B, 1, 16H, 16W]."""
+    def _decode_cl(self, q, B, H, W, amax=None):
+        """q: channels-last quant [B, H, W, C] -> mel [B, 1, 16H, 16W].  amax (f16x2 mode): a zeroed device float[5] that
+        receives max |operand| of conv_in and of the four upsample convs, the split operands that are not normalised."""
         pk, d = self._packed(), self.decoder
         Cz = q.shape[-1]
-        h = self._conv1(q, B * H * W, Cz, pk["pq"]).view(B, H, W, -1)
-        h = self._conv3(h, B, H, W, h.shape[-1], pk["conv_in"])
+        split = self.conv_precision == "f16x2"
+        h = self._conv1(q, B * H * W, Cz, pk["pq_f16x2" if split else "pq"]).view(B, H, W, -1)
+        if amax is not None:
+            _lib.check(_lib.lib().ds_amax(_lib.ptr(h), h.numel(), _lib.ptr(amax), _lib.stream()))
+        h = self._conv3(h, B, H, W, h.shape[-1], pk["conv_in_f16x2" if split else "conv_in"])
         r1, a1, r2 = pk["mid"]
         h = self._res(h, B, H, W, r1)
         h = self._attn(h, B, H, W, a1)
@@ -415,6 +450,8 @@ class VQModel(nn.Module):
                 if u["attn"]:
                     h = self._attn(h, B, H, W, u["attn"][i])
             if lvl != 0:
+                if amax is not None:
+                    _lib.check(_lib.lib().ds_amax(_lib.ptr(h), h.numel(), _lib.ptr_off(amax, lvl), _lib.stream()))
                 H, W = 2 * H, 2 * W
                 h = self._conv3(h, B, H, W, h.shape[-1], u["upsample"], up=1)
         Cc = h.shape[-1]
@@ -474,6 +511,29 @@ class VQModel(nn.Module):
         B, _, H, W = x.shape
         return self._encode_cl(x[:, 0].float().contiguous(), B, H, W).permute(0, 3, 1, 2).contiguous()
 
+    def _decode_guarded(self, q, B, H, W):
+        """_decode_cl with the range guard of the f16x2 mode: if a split operand of this chunk exceeds SPLIT_LIMIT (one host
+        read of five device floats), the chunk is decoded again in the strict "fp32" mode and range_fallbacks counts it.  If
+        the weight-only GroupNorm bound already exceeds it, the chunk goes to the strict mode directly."""
+        if self.conv_precision != "f16x2":
+            return self._decode_cl(q, B, H, W)
+        peak = self.gn_operand_bound(H, W)       # weights only: past the limit, no f16x2 pass is worth running
+        if peak <= SPLIT_LIMIT:
+            amax = torch.zeros(5, device=q.device)
+            out = self._decode_cl(q, B, H, W, amax)
+            peak = float(amax.max().item())
+            if peak <= SPLIT_LIMIT:
+                return out
+        if not self.range_fallbacks:
+            warnings.warn("VQModel.decode: a split-fp16 conv operand reaches %.4g > %g; this chunk and any other such chunk "
+                          "is decoded in the strict fp32 mode (counted in range_fallbacks)" % (peak, SPLIT_LIMIT))
+        self.range_fallbacks += 1
+        self.conv_precision = "fp32"
+        try:
+            return self._decode_cl(q, B, H, W)
+        finally:
+            self.conv_precision = "f16x2"
+
     @torch.no_grad()
     def decode(self, quant):
         """quant f32[B, 256, 5, 53] -> f32[B, 1, 80, 848] (spec_codec/vqgan.py:62-65)."""
@@ -481,7 +541,7 @@ class VQModel(nn.Module):
         outs = []
         for s in range(0, B, self.decode_chunk):
             q = quant[s:s + self.decode_chunk].permute(0, 2, 3, 1).contiguous().float()
-            outs.append(self._decode_cl(q, q.shape[0], H, W))
+            outs.append(self._decode_guarded(q, q.shape[0], H, W))
         return torch.cat(outs, 0) if len(outs) > 1 else outs[0]
 
     @torch.no_grad()
@@ -510,5 +570,5 @@ class VQModel(nn.Module):
             q = torch.empty(b, H, W, E.shape[1], device=tk.device)
             _lib.check(_lib.lib().ds_codebook_gather(_lib.ptr(tk), _lib.ptr(E), _lib.ptr(q), b, H, W, E.shape[1],
                                                      E.shape[0], _lib.stream()))
-            outs.append(self._decode_cl(q, b, H, W))
+            outs.append(self._decode_guarded(q, b, H, W))
         return torch.cat(outs, 0) if len(outs) > 1 else outs[0]

@@ -89,15 +89,86 @@ def _trained_tensor(key, shape, seed):
     return None
 
 
+# ---- "trained-like" statistics for the codec and the vocoder (profile="trained_conv") -----------------------------------
+# The split-fp16 convolutions of the SpecVQGAN codec and the MelGAN vocoder split UN-normalised fp32 activations: the split is
+# fp32-class only for |a| in about [2^-3, 65504].  This profile pushes both networks to the two edges of that band: GroupNorm
+# gains over two decades, Student-t conv weights, residual streams whose hot channels grow level by level to ~2^14 (below
+# 65504) in front of the decoder's upsample convs and the encoder's stride-2 convs, a codebook with O(1) norms and near-duplicate
+# codes, MelGAN weight_g over a decade and a last vocoder stage whose every split operand stays below 2^-3.
+CODEC_HOT = (3, 77)                         # stream channels that run hot (exist at every width: 128 .. 512)
+CODEC_HOT_GAIN = {"decoder": (200.0, 2400.0, 2400.0, 2400.0, 3600.0), "encoder": (2000.0, 1700.0, 2200.0, 2300.0, 6.0)}  # conv2 rows
+MELGAN_QUIET = ("model.18.", "model.19.", "model.20.", "model.21.")   # the last stage: ConvTranspose1d 64 -> 32 + its 3 blocks
+MELGAN_QUIET_GAIN = (4e-5, 0.4)          # weight_g factor of its ConvTranspose1d / of its blocks' convs
+
+
+def _student_t(g, shape, std):
+    z = torch.randn(shape, generator=g)
+    chi = (torch.randn((3,) + tuple(shape), generator=g) ** 2).sum(0) / 3.0
+    return std * z / chi.sqrt() / 3.0 ** 0.5
+
+
+def _trained_conv_tensor(key, shape, seed):
+    g = _gen(seed, "trained_conv:" + key)
+    shape = tuple(shape)
+    leaf = key.rsplit(".", 1)[-1]
+    nd = len(shape)
+    if key.endswith("quantize.embedding.weight"):
+        # O(1) norms; codes 2j + 1 (j < 8) are near-duplicates of codes 2j, so the code search meets argmin near-ties
+        t = torch.randn(shape, generator=g) / shape[1] ** 0.5
+        t[1:16:2] = t[0:16:2] + 1e-3 * torch.randn((8, shape[1]), generator=g) / shape[1] ** 0.5
+        return t
+    if key.startswith("content_codec."):
+        if nd == 1 and leaf == "weight":                         # GroupNorm gains: log-uniform over 0.1 .. 10
+            return 10.0 ** (torch.rand(shape, generator=g) * 2.0 - 1.0)
+        if leaf == "bias":
+            return torch.randn(shape, generator=g) * 0.1
+        if nd == 4:
+            fan_in = shape[1] * shape[2] * shape[3]
+            t = _student_t(g, shape, 1.0 / (3.0 * fan_in) ** 0.5)
+            part = key.split(".")[1]
+            if key.endswith("conv2.weight") and ".block." in key and part in CODEC_HOT_GAIN:
+                # the residual branches keep writing into the hot channels: the stream grows level by level
+                lvl = int(key.split(".up." if part == "decoder" else ".down.")[1].split(".")[0])
+                t[list(CODEC_HOT)] *= CODEC_HOT_GAIN[part][lvl]
+            elif key.endswith("nin_shortcut.weight"):
+                for c in CODEC_HOT:                              # the hot channels survive a change of width
+                    t[c, c] = 1.0
+            return t
+        return None
+    if key.startswith("model."):
+        quiet = key.startswith(MELGAN_QUIET)
+        if leaf == "weight_v":
+            fan_in = 1
+            for s in shape[1:]:
+                fan_in *= s
+            return _student_t(g, shape, 1.0 / fan_in ** 0.5)
+        if leaf == "weight_g":                                   # a factor over a decade around ||v|| (applied below)
+            f = 10.0 ** (torch.rand(shape, generator=g) - 0.5)
+            if quiet:
+                f = f * MELGAN_QUIET_GAIN[int(".block." in key or ".shortcut." in key)]
+            return f
+        if leaf == "bias":
+            return torch.randn(shape, generator=g) * (0.002 if quiet else 0.05)
+    return None
+
+
 def synth_state_dict(shapes, seed=0, profile="init"):
     """shapes: {key: shape}.  Returns {key: tensor}; weight_g follows weight_v.  profile = "trained": the denoiser's
-    tensors (keys under transformer.transformer.) get trained-like statistics, see above; everything else as "init"."""
+    tensors (keys under transformer.transformer.) get trained-like statistics, see above; profile = "trained_conv": the
+    codec's (content_codec.*) and the vocoder's (model.*) tensors do; everything else as "init"."""
+    if profile not in ("init", "trained", "trained_conv"):
+        raise ValueError("unknown profile %r" % (profile,))
     out = {}
+    factor_g = set()
     for k, shp in shapes.items():
         t = None
         if profile == "trained" and (k.startswith("transformer.transformer.") or k.startswith("transformer.blocks.")
                                      or k.startswith("blocks.")):
             t = _trained_tensor(k, shp, seed)
+        elif profile == "trained_conv":
+            t = _trained_conv_tensor(k, shp, seed)
+            if t is not None and k.endswith("weight_g"):
+                factor_g.add(k)
         out[k] = synth_tensor(k, shp, seed) if t is None else t
     for k in list(out):
         if k.endswith("weight_g"):
@@ -105,7 +176,7 @@ def synth_state_dict(shapes, seed=0, profile="init"):
             if v is not None:
                 # torch weight_norm: norm over all dims except 0 (vocoder/modules.py:18-23)
                 nrm = v.reshape(v.shape[0], -1).norm(dim=1).reshape(out[k].shape)
-                out[k] = nrm * (1.0 + 0.1 * out[k])
+                out[k] = nrm * out[k] if k in factor_g else nrm * (1.0 + 0.1 * out[k])
     return out
 
 
