@@ -518,6 +518,21 @@ int ds_stencil7_tanh(const float* taps, int ldt, float bias, float* out, int B, 
 /* mel [B][C][T] -> [B][T][Cpad], y = a*x + b (generate_samples_batch.py:181-182 uses a = b = 0.5) */
 int ds_mel_to_cl(const float* mel, float* out, int B, int C, int T, int Cpad, float a, float b,
                  ds_stream_t stream);
+/* Audio front end: waveform -> log-mel spectrogram in one launch (csrc/stft_mel.hip).  Replaces the librosa chain of
+ * vocoder/mel2wav/extract_mel_spectrogram.py:15-38,141-187 (= Codebook/feature_extraction/extract_mel_spectrogram.py) and
+ * Audio2Mel.forward (vocoder/modules.py:54-69).  Per clip b and frame f:
+ *   x      = wave[b] (f32[B][T]) laid on a zero-extended / truncated length `length` (0: T as it is)
+ *   xp[i]  = x reflected by `pad` samples at both ends (numpy / torch "reflect": the edge sample is not repeated; pad < length)
+ *   S[k]   = | sum_n window[n] xp[256 f + n] e^{-2 pi i k n / 1024} |,  k = 0..512    (FFT in double, |.|^2 rounded to fp32 once,
+ *                                                                                    correctly rounded fp32 sqrt; the rest fp32)
+ *   m[j]   = sum_k mel_basis[j][k] S[k]  over k ascending in [krange[j][0], krange[j][1])
+ *   out[b][j][f - f0] = min(max(a log10(max(m[j], floor)) + c, lo), hi)   for f in [f0, f0 + n_out);  out f32[B][n_mels][n_out]
+ * window f32[1024]; twiddle f64[769][2] = (cos, -sin) of 2 pi m / 512 for m < 512, then of 2 pi k / 1024 for k <= 256; mel_basis f32[n_mels][513], any dense matrix; krange i32[n_mels][2] = a range of each row outside
+ * which it is zero, or NULL (every row is summed over all 513 bins).  n_fft = 1024 and hop = 256 are the only built sizes;
+ * 1 <= n_mels <= 128; floor > 0; lo / hi may be -inf / +inf.  A clip's result is bit-identical whatever the batch around it. */
+int ds_wave_to_mel(const float* wave, int B, int T, int length, int pad, const float* window, const double* twiddle,
+                   const float* mel_basis, const int32_t* krange, int n_mels, int n_fft, int hop, int f0, int n_out,
+                   float a, float c, float lo, float hi, float floor, float* out, ds_stream_t stream);
 
 #ifdef __cplusplus
 }

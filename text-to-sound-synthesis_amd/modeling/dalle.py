@@ -41,14 +41,24 @@ class DALLE(nn.Module):
         return quant_z, indices
 
     @torch.no_grad()
+    def content_image(self, batch):
+        """batch[content key] on the model's device; a batch without it that carries 'audio' (f32[B, T] on the device, or a
+        list of .wav paths / host arrays) gets the mel image from the HIP front end (modeling/melspec.py: the reference's
+        offline extract_mel_spectrogram.py + the dataset's crop and 2 x - 1)."""
+        key = self.content_info["key"]
+        if key not in batch and batch.get("audio") is not None:
+            from .melspec import mel_image_from_audio
+            return mel_image_from_audio(batch["audio"], self.device)
+        cont = batch[key]
+        return cont.to(self.device) if torch.is_tensor(cont) else cont
+
+    @torch.no_grad()
     def prepare_content(self, batch, with_mask=False):
-        """batch[content key] -> {'content_token', 'content_quant'} (dalle_spec.py:107-126, with_mask=False branch)."""
+        """batch[content key] (or batch['audio']) -> {'content_token', 'content_quant'} (dalle_spec.py:107-126, with_mask=False
+        branch)."""
         if with_mask:
             raise NotImplementedError("masked content encoding is not part of the sound pipeline (:118-120)")
-        cont = batch[self.content_info["key"]]
-        if torch.is_tensor(cont):
-            cont = cont.to(self.device)
-        quant_z, indices = self.get_tokens(cont)
+        quant_z, indices = self.get_tokens(self.content_image(batch))
         return {"content_token": indices, "content_quant": quant_z}
 
     @torch.no_grad()
@@ -147,6 +157,8 @@ class DALLE(nn.Module):
             raise NotImplementedError("sample_debug is not part of the sound pipeline")
         self.eval()
         condition = self.prepare_condition(batch)
+        if self.content_info["key"] not in batch and batch.get("audio") is not None:     # encode the audio once
+            batch = dict(batch, **{self.content_info["key"]: self.content_image(batch)})
         content = self.prepare_content(batch)
         out = {"input_image": batch[self.content_info["key"]]}
         zshape = content["content_quant"].shape

@@ -321,3 +321,45 @@ class Generator(nn.Module):
         _lib.gemm(h, wl, taps, B * T, 7, wl.shape[1], ldc=8, pro=_lib.PRO_LRELU)
         _lib.check(_lib.lib().ds_stencil7_tanh(_lib.ptr(taps), 8, bl, _lib.ptr(out), B, T, _lib.stream()))
         return out
+
+
+class Audio2Mel(nn.Module):
+    """Drop-in for vocoder/modules.py:26-69: same constructor keywords and defaults, same buffers (`mel_basis` f32[80, 513],
+    `window` f32[1024]: a checkpoint's filterbank loads over the computed one), forward(audio f32[B, 1, T]) ->
+    log10(max(mel_basis |STFT|, 1e-5)) f32[B, n_mel_channels, T / 256] -- as ONE launch of ds_wave_to_mel (csrc/stft_mel.hip)
+    instead of F.pad -> torch.stft -> sqrt -> matmul -> clamp -> log10 (the reference's torch.stft call, without
+    return_complex, does not run on torch >= 2.0).  n_fft 1024 / hop 256 / win 1024 are the built sizes; others raise.
+    No CPU path: a host tensor raises."""
+
+    def __init__(self, n_fft=1024, hop_length=256, win_length=1024, sampling_rate=22050, n_mel_channels=80, mel_fmin=0.0,
+                 mel_fmax=None):
+        super().__init__()
+        from .. import audio
+        if (n_fft, hop_length, win_length) != (audio.N_FFT, audio.HOP, audio.N_FFT):
+            raise NotImplementedError("ds_wave_to_mel is built for n_fft = win_length = 1024, hop_length = 256")
+        self.register_buffer("mel_basis", audio.mel_filterbank(sampling_rate, n_fft, n_mel_channels, mel_fmin, mel_fmax))
+        self.register_buffer("window", audio.hann_window(win_length))
+        self.n_fft = n_fft
+        self.hop_length = hop_length
+        self.win_length = win_length
+        self.sampling_rate = sampling_rate
+        self.n_mel_channels = n_mel_channels
+        self._ranges = None          # (mel_basis version, device, i32[n_mels, 2]): the rows' non-zero ranges, found at pack time
+
+    def _krange(self):
+        key = (self.mel_basis._version, self.mel_basis.data_ptr())
+        if self._ranges is None or self._ranges[0] != key:
+            from .. import audio
+            self._ranges = (key, audio.row_ranges(self.mel_basis).to(self.mel_basis.device))
+        return self._ranges[1]
+
+    @torch.no_grad()
+    def forward(self, audio):
+        from .. import audio as A
+        if audio.dim() != 3 or audio.shape[1] != 1:
+            raise ValueError("audio must be f32[B, 1, T]")
+        if not audio.is_cuda or not self.mel_basis.is_cuda:
+            raise _lib.DiffsoundHipError("Audio2Mel: input and module must be on a GPU: the HIP path has no CPU fallback")
+        p = (self.n_fft - self.hop_length) // 2
+        return A.wave_to_mel(audio[:, 0], self.window, self.mel_basis, self._krange(), pad=p, length=0, a=1.0, c=0.0,
+                             floor=1e-5)

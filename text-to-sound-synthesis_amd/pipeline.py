@@ -99,6 +99,46 @@ class Diffsound:
         return (mel[:, 0] + 1) / 2, wave, out["content_token"]
 
     @torch.no_grad()
+    def generate_sample_from_audio(self, audio, text, filter_ratio=0.5, truncation_rate=0.85, save_root=None):
+        """Re-sample given recordings under new captions: audio (f32[B, T] at 22 050 Hz on the device, or a list of `.wav`
+        paths / host arrays) -> mel (modeling/melspec.py, one HIP launch) -> VQ tokens -> diffused forward to
+        t = int(T * filter_ratio) - 1 and denoised from there under `text` (a list of B captions, token ids or embeddings, as in
+        generate_sample_with_condition) -> decode -> vocoder.  Returns (mel01 f32[B,80,848], wave f32[B,1,217088] or None,
+        tokens); with save_root also writes `{i:06d}.npy` and, with a vocoder, `{i:06d}.wav` like the other drivers."""
+        import numpy as np
+        if isinstance(text, (list, tuple, str)):
+            batch = {"text": [text] if isinstance(text, str) else list(text)}
+        elif text.dtype == torch.long:
+            batch = {"condition_token": text}
+        else:
+            batch = {"condition_embed_token": text}
+        model = self.model
+        cond = model.prepare_condition(batch)
+        content = model.prepare_content({"audio": audio})
+        tr = model.transformer
+        keep = tr.truncation_r, tr.truncation_k
+        tr.truncation_r, tr.truncation_k = float(truncation_rate), None
+        try:
+            out = tr.sample(condition_token=cond.get("condition_token"), condition_mask=cond.get("condition_mask"),
+                            condition_embed=cond.get("condition_embed_token"), content_token=content["content_token"],
+                            filter_ratio=filter_ratio, print_log=False)
+        finally:
+            tr.truncation_r, tr.truncation_k = keep
+        tokens = out["content_token"]
+        mel = model.decode_to_img(tokens, content["content_quant"].shape)
+        wave = None if self.vocoder is None else self.vocoder(mel[:, 0], scale=0.5, shift=0.5)
+        mel01 = (mel[:, 0] + 1) / 2
+        if save_root is not None:
+            os.makedirs(save_root, exist_ok=True)
+            m_, w_ = mel01.cpu().numpy(), None if wave is None else wave[:, 0].cpu().numpy()
+            for i in range(m_.shape[0]):
+                path = os.path.join(save_root, str(i).zfill(6))
+                np.save(path + ".npy", m_[i])
+                if w_ is not None:
+                    write_wav_pcm24(path + ".wav", w_[i], 22050)
+        return mel01, wave, tokens
+
+    @torch.no_grad()
     def inference_generate_sample_with_condition(self, text, truncation_rate, save_root, batch_size, fast=False):
         """The reference's single-caption driver, same signature and behaviour (generate_samples_batch.py:89-123):
         ONE caption `text`, sampled `replicate = 10` times (hard-coded there, :111; `batch_size` is accepted and
