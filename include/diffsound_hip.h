@@ -533,6 +533,21 @@ int ds_mel_to_cl(const float* mel, float* out, int B, int C, int T, int Cpad, fl
 int ds_wave_to_mel(const float* wave, int B, int T, int length, int pad, const float* window, const double* twiddle,
                    const float* mel_basis, const int32_t* krange, int n_mels, int n_fft, int hop, int f0, int n_out,
                    float a, float c, float lo, float hi, float floor, float* out, ds_stream_t stream);
+/* Band-limited rational resampling, one launch for the batch (csrc/resample.hip).  Stands in for `librosa.load(path, sr=22050)`
+ * of the reference's data preparation (Codebook/feature_extraction/extract_mel_spectrogram.py:167) and the 32 kHz resampling
+ * of its captioning metric (Codebook/AudiocaptionLoss/data_handling/audiocaps_dataset.py:246-260).  With g = gcd(src, dst),
+ * L = dst / g, M = src / g, input x[k], k in [0, len_b), zero outside:
+ *   N    = ceil(len_b L / M)                                  valid outputs of row b
+ *   s    = rho min(1, L / M)                                  cutoff relative to the input Nyquist
+ *   h(t) = s sinc(s t) I0(beta sqrt(1 - (s t / Z)^2)) / I0(beta)   for |s t| < Z, else 0       (sinc(u) = sin(pi u) / (pi u))
+ *   y[b][n] = sum_k x[b][k] h(n M / L - k) = sum_{j = -W..W} x[b][i0 + j] taps[p][j + W],   p = (n M) mod L, i0 = (n M) div L
+ *   Z = 32, beta = 14.769656459379492, rho = 0.9475937167399596, W = ceil(Z / s), taps[p][j + W] = h(p / L - j)
+ * taps f32[L][2W+1] is built in float64 on the host and rounded once (audio.resample_taps).  x f32[B][T] (T = row stride);
+ * lengths i32[B] on the device (clamped to 0..T) or NULL (= T); y f32[B][n_out], y[b][n] = 0 for n >= N.  fp32 fma over
+ * j ascending by one thread per output: a clip's result is bit-identical whatever the batch, its position in it, n_out and the
+ * launch.  L / M in lowest terms, both < 2^20; 1024 M / L + 2 W + 2 <= 15360 (M / L up to ~13); n_out == 0 is a no-op. */
+int ds_resample(const float* x, int B, int T, const int32_t* lengths, int L, int M, const float* taps, int W,
+                float* y, int n_out, ds_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -154,6 +154,7 @@ _PROTOS = {
     "ds_mel_to_cl": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f, _f, _vp]),
     "ds_wave_to_mel": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_int, _f, _f, _f, _f, _f, _vp, _vp]),
+    "ds_resample": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp]),
 }
 EXPORTED = tuple(_PROTOS)
 

@@ -1,8 +1,10 @@
 """Host side of the audio front end: the mel filterbank, the FFT tables of `ds_wave_to_mel`, a RIFF reader, and the thin
-launcher of the kernel (csrc/stft_mel.hip) that `modeling.vocoder.Audio2Mel` and `modeling.melspec.WaveToMel` share.
+launcher of the kernel (csrc/stft_mel.hip) that `modeling.vocoder.Audio2Mel` and `modeling.melspec.WaveToMel` share; the
+polyphase table of `ds_resample` (csrc/resample.hip) and its launcher: audio at any integer sample rate in and out.
 
 The reference extracts mels with librosa on the host (Diffsound/vocoder/mel2wav/extract_mel_spectrogram.py:15-38,141-187)
-and reads audio with `librosa.load(path, sr=None)` (:167).  Nothing here needs librosa or soundfile."""
+and reads audio with `librosa.load(path, sr=None)` (:167); its data preparation resamples with `librosa.load(path, sr=22050)`
+(Codebook/feature_extraction/extract_mel_spectrogram.py:167).  Nothing here needs librosa, resampy or soundfile."""
 import math
 import struct
 
@@ -99,6 +101,97 @@ def wave_to_mel(wave, window, mel_basis, krange, *, pad, length=0, f0=0, n_out=N
     _lib.check(_lib.lib().ds_wave_to_mel(_lib.ptr(wave), B, T, int(length), int(pad), _lib.ptr(window),
                                          _lib.ptr(_twiddle(wave.device)), _lib.ptr(mel_basis), _lib.ptr(krange), n_mels,
                                          N_FFT, HOP, int(f0), int(n_out), a, c, lo, hi, floor, _lib.ptr(out), _lib.stream()))
+    return out
+
+
+# the resampling filter: Kaiser-windowed sinc, Z zero crossings a side; beta and rho are the published "kaiser_best" constants
+RESAMPLE_ZEROS = 32
+RESAMPLE_BETA = 14.769656459379492
+RESAMPLE_ROLLOFF = 0.9475937167399596
+
+
+def _rates(src, dst):
+    for r in (src, dst):
+        if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or r < 1:
+            raise ValueError("sample rates must be positive integers, got %r" % (r,))
+    g = math.gcd(int(src), int(dst))
+    return int(dst) // g, int(src) // g
+
+
+def resample_length(n, src, dst):
+    """ceil(n dst / src): the samples `n` input samples give"""
+    L, M = _rates(src, dst)
+    return (int(n) * L + M - 1) // M
+
+
+def resample_half_width(src, dst):
+    """W = ceil(Z / s): input samples on either side of an output's position that the filter reaches"""
+    L, M = _rates(src, dst)
+    return int(math.ceil(RESAMPLE_ZEROS / (RESAMPLE_ROLLOFF * min(1.0, L / M))))
+
+
+def resample_taps(src, dst):
+    """(f32[L, 2W+1], L, M, W): row p holds h(p / L - j), j = -W..W, of
+        h(t) = s sinc(s t) I0(beta sqrt(1 - (s t / Z)^2)) / I0(beta)  for |s t| < Z, else 0,    s = rho min(1, L / M),
+    L / M = dst / src in lowest terms, W = ceil(Z / s) (include/diffsound_hip.h: ds_resample).  Built in float64, rounded
+    once."""
+    L, M = _rates(src, dst)
+    s = RESAMPLE_ROLLOFF * min(1.0, L / M)
+    W = resample_half_width(src, dst)
+    p = np.arange(L, dtype=np.int64)[:, None]
+    j = np.arange(-W, W + 1, dtype=np.int64)[None, :]
+    u = s * ((p - j * L).astype(np.float64) / L)                     # s t, t = p / L - j
+    inside = np.abs(u) < RESAMPLE_ZEROS
+    arg = np.sqrt(np.where(inside, 1.0 - (u / RESAMPLE_ZEROS) ** 2, 0.0))
+    h = np.where(inside, s * np.sinc(u) * np.i0(RESAMPLE_BETA * arg) / np.i0(RESAMPLE_BETA), 0.0)
+    return torch.from_numpy(h.astype(np.float32)), L, M, W
+
+
+_RESAMPLE_TABLES = {}
+
+
+def _resample_table(src, dst, device):
+    L, M = _rates(src, dst)
+    key = (L, M, device.type, device.index)
+    if key not in _RESAMPLE_TABLES:
+        taps, _, _, W = resample_taps(src, dst)
+        _RESAMPLE_TABLES[key] = (taps.to(device), W)
+    return (L, M) + _RESAMPLE_TABLES[key]
+
+
+def resample(wave, src, dst, *, lengths=None, n_out=None):
+    """ds_resample on wave f32[B, T] (device) at `src` Hz -> f32[B, n_out] at `dst` Hz (default n_out = ceil(T dst / src)).
+    lengths: per-row sample counts (i32[B] on the device, or a list): row b is x[b, :len_b], zero outside, and its output
+    past ceil(len_b dst / src) is zero.  src == dst returns the input without a launch (zero-extended or cut if n_out or
+    lengths ask for it).  A host tensor raises (there is no CPU path)."""
+    L, M = _rates(src, dst)
+    if not torch.is_tensor(wave) or wave.dim() != 2:
+        raise ValueError("wave must be a tensor f32[B, T]")
+    if n_out is not None and n_out < 0:
+        raise ValueError("n_out must be >= 0")
+    if L == M and lengths is None and n_out is None:
+        return wave
+    if not wave.is_cuda:
+        raise _lib.DiffsoundHipError("wave is not on a GPU: the HIP path has no CPU fallback")
+    wave = wave.float().contiguous()
+    B, T = wave.shape
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths, dtype=torch.int32).to(wave.device).contiguous()
+        if lengths.shape != (B,):
+            raise ValueError("lengths must hold one count per row")
+    if n_out is None:
+        n_out = (T * L + M - 1) // M
+    if L == M or B == 0 or T == 0 or n_out == 0:          # nothing to filter: the rows as they are, zero-extended or cut
+        out = torch.zeros(B, n_out, device=wave.device, dtype=torch.float32)
+        n = min(T, n_out) if L == M else 0
+        out[:, :n] = wave[:, :n]
+        if lengths is not None and n:
+            out *= (torch.arange(n_out, device=wave.device)[None, :] < lengths[:, None])
+        return out
+    out = torch.empty(B, n_out, device=wave.device, dtype=torch.float32)
+    _, _, taps, W = _resample_table(src, dst, wave.device)
+    _lib.check(_lib.lib().ds_resample(_lib.ptr(wave), B, T, _lib.ptr(lengths), L, M, _lib.ptr(taps), W, _lib.ptr(out),
+                                      int(n_out), _lib.stream()))
     return out
 
 

@@ -44,11 +44,13 @@ class DALLE(nn.Module):
     def content_image(self, batch):
         """batch[content key] on the model's device; a batch without it that carries 'audio' (f32[B, T] on the device, or a
         list of .wav paths / host arrays) gets the mel image from the HIP front end (modeling/melspec.py: the reference's
-        offline extract_mel_spectrogram.py + the dataset's crop and 2 x - 1)."""
+        offline extract_mel_spectrogram.py + the dataset's crop and 2 x - 1).  batch['audio_rate'] (an int, or a list with one
+        rate per clip) states the sample rate; absent = 22 050 Hz for tensors and arrays, the header's rate for paths.  Another
+        rate than 22 050 Hz is resampled on the device first (audio.resample)."""
         key = self.content_info["key"]
         if key not in batch and batch.get("audio") is not None:
             from .melspec import mel_image_from_audio
-            return mel_image_from_audio(batch["audio"], self.device)
+            return mel_image_from_audio(batch["audio"], self.device, rate=batch.get("audio_rate"))
         cont = batch[key]
         return cont.to(self.device) if torch.is_tensor(cont) else cont
 

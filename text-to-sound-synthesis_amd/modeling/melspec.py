@@ -9,6 +9,7 @@ Replaces the reference's offline feature extraction and the dataset's last steps
 The constants below are those settings; the crop and both affine maps are kernel arguments, not extra passes."""
 import os
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -53,23 +54,81 @@ class WaveToMel(nn.Module):
 _FRONT_ENDS = {}
 
 
-def mel_image_from_audio(item, device, crop="center"):
+def _front_end(device):
+    key = (device.type, device.index)
+    if key not in _FRONT_ENDS:
+        _FRONT_ENDS[key] = WaveToMel().to(device)
+    return _FRONT_ENDS[key]
+
+
+def _clip_rates(rate, n):
+    """`rate` (None, one rate, or one per clip) -> a list of n entries (None = not stated)"""
+    if rate is None or isinstance(rate, (int, float, np.number)):
+        if rate is not None and (isinstance(rate, bool) or not isinstance(rate, (int, np.integer)) or rate < 1):
+            raise ValueError("sample rates must be positive integers, got %r" % (rate,))
+        return [rate] * n
+    if torch.is_tensor(rate):
+        rate = rate.tolist()
+    rate = list(rate)
+    if len(rate) != n:
+        raise ValueError("%d sample rates for %d clips" % (len(rate), n))
+    return rate
+
+
+def mel_image_from_audio(item, device, crop="center", rate=None):
     """batch['audio'] -> the content image f32[B, 1, 80, 848] on `device`: the one helper behind every entry point that
     accepts audio (DALLE.prepare_content / sample, modeling.train.training_prologue and so the solvers,
     pipeline.Diffsound.generate_sample_from_audio).  `item`: f32[B, T] (or [T]) already on the device, or a list of
-    `.wav` paths / host arrays / host tensors -- read, zero-extended or cut to 220 500 samples on the host and copied once."""
+    `.wav` paths / host arrays / host tensors -- read, zero-extended or cut to 220 500 samples on the host and copied once.
+    `rate` (batch['audio_rate']): the sample rate of a tensor / of all host arrays, or a list, one per clip; None = 22 050 Hz
+    for tensors and arrays, the header's rate for paths.  Clips at another rate than 22 050 Hz are resampled on the device
+    (audio.resample: one copy and one ds_resample launch per distinct rate, written into the [B, 220 500] buffer)."""
     device = torch.device(device)
     if torch.is_tensor(item) and item.is_cuda:
         wave = item[None] if item.dim() == 1 else item
-    else:
-        clips = [item] if isinstance(item, (str, os.PathLike)) or (torch.is_tensor(item) and item.dim() == 1) else list(item)
+        rates = _clip_rates(rate, wave.shape[0])
+        if any(r not in (None, SAMPLE_RATE) for r in rates):
+            rates = [SAMPLE_RATE if r is None else r for r in rates]
+            if len(set(rates)) == 1:          # one rate for the batch: the launch writes the buffer WaveToMel consumes
+                wave = audio.resample(wave, rates[0], SAMPLE_RATE, n_out=CLIP_SAMPLES)
+            else:
+                buf = torch.empty(wave.shape[0], CLIP_SAMPLES, device=wave.device)
+                for r in sorted(set(rates)):
+                    rows = [i for i, q in enumerate(rates) if q == r]
+                    buf[rows] = audio.resample(wave[rows], r, SAMPLE_RATE, n_out=CLIP_SAMPLES)
+                wave = buf
+        return _front_end(wave.device)(wave, crop=crop)
+    clips = [item] if isinstance(item, (str, os.PathLike)) or (torch.is_tensor(item) and item.dim() == 1) else list(item)
+    rates = _clip_rates(rate, len(clips))
+    waves = []
+    for i, clip in enumerate(clips):
+        if isinstance(clip, (str, os.PathLike)):
+            x, sr = audio.read_wav(clip)
+            if rates[i] is not None and rates[i] != sr:
+                raise ValueError("%s: sample rate %d in the header, %d stated" % (clip, sr, rates[i]))
+            rates[i] = sr
+        else:
+            x = torch.as_tensor(clip).float().reshape(-1)
+            rates[i] = SAMPLE_RATE if rates[i] is None else rates[i]
+        waves.append(x)
+    front = _front_end(device)
+    if all(r == SAMPLE_RATE for r in rates):
         host = torch.zeros(len(clips), CLIP_SAMPLES)
-        for i, clip in enumerate(clips):
-            x = audio.read_wav(clip, rate=SAMPLE_RATE)[0] if isinstance(clip, (str, os.PathLike)) else torch.as_tensor(clip).float().reshape(-1)
+        for i, x in enumerate(waves):
             n = min(x.numel(), CLIP_SAMPLES)
             host[i, :n] = x[:n]
-        wave = host.to(device)
-    key = (wave.device.type, wave.device.index)
-    if key not in _FRONT_ENDS:
-        _FRONT_ENDS[key] = WaveToMel().to(wave.device)
-    return _FRONT_ENDS[key](wave, crop=crop)
+        return front(host.to(device), crop=crop)
+    buf = torch.empty(len(clips), CLIP_SAMPLES, device=device)
+    for r in sorted(set(rates)):
+        rows = [i for i, q in enumerate(rates) if q == r]
+        need = -(-CLIP_SAMPLES * r // SAMPLE_RATE) + audio.resample_half_width(r, SAMPLE_RATE) + 1    # what the last output reaches
+        lens = [min(waves[i].numel(), need) for i in rows]
+        host = torch.zeros(len(rows), max(max(lens), 1))
+        for k, i in enumerate(rows):
+            host[k, :lens[k]] = waves[i][:lens[k]]
+        part = audio.resample(host.to(device), r, SAMPLE_RATE, lengths=lens, n_out=CLIP_SAMPLES)
+        if len(rows) == len(clips):
+            buf = part
+        else:
+            buf[rows] = part
+    return front(buf, crop=crop)

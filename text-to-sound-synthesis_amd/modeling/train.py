@@ -476,7 +476,7 @@ def training_inputs(model, batch, generator=None):
 
     `model` is the DALLE drop-in (`condition_codec` + `transformer.condition_emb` built: config.default_config(with_clip=True)).
     A batch that already carries 'condition_embed_token' / 'condition_token' (DALLE.prepare_condition's other forms) or
-    'content_token' skips the respective stage; one that carries 'audio' (22 050 Hz waveforms) instead of 'image' gets the mel
+    'content_token' skips the respective stage; one that carries 'audio' (waveforms at 22 050 Hz, or at batch['audio_rate']) instead of 'image' gets the mel
     from the HIP front end first (DALLE.content_image -> modeling/melspec.py).  generator: torch.Generator of the model's device for t and the noise.
     Everything is enqueued on the current stream; the only host synchronisation is sample_time's Lt_count test while it
     is still false."""

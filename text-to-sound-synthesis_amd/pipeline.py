@@ -43,6 +43,9 @@ def load_vocoder(ckpt_vocoder, eval_mode=True):
     return {"model": g.eval() if eval_mode else g}
 
 
+VOCODER_RATE = 22050          # the rate the vocoder generates at
+
+
 class Diffsound:
     def __init__(self, config=None, path=None, ckpt_vocoder=None, device="cuda", random_vocoder=False):
         """ckpt_vocoder falsy: `self.vocoder = None` and the drivers write `.npy` only, as the reference does (:53-56).
@@ -73,14 +76,15 @@ class Diffsound:
 
     @torch.no_grad()
     def generate_sample_with_condition(self, cond, truncation_rate=0.85, replicate=1, fast=False, caption_ids=None,
-                                       seed=None):
+                                       seed=None, sample_rate=None):
         """Captions -> (mel01 f32[B,80,848], wave f32[B,1,217088] -- None without a vocoder --, tokens), everything left on the GPU.
         `cond` is a list of caption strings (needs the text stage: tokenizer + CLIP in the config),
         token ids i64[B,77], or caption embeddings f32[B,77,512].  fast=n selects the skip-step sampler with
         skip_step n-1, spelled like the reference's drivers (generate_samples_batch.py:100-103,148-151).
         caption_ids (one global index per caption) switches the sampler to per-caption in-kernel noise: a caption's clip
         then does not depend on the batch it is generated in (DiffusionTransformer.rng_mode); replicate r of caption i
-        draws as caption id ids[i] + r * 2^24."""
+        draws as caption id ids[i] + r * 2^24.  sample_rate: the rate of the returned waveform; another one than 22 050 Hz is the
+        vocoder's output resampled on the device (audio.resample): f32[B,1,ceil(217088 sample_rate / 22050)]."""
         if isinstance(cond, (list, tuple, str)):
             batch = {"text": [cond] if isinstance(cond, str) else list(cond)}
         elif cond.dtype == torch.long:
@@ -96,12 +100,21 @@ class Diffsound:
                                           sample_type="top" + str(truncation_rate) + ("r,fast" + str(fast - 1) if fast else "r"))
         mel = out["content"]                                   # [B,1,80,848] in ~[-1,1]
         wave = None if self.vocoder is None else self.vocoder(mel[:, 0], scale=0.5, shift=0.5)   # spec = (x+1)/2, :182
-        return (mel[:, 0] + 1) / 2, wave, out["content_token"]
+        return (mel[:, 0] + 1) / 2, self._at_rate(wave, sample_rate), out["content_token"]
+
+    @staticmethod
+    def _at_rate(wave, sample_rate):
+        """the vocoder's f32[B,1,T] at 22 050 Hz -> at `sample_rate` (None / 22 050: as it is)"""
+        if wave is None or sample_rate is None or sample_rate == VOCODER_RATE:
+            return wave
+        from . import audio
+        return audio.resample(wave[:, 0], VOCODER_RATE, sample_rate)[:, None]
 
     @torch.no_grad()
-    def generate_sample_from_audio(self, audio, text, filter_ratio=0.5, truncation_rate=0.85, save_root=None):
-        """Re-sample given recordings under new captions: audio (f32[B, T] at 22 050 Hz on the device, or a list of `.wav`
-        paths / host arrays) -> mel (modeling/melspec.py, one HIP launch) -> VQ tokens -> diffused forward to
+    def generate_sample_from_audio(self, audio, text, filter_ratio=0.5, truncation_rate=0.85, save_root=None, audio_rate=None):
+        """Re-sample given recordings under new captions: audio (f32[B, T] on the device, or a list of `.wav` paths / host
+        arrays; audio_rate = their sample rate, one or a list, None = 22 050 Hz / the files' own: another rate is resampled on
+        the device first) -> mel (modeling/melspec.py, one HIP launch) -> VQ tokens -> diffused forward to
         t = int(T * filter_ratio) - 1 and denoised from there under `text` (a list of B captions, token ids or embeddings, as in
         generate_sample_with_condition) -> decode -> vocoder.  Returns (mel01 f32[B,80,848], wave f32[B,1,217088] or None,
         tokens); with save_root also writes `{i:06d}.npy` and, with a vocoder, `{i:06d}.wav` like the other drivers."""
@@ -114,7 +127,7 @@ class Diffsound:
             batch = {"condition_embed_token": text}
         model = self.model
         cond = model.prepare_condition(batch)
-        content = model.prepare_content({"audio": audio})
+        content = model.prepare_content({"audio": audio, "audio_rate": audio_rate})
         tr = model.transformer
         keep = tr.truncation_r, tr.truncation_k
         tr.truncation_r, tr.truncation_k = float(truncation_rate), None
@@ -172,11 +185,12 @@ class Diffsound:
         return caps
 
     @torch.no_grad()
-    def generate_sample(self, val_path, truncation_rate, save_root, fast=False, replicate=2):
+    def generate_sample(self, val_path, truncation_rate, save_root, fast=False, replicate=2, sample_rate=None):
         """The reference's file-writing driver (generate_samples_batch.py:143-187): per audio file, all of
         its captions x `replicate` are sampled in one batch; every sample is written as
         `{base}_mel_sample_{i}.npy` (mel in [0,1], f32[80,848]) and -- if there is a vocoder (:183) --
-        `{base}_mel_sample_{i}.wav` (22 050 Hz, PCM_24).  Unlike the reference the vocoder runs on the whole batch at once."""
+        `{base}_mel_sample_{i}.wav` (22 050 Hz or `sample_rate`, PCM_24).  Unlike the reference the vocoder runs on the whole
+        batch at once."""
         import numpy as np
         os.makedirs(save_root, exist_ok=True)
         written = []
@@ -187,13 +201,13 @@ class Diffsound:
             ids = list(range(n_seen, n_seen + len(captions))) if philox else None
             n_seen += len(captions)
             mel01, wave, _ = self.generate_sample_with_condition(list(captions), truncation_rate, replicate, fast=fast,
-                                                                 caption_ids=ids)
+                                                                 caption_ids=ids, sample_rate=sample_rate)
             mel01, wave = mel01.cpu().numpy(), None if wave is None else wave[:, 0].cpu().numpy()
             for i in range(mel01.shape[0]):
                 path = os.path.join(save_root, base + str(i))
                 np.save(path + ".npy", mel01[i])
                 if wave is not None:
-                    write_wav_pcm24(path + ".wav", wave[i], 22050)
+                    write_wav_pcm24(path + ".wav", wave[i], VOCODER_RATE if sample_rate is None else int(sample_rate))
                 written.append(path)
         return written
 
