@@ -164,15 +164,15 @@ def test_loss_and_gradients_L19_b20_vs_reference(model_init, profile):
             step.calib_log2 = calib
         loss, grads = step.loss_and_grads(x0, cond, t, pt, u)
         check_grads(g, meta, loss, grads, "train L19 B20 %s (operand maxima calibrated to 2^%d, loss scale 2^%d, site exponents %d..%d)"
-                    % (profile, step.calib_log2, step.loss_scale_exp, min(step._site_exp.values()), max(step._site_exp.values())),
+                    % (profile, step.calib_log2, step.loss_scale_exp, min(step.policy._site_exp.values()), max(step.policy._site_exp.values())),
                     floor=floor)
         if calib is None:
             # what ONE scale for the whole backward (rounds 2-5) does to the small gradients, for the record: the same step
             # with the per-site exponents dropped
-            keep = step._site_exp
-            step._site_exp = None
+            keep = step.policy._site_exp
+            step.policy._site_exp = None
             _, g1 = step.loss_and_grads(x0, cond, t, pt, u)
-            step._site_exp = keep
+            step.policy._site_exp = keep
             n1 = {k: float(v.double().norm()) for k, v in g1.items()}
             w1 = max((abs(n1[n] - n64) / n64, n) for n, n64, am in zip(meta["grad_names"], g["grad_norms64"].tolist(), g["grad_amax"].tolist())
                      if am >= 1e-7)
@@ -187,7 +187,7 @@ def test_loss_and_gradients_L19_b20_vs_reference(model_init, profile):
             # carries its own power of two on top of the loss scale (the small ones many bits)
             assert step.check_loss_scale(force=True) is False
             assert step.calib_log2 - 1 <= step.monitor_log[-1] < step.calib_log2 + 3, step.monitor_log
-            ex = step._site_exp
+            ex = step.policy._site_exp
             assert len(ex) == 19 * 9 + 1                            # 7 linears + 2 attention backwards per block, + the logits layer
             print("site exponents: logits %d, block 18 %s, block 0 %s" % (ex["logits"], {k[4:]: v for k, v in ex.items() if k.startswith("b18.")},
                                                                         {k[3:]: v for k, v in ex.items() if k.startswith("b0.")}))

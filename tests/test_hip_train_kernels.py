@@ -795,7 +795,7 @@ def test_graph_solver_resumes_from_its_state_dict():
     a = GraphSolver(TrainStep(dt_a, precision="f16x2"), lr=1e-3, clip_grad_norm=GradClipWindow(0, 5000, 0.5))
     for t, u in batches[:2]:
         a.step(x0, cond, t, pt, u)
-    assert float(a.train_step._amax_live) > 0.0            # the monitor accumulates max |scaled dY| on the device
+    assert float(a.train_step.policy._amax_live) > 0.0            # the monitor accumulates max |scaled dY| on the device
     state = a.state_dict()
     weights = {k: v.detach().clone() for k, v in dt_a.state_dict().items()}
     oa = a.step(x0, cond, batches[2][0], pt, batches[2][1])

@@ -73,7 +73,8 @@ class DALLE(nn.Module):
     @torch.no_grad()
     def forward(self, batch, name="none", **kwargs):
         """batch {'image': mel f32[B,1,80,848], 'text' | 'condition_embed_token': ...} -> the transformer's
-        {'logits', 'loss'} (dalle_spec.py:389-400).  Forward value only (no autograd through the HIP path)."""
+        {'logits', 'loss'} (dalle_spec.py:389-400).  A forward value (no autograd through the HIP path): training enters
+        through `Solver.step(batch)` / `TrainStep` (modeling/solver.py, modeling/train.py), which has its own backward."""
         return self.transformer(self.prepare_input(batch), **kwargs)
 
     def decode_to_img(self, index, zshape, stage="first"):

@@ -296,8 +296,8 @@ class DiffusionTransformer(nn.Module):
 
     @torch.no_grad()
     def forward(self, input, return_loss=False, return_logits=True, return_att_weight=False, is_train=True, **kwargs):
-        """{'logits': exp(log_model_prob), 'loss': scalar} as :539-577.  The loss is a forward value: this package
-        has no backward pass, so it serves evaluation / loss parity, not optimisation."""
+        """{'logits': exp(log_model_prob), 'loss': scalar} as :539-577.  The loss is a forward value for evaluation / loss
+        parity; optimisation enters through `Solver.step(batch)` / `TrainStep` (modeling/train.py: the hand-written backward)."""
         x = input["content_token"]
         cond_emb = self._cond(input.get("condition_token"), input.get("condition_embed_token")).to(x.device)
         out = {}

@@ -9,7 +9,7 @@ contributes three GEMMs (y = x W^T, dX = dY W, dW = dY^T X -- 98 % of the step's
 pieces run on csrc/train.hip, norm.hip and sampler.hip.  The self-attention Q | K | V projections and the
 cross-attention K | V projections are fused into one linear each (one GEMM of N = 3D / 2D instead of three / two).
 
-Two GEMM backends (`TrainStep(precision=...)`), both behind the same step:
+Two GEMM backends (`TrainStep(precision=...)`; modeling/train_gemm.py), both behind the same step:
 
   "fp32"   exact-fp32 MFMA (`ds_gemm`); transposed / padded operands are made by torch.  The reference arithmetic.
   "f16x2"  the fp32-class 3-pass fp16 split GEMM with PACKED split planes on both operands of all three GEMMs (LDS-DMA
@@ -28,7 +28,8 @@ Two GEMM backends (`TrainStep(precision=...)`), both behind the same step:
            logits is multiplied by it, every dX carries it, the dW GEMMs' epilogue and one multiply over the small gradients
            take it out again -- PLUS one power of two per site (every linear's dY, every attention backward's dO; round 6): the
            operand times 2^e is what is split to fp16 and 2^-e goes into the consuming epilogues / stores, exact.  k and the e
-           come from a two-pass calibration (`calibrate`: max |operand| per site, two host syncs).  A split value keeps an
+           come from a two-pass calibration (`calibrate`: max |operand| per site, two host syncs; the policy around them -- where a
+           calibration aims, when it is dropped -- is modeling/loss_scale.py).  A split value keeps an
            absolute precision of 2^-25, so anything above 2^-3 after scaling is fp32-class; the calibration puts every site's
            largest value at 2^6..2^7 under a saturation monitor whose window ends at 2^15.  The step has no host
            synchronisation at all and is captured in a hipGraph (`capture`): one graph launch per iteration instead of ~2000
@@ -47,26 +48,11 @@ import math
 import torch
 
 from .. import _lib
+from .loss_scale import LossScalePolicy
+from .train_gemm import (PACK_GELU2, PACK_GELU2_BWD, PACK_PLAIN, _ceil, _colsum, _Fp32Gemm, _Linear, _Packed, _pack,  # noqa: F401
+                         _pack_parts, _SplitGemm)
 
 L_ = _lib
-
-
-def _ceil(a, b):
-    return (a + b - 1) // b * b
-
-
-def _colsum(x, G=1, R=None, accumulate_into=None):
-    """out[g][c] = sum over the R rows of group g (tall inputs: chunked two-stage sum, ds_colsum_ws)"""
-    M, C_ = x.shape
-    R = M // G if R is None else R
-    out = torch.empty(G, C_, device=x.device) if accumulate_into is None else accumulate_into
-    if R >= 64:
-        work = torch.empty(G * 64 * C_, device=x.device)
-        L_.check(L_.lib().ds_colsum_ws(L_.ptr(x), L_.ptr(out), G, R, C_, C_, R * C_, int(accumulate_into is not None),
-                                       L_.ptr(work), work.numel(), L_.stream()))
-    else:
-        L_.check(L_.lib().ds_colsum(L_.ptr(x), L_.ptr(out), G, R, C_, C_, R * C_, int(accumulate_into is not None), L_.stream()))
-    return out
 
 
 _ROWS_MAX = 32      # rows per launch of ds_rows_outer / ds_rows_times_matrix
@@ -91,264 +77,6 @@ def _rows_outer(a, s):
     return out
 
 
-PACK_PLAIN, PACK_GELU2, PACK_GELU2_BWD = 0, 1, 2
-
-
-class _Linear:
-    """One (possibly fused) nn.Linear of the step: the weights of its parts (each [N_i][K] fp32; query | key | value of a fused
-    projection), bias [N], plus what the GEMM backend derived from them.  `W` (the concatenated fp32 matrix) is only built
-    when somebody asks for it -- the "fp32" backend; the "f16x2" backend packs every part straight into its range of the
-    fused operand (ds_pack_operand's sub-range form)."""
-
-    def __init__(self, key, W, b):
-        self.key = key
-        self.parts = [w.detach() for w in W] if isinstance(W, (list, tuple)) else [W.detach()]
-        self.b = torch.cat([x.detach() for x in b]) if isinstance(b, (list, tuple)) else b.detach()
-        self.N, self.K = sum(w.shape[0] for w in self.parts), self.parts[0].shape[1]
-        self._W = self.parts[0] if len(self.parts) == 1 else None
-        self.extra = {}
-
-    @property
-    def W(self):
-        if self._W is None:
-            self._W = torch.cat(self.parts)
-        return self._W
-
-
-def _gelu2(x, dy=None):
-    out = torch.empty_like(x)
-    L_.check(L_.lib().ds_gelu2(L_.ptr(x), L_.ptr(dy), L_.ptr(out), x.numel(), L_.stream()))
-    return out
-
-
-class _Fp32Gemm:
-    """Backend "fp32": every GEMM on the exact-fp32 MFMA kernel; transposes and zero padding by torch.  An operand handle is
-    the fp32 matrix itself (after the elementwise prologue, if any)."""
-    name = "fp32"
-
-    def prepare(self, lin):
-        pass
-
-    def prep_x(self, lin, x, pro=PACK_PLAIN):
-        return _gelu2(x) if pro == PACK_GELU2 else x
-
-    def prep_dy(self, lin, dy, pro=PACK_PLAIN, aux=None, amax=None, need_row=True, scale=1.0):
-        return _gelu2(aux, dy) if pro == PACK_GELU2_BWD else dy
-
-    def fwd(self, lin, x, R=None):
-        M = x.shape[0]
-        y = torch.empty(M, lin.N, device=x.device)
-        return L_.gemm(x, lin.W, y, M, lin.N, lin.K, bias=lin.b, R=R)
-
-    def dx(self, lin, dy, unscale=1.0):
-        M, N, K = dy.shape[0], lin.N, lin.K
-        Np = _ceil(N, 32)
-        Wt = lin.extra.get("Wt")
-        if Wt is None:                                  # [K][Np]: rows are K-contiguous operands of the GEMM
-            Wt = torch.zeros(K, Np, device=dy.device)
-            Wt[:, :N] = lin.W.t()
-            lin.extra["Wt"] = Wt
-        dyp = dy if Np == N else torch.nn.functional.pad(dy, (0, Np - N))
-        out = torch.empty(M, K, device=dy.device)
-        return L_.gemm(dyp.contiguous(), Wt, out, M, K, Np)
-
-    def dw(self, lin, x, dy, inv_scale):
-        M = x.shape[0]
-        Mp = _ceil(M, 32)
-
-        def pad_t(a):                                   # a [M][C] -> a^T zero-padded to [C][Mp]
-            out = torch.zeros(a.shape[1], Mp, device=a.device)
-            out[:, :M] = a.t()
-            return out
-        dW = torch.empty(lin.N, lin.K, device=x.device)
-        L_.gemm(pad_t(dy), pad_t(x), dW, lin.N, lin.K, Mp)
-        if inv_scale != 1.0:
-            dW.mul_(inv_scale)
-        return dW
-
-    def db(self, lin, dy):
-        return _colsum(dy)[0]
-
-
-class _Packed:
-    """What ds_pack_operand made of one fp32 matrix [rows][cols]: `row` = packed planes of the matrix (int16 [2][plane]),
-    `t` = packed planes of its transpose with the contraction index padded to rows_pad, `part` = per-64-row column sums."""
-    __slots__ = ("rows", "cols", "row", "row_plane", "t", "t_plane", "rows_pad", "part")
-
-
-def _pack(src, rows, cols, *, scale=1.0, pro=PACK_PLAIN, aux=None, want_row=True, rows_pad=0, colsum=False, amax=None, ld=None):
-    """One ds_pack_operand launch (csrc/pack.hip) over src [rows][ld >= cols]."""
-    dev = src.device
-    o = _Packed()
-    o.rows, o.cols, o.rows_pad = rows, cols, rows_pad
-    o.row = o.t = o.part = None
-    o.row_plane = _ceil(rows, 16) * cols
-    o.t_plane = _ceil(cols, 16) * rows_pad
-    if want_row:
-        o.row = torch.empty(2, o.row_plane, dtype=torch.int16, device=dev)
-    if rows_pad:
-        o.t = torch.empty(2, o.t_plane, dtype=torch.int16, device=dev)
-    if colsum:
-        o.part = torch.empty(L_.lib().ds_pack_operand_tile_rows(rows, rows_pad), cols, device=dev)
-    L_.check(L_.lib().ds_pack_operand(L_.ptr(src), rows, cols, cols if ld is None else ld, float(scale), int(pro), L_.ptr(aux),
-                                      cols, L_.ptr(o.row), o.row_plane, L_.ptr(o.t), o.t_plane, rows_pad, 0, 0, L_.ptr(o.part),
-                                      L_.ptr(amax), L_.stream()))
-    return o
-
-
-def _pack_parts(parts, K, scale):
-    """The parts [N_i][K] of a fused weight (N = sum N_i, every N_i % 32 == 0) -> ONE _Packed of the fused matrix [N][K]: part i
-    goes to the row groups [n0 / 16, ..) of the row form and to the k-range [n0, n0 + N_i) of the transposed form [K][N]."""
-    dev = parts[0].device
-    N = sum(w.shape[0] for w in parts)
-    assert all(w.shape[0] % 32 == 0 and w.shape[1] == K and w.is_contiguous() for w in parts)
-    o = _Packed()
-    o.rows, o.cols, o.rows_pad, o.part = N, K, N, None
-    o.row_plane, o.t_plane = N * K, _ceil(K, 16) * N
-    o.row = torch.empty(2, o.row_plane, dtype=torch.int16, device=dev)
-    o.t = torch.empty(2, o.t_plane, dtype=torch.int16, device=dev)
-    n0 = 0
-    for w in parts:
-        Ni = w.shape[0]
-        L_.check(L_.lib().ds_pack_operand(L_.ptr(w), Ni, K, K, float(scale), PACK_PLAIN, None, 0,
-                                          L_.ptr_off(o.row, n0 * K), o.row_plane,       # row group n0 / 16: (n0 / 16) * (K / 32) * 512 halves
-                                          L_.ptr(o.t), o.t_plane, Ni, n0, N, None, None, L_.stream()))
-        n0 += Ni
-    return o
-
-
-class _SplitGemm:
-    """Backend "f16x2": every linear-layer GEMM on the 3-pass fp16 split kernel with packed split planes on both operands
-    (module docstring).  Operand handles are `_Packed` objects."""
-    name = "f16x2"
-
-    def __init__(self):
-        self.wexp = {}              # key -> s: the weight is split as W * 2^s (max |W| 2^s in [2^13, 2^14))
-        self.rows_per_sample = 0    # token rows per sample of the activations (set by the step; 0: unknown)
-
-    @staticmethod
-    def scales_of(lins):
-        """{key: s} with s = 13 - floor(log2 max|W|) for every matrix; one host sync for all of them"""
-        mx = torch.stack([torch.stack([w.abs().max() for w in l.parts]).max() for l in lins]).tolist()
-        return {l.key: 0 if (m == 0.0 or not math.isfinite(m)) else 13 - math.floor(math.log2(m)) for l, m in zip(lins, mx)}
-
-    def refresh_scales(self, lins):
-        self.wexp.update(self.scales_of(lins))
-
-    @staticmethod
-    def split_k(N, K, M=4096):
-        """K-ranges of a dW = dY^T X launch over M rows, from the measured sweep of the packed kernel INCLUDING the fixed-order
-        reduction of the partial results (tools/train_gemm_ab.py -> profiles/r05g_train_gemm_packed_sweep.txt, M = 5300 / 1540):
-        >= 256 tiles of 128 x 128 (fc1 / fc2: half a round of the chip) run unsplit -- the partials' write + re-read costs more
-        than the idle slots (133 vs 148 us); so does 3072 x 1024 since round 6 (256 tiles of 96 x 128, one per CU: 111 us against
-        118 in 4 ranges, profiles/r06x_train_gemm_tile_sweep.txt); smaller products take 4 ranges (1024 x 1024: 48 us against 52
-        at 8, 83 unsplit), 2 when the contraction itself is short (the caption rows: 22 us against 31 at 8)."""
-        tiles = ((N + 127) // 128) * ((K + 127) // 128)
-        if tiles >= 192:
-            return 1
-        return 4 if M >= 4096 else 2
-
-    def rows_pad(self, lin, M):
-        """the padded contraction length of this layer's dW = dY^T X over M rows: a multiple of 32 per K-range"""
-        return _ceil(M, 32 * self.split_k(lin.N, lin.K, M))
-
-    def prepare(self, lin):
-        """W * 2^s -> row form [N][K] (forward) and transposed form [K][ceil32(N)] (dX), one pass"""
-        s = self.wexp[lin.key]
-        lin.extra["osc"] = 2.0 ** (-s)
-        if len(lin.parts) > 1 or lin.N % 32 == 0:
-            lin.extra["Wp"] = _pack_parts(lin.parts, lin.K, 2.0 ** s)
-        else:
-            lin.extra["Wp"] = _pack(lin.W, lin.N, lin.K, scale=2.0 ** s, rows_pad=_ceil(lin.N, 32))
-
-    def prep_x(self, lin, x, pro=PACK_PLAIN):
-        M = x.shape[0]
-        return _pack(x, M, lin.K, pro=pro, rows_pad=self.rows_pad(lin, M))
-
-    def prep_dy(self, lin, dy, pro=PACK_PLAIN, aux=None, amax=None, need_row=True, scale=1.0):
-        """scale: the site's own power of two (TrainStep._site_exp): the planes hold dY * scale, the column sums (bias
-        gradient) are those of dY itself, `amax` takes max |dY * scale|"""
-        M = dy.shape[0]
-        return _pack(dy, M, lin.N, scale=scale, pro=pro, aux=aux, want_row=need_row, rows_pad=self.rows_pad(lin, M), colsum=True,
-                     amax=amax)
-
-    def fwd(self, lin, xp, R=None):
-        M = xp.rows
-        y = torch.empty(M, lin.N, device=xp.row.device)
-        Wp = lin.extra["Wp"]
-        # (rows_per_sample: lets the dispatcher take the sampling loop's per-sample 272 x 256 program where its grid pays --
-        #  the 20 x 12 tiles of the QKV projection, 91 us against 101; same bits, tests/test_hip_widening.py)
-        return L_.gemm(xp.row, Wp.row, y, M, lin.N, lin.K, bias=lin.b, R=R, split2=lin.extra["osc"], a_plane=xp.row_plane,
-                       w_plane=Wp.row_plane, rows_per_sample=self.rows_per_sample if M % max(1, self.rows_per_sample) == 0 else 0)
-
-    def dx(self, lin, dyp, unscale=1.0):
-        """unscale: 2^-e of the site's own scale, folded into the epilogue's output scale (exact: powers of two)"""
-        M = dyp.rows
-        Wp = lin.extra["Wp"]
-        out = torch.empty(M, lin.K, device=dyp.row.device)
-        Np = Wp.rows_pad                                       # contraction length of dX = dY W (N, a multiple of 32 here)
-        assert Np == lin.N, "dX needs N % 32 == 0 (true for every linear of this network)"
-        return L_.gemm(dyp.row, Wp.t, out, M, lin.K, Np, split2=lin.extra["osc"] * unscale, a_plane=dyp.row_plane,
-                       w_plane=Wp.t_plane, rows_per_sample=self.rows_per_sample if M % max(1, self.rows_per_sample) == 0 else 0)
-
-    def dw(self, lin, xp, dyp, inv_scale, out=None):
-        N, K, Mp = lin.N, lin.K, dyp.rows_pad
-        assert xp.rows_pad == Mp and xp.cols == K and dyp.cols == N
-        S = self.split_k(N, K, dyp.rows)
-        dev = dyp.t.device
-        dW = torch.empty(N, K, device=dev) if out is None else out
-        if S == 1:
-            return L_.gemm(dyp.t, xp.t, dW, N, K, Mp, split2=inv_scale, a_plane=dyp.t_plane, w_plane=xp.t_plane)
-        part = torch.empty(S, N * K, device=dev)
-        Kc = Mp // S
-        L_.gemm(dyp.t, xp.t, part, N, K, Kc, lda=Mp, ldw=Mp, ldc=K, groups=S, a_gstride=Kc * 16, w_gstride=Kc * 16,
-                c_gstride=N * K, split2=inv_scale, a_plane=dyp.t_plane, w_plane=xp.t_plane)
-        L_.check(L_.lib().ds_colsum(L_.ptr(part), L_.ptr(dW), 1, S, N * K, N * K, 0, 0, L_.stream()))
-        return dW
-
-    def dw_many(self, items):
-        """items: [(lin, xp, dyp, inv_scale, dW)] -- the weight gradients of several layers whose operands are all packed, into
-        the pre-allocated dW tensors.  Every dW launch is sized to about one workgroup per CU, and a workgroup alone on a CU
-        runs its tile in ~0.6 of the time two co-resident ones take: products of equal tile configuration and K-range count go
-        out as ONE grid (ds_gemm_f16x2_multi, up to four), the same bits as one launch each."""
-        groups = {}
-        for it in items:
-            lin, xp, dyp = it[0], it[1], it[2]
-            S = self.split_k(lin.N, lin.K, dyp.rows)
-            cfg = L_.lib().ds_gemm_f16x2_auto_tile(lin.N, lin.K, S)
-            groups.setdefault((cfg, S), []).append(it)
-        for (cfg, S), its in groups.items():
-            for c0 in range(0, len(its), 4):
-                chunk = its[c0:c0 + 4]
-                if cfg == 2 or len(chunk) == 1:
-                    for lin, xp, dyp, inv_scale, dW in chunk:
-                        self.dw(lin, xp, dyp, inv_scale, out=dW)
-                    continue
-                descs, finish = [], []
-                for lin, xp, dyp, inv_scale, dW in chunk:
-                    N, K, Mp = lin.N, lin.K, dyp.rows_pad
-                    assert xp.rows_pad == Mp and xp.cols == K and dyp.cols == N
-                    if S == 1:
-                        descs.append(L_.gemm(dyp.t, xp.t, dW, N, K, Mp, split2=inv_scale, a_plane=dyp.t_plane, w_plane=xp.t_plane,
-                                             desc_only=True))
-                    else:
-                        part = torch.empty(S, N * K, device=dW.device)
-                        Kc = Mp // S
-                        descs.append(L_.gemm(dyp.t, xp.t, part, N, K, Kc, lda=Mp, ldw=Mp, ldc=K, groups=S, a_gstride=Kc * 16,
-                                             w_gstride=Kc * 16, c_gstride=N * K, split2=inv_scale, a_plane=dyp.t_plane,
-                                             w_plane=xp.t_plane, desc_only=True))
-                        finish.append((part, dW, N * K))
-                L_.gemm_multi(descs, cfg)
-                for part, dW, n in finish:
-                    L_.check(L_.lib().ds_colsum(L_.ptr(part), L_.ptr(dW), 1, S, n, n, 0, 0, L_.stream()))
-
-    def db(self, lin, dyp):
-        out = torch.empty(1, dyp.cols, device=dyp.part.device)
-        R = (dyp.rows + 63) // 64                              # tile rows that hold data (the rest pad the contraction)
-        L_.check(L_.lib().ds_colsum(L_.ptr(dyp.part), L_.ptr(out), 1, R, dyp.cols, dyp.cols, 0, 0, L_.stream()))
-        return out[0]
-
-
 def _norm_fwd(x, mode, L, table=None, t=None, gamma=None, beta=None):
     M, D = x.shape
     y = torch.empty_like(x)
@@ -360,8 +88,8 @@ def _norm_fwd(x, mode, L, table=None, t=None, gamma=None, beta=None):
 
 
 def _norm_bwd(x, dy, mode, L, table=None, t=None, gamma=None, add_to=None):
-    """-> (dx, d scale, d shift): per sample [B][D] (AdaLN, mode 0) or summed [1][D] (LayerNorm, mode 1).  One kernel computes dx
-    and per-chunk column sums of dy * xn and dy (ds_layernorm_bwd_sums), one ds_colsum adds the chunks.
+    """-> (dx, [d scale | d shift]): the sums per sample [B][2D] (AdaLN, mode 0) or over all rows [1][2D] (LayerNorm, mode 1).
+    One kernel computes dx and per-chunk column sums of dy * xn and dy (ds_layernorm_bwd_sums), one ds_colsum adds the chunks.
     add_to: the residual stream's gradient -- the norm-input gradient is ADDED to it in place instead of being returned."""
     M, D = x.shape
     dx = torch.empty_like(x) if add_to is None else add_to
@@ -372,7 +100,7 @@ def _norm_bwd(x, dy, mode, L, table=None, t=None, gamma=None, add_to=None):
                                             L_.ptr(gamma), int(add_to is not None), L_.stream()))
     sums = torch.empty(G, 2 * D, device=x.device)
     L_.check(L_.lib().ds_colsum(L_.ptr(part), L_.ptr(sums), G, chunks, 2 * D, 2 * D, chunks * 2 * D, 0, L_.stream()))
-    return dx, sums[:, :D], sums[:, D:]
+    return dx, sums
 
 
 def _heads(x, B, Lx, H, Lp):
@@ -388,10 +116,20 @@ def _merge_into(out, x4, B, Lx, H):
     return out
 
 
-class _Attn:
-    """softmax(q k^T / 8) v per head (FullAttention / CrossAttention cores, transformer_utils.py:43-58,91-109)"""
+# The two attention classes share one surface: an operand is (tensor, first column, row stride) -- a column range of a fused
+# projection buffer, read or written where it lies -- `out` is the forward's [B*Lq][H*64] result, and
+# backward(dO, dq, dk, dv, amax, do_scale) writes the three gradients into their operands.  `site`: whether the backward splits
+# dO to fp16 under a power of two of its own, i.e. is a site of the loss-scale calibration (TrainStep.calibrate).
 
-    def __init__(self, q, k, v, B, Lq, Lk, H):
+class _Attn:
+    """softmax(q k^T / 8) v per head (FullAttention / CrossAttention cores, transformer_utils.py:43-58,91-109), composed:
+    grouped exact-fp32 GEMMs + row softmax with stored probabilities; torch slices the operands' column ranges and splits /
+    merges the heads.  The first version, kept as a cross-check of the fused kernels."""
+    site = False
+
+    def __init__(self, q, k, v, B, Lq, Lk, H, split=False):
+        """split: ignored (every product is exact fp32 here)"""
+        q, k, v = (x[:, c:c + H * 64] for x, c, _ in (q, k, v))
         self.B, self.Lq, self.Lk, self.H = B, Lq, Lk, H
         self.Lqp, self.Lkp = _ceil(Lq, 32), _ceil(Lk, 32)
         G = B * H
@@ -407,8 +145,9 @@ class _Attn:
                 c_gstride=self.Lqp * 64)
         self.out = _merge_into(torch.empty(B * Lq, H * 64, device=q.device), o4, B, Lq, H)
 
-    def backward(self, dO, dq_out, dk_out, dv_out):
-        """dO [B*Lq, H*64] -> writes dQ / dK / dV into the given [rows, H*64] views (column ranges of a fused gradient)"""
+    def backward(self, dO, dq, dk, dv, amax=None, do_scale=1.0):
+        """dO [B*Lq, H*64] -> dQ / dK / dV into the column ranges dq / dk / dv of the fused gradient buffers.  amax, do_scale:
+        ignored (nothing is split to fp16 here)"""
         B, Lq, Lk, H, Lqp, Lkp = self.B, self.Lq, self.Lk, self.H, self.Lqp, self.Lkp
         G = B * H
         dO4 = _heads(dO, B, Lq, H, Lqp)
@@ -426,15 +165,15 @@ class _Attn:
         dK4 = torch.empty(G, Lkp, 64, device=dev)                                   # dK = dS^T Q
         L_.gemm(dS.transpose(1, 2).contiguous(), self.q4.transpose(1, 2).contiguous(), dK4, Lkp, 64, Lqp, groups=G,
                 a_gstride=Lkp * Lqp, w_gstride=64 * Lqp, c_gstride=Lkp * 64)
-        _merge_into(dq_out, dQ4, B, Lq, H)
-        _merge_into(dk_out, dK4, B, Lk, H)
-        _merge_into(dv_out, dV4, B, Lk, H)
+        for (x, c, _), x4, Lx in ((dq, dQ4, Lq), (dk, dK4, Lk), (dv, dV4, Lk)):
+            _merge_into(x[:, c:c + H * 64], x4, B, Lx, H)
 
 
 class _FusedAttn:
     """The same attention cores on the fused kernels: `ds_attention` forward and `ds_attention_bwd` (tile-wise
     recomputation: the probabilities are never stored), reading Q / K / V and writing dQ / dK / dV IN PLACE in the fused
-    projection buffers -- an operand is (tensor, first column, row stride).  Exact-fp32 MFMA, like the composed version."""
+    projection buffers.  Exact-fp32 MFMA, like the composed version."""
+    site = True
 
     def __init__(self, q, k, v, B, Lq, Lk, H, split=False):
         """split: the forward on the streamed fp16-split attention kernel of the sampling path (ds_attention_f16x2: fp32-class,
@@ -512,10 +251,329 @@ def training_draws(model, x0, cond_emb, generator=None):
     return x0, cond_emb, t.to(dev), pt.to(dev), noise
 
 
+class _BlockActs:
+    """What the forward of one block keeps for its backward: the residual stream at the three norm inputs (x0, x1, x2), the
+    operand handles of the seven linears' inputs (h1: qkv1, o1: proj1, h2: q2, o2: proj2, h3: fc1, g: fc2 -- gelu2(u); the
+    caption handle of kv2 is the pass's), the two attention objects, and fc1's output u."""
+    __slots__ = ("x0", "h1", "att1", "o1", "x1", "h2", "att2", "o2", "x2", "h3", "u", "g")
+
+
+_BLOCK_WEIGHTS = ("mlp.2.weight", "mlp.0.weight", "attn2.proj.weight", "attn2.query.weight", "attn2.key.weight",
+                  "attn2.value.weight", "attn1.proj.weight", "attn1.query.weight", "attn1.key.weight", "attn1.value.weight")
+
+
+class _Pass:
+    """One walk of the network -- forward keeping activations, loss, backward -- for `TrainStep`: the normal step and the two
+    calibration passes are this one code path (`calibrating`, `amax`, `site_amax`).  Every d* of the backward carries the loss
+    scale; `small` collects what one multiply un-scales at the end (the weight gradients lose it in their GEMM's epilogue).
+
+    site_amax: second calibration pass -- a zeroed f32[>= number of sites] whose slot i takes max |operand| of the i-th site
+    (a linear's dY, a fused attention backward's dO) IN THE ORDER THE BACKWARD VISITS THEM; `site_index` receives the keys."""
+
+    def __init__(self, step, x0, cond_emb, t, pt, noise, calibrating, amax=None, on_grads=None, site_amax=None):
+        self.step, self.dt, self.tr, self.gemm, self.policy = step, step.dt, step.tr, step.gemm, step.policy
+        self.x0, self.cond_emb, self.t, self.pt, self.noise = x0, cond_emb, t, pt, noise
+        self.calibrating, self.amax, self.site_amax = calibrating, amax, site_amax
+        self.on_grads = None if calibrating else on_grads
+        self.site_exp = {} if (calibrating or self.policy._site_exp is None) else self.policy._site_exp
+        self.site_index = {}                    # site key -> slot of site_amax, in visiting order
+        self.dev = x0.device
+        self.B, self.Lx = x0.shape
+        self.Lc = cond_emb.shape[1]
+        self.D, self.H, self.K = self.tr.n_embd, self.tr.n_head, self.tr.num_codes
+        self.M = self.B * self.Lx
+        self.T = self.dt.num_timesteps
+        self.loss_scale = 2.0 ** self.policy.loss_scale_exp
+        self.inv = 1.0 / self.loss_scale
+        self.g, self.small = {}, []             # {parameter name: gradient}; the tensors the closing multiply un-scales
+        self.pending_dw, self.pending_names = [], []     # weight-gradient work not launched yet; names not handed over yet
+        self.ada = [None] * (2 * len(self.tr.blocks))    # [d scale | d shift] [B][2D] per AdaLN module, forward order
+
+    # ---- the walk --------------------------------------------------------------------------------------------------------
+    def run(self):
+        step, G_ = self.step, self.gemm
+        G_.rows_per_sample = self.Lx
+        self.blocks, self.lin_logits = step._linears()
+        all_lins = [l for b in self.blocks for l in b.values()] + [self.lin_logits]
+        if step.precision == "f16x2" and (not G_.wexp or (step._steps % step.rescale_interval == 0 and not self.calibrating
+                                                           and not step._capturing)):
+            G_.refresh_scales(all_lins)
+        for l in all_lins:
+            G_.prepare(l)
+        if self.amax is None and step.precision == "f16x2":     # the saturation monitor (LossScalePolicy.check_loss_scale)
+            if self.policy._amax_live is None or self.policy._amax_live.device != self.dev:
+                self.policy._amax_live = torch.zeros(1, device=self.dev)
+            self.amax = self.policy._amax_live
+        x = self.embed()
+        self.adaln_tables()
+        saved = []
+        for li in range(len(self.blocks)):
+            s, x = self.block_fwd(li, x)
+            saved.append(s)
+        lnf = self.tr.to_logits[0]
+        hf = G_.prep_x(self.lin_logits, _norm_fwd(x, 1, self.Lx, gamma=lnf.weight, beta=lnf.bias))
+        logits = G_.fwd(self.lin_logits, hf)                                        # [M, K]
+        loss, dlog = self.loss_and_dlogits(logits)
+        g = self.g
+        dh, g["transformer.to_logits.1.weight"], g["transformer.to_logits.1.bias"] = self.lin_bwd(self.lin_logits, hf, dlog)
+        self.hand_over(["transformer.to_logits.1.weight"])
+        dx, sums = _norm_bwd(x, dh, 1, self.Lx, gamma=lnf.weight)
+        self.norm_gain_grads("transformer.to_logits.0", sums)
+        for li in reversed(range(len(saved))):
+            self.block_bwd(li, saved[li], dx)
+            self.hand_over(["transformer.blocks.%d.%s" % (li, n) for n in _BLOCK_WEIGHTS], now=False)
+        self.hand_over([])                       # the blocks still waiting
+        self.adaln_param_grads_all()
+        # the AdaLN parameter gradients (17 MB per block, 22 % of the gradient bytes) are final here: hand them to the
+        # overlapped reduction before the embedding backward and the closing un-scale instead of leaving them to finish()
+        self.hand_over([pfx + sfx for pfx in self.adaln_prefixes() for sfx in (".linear.weight", ".emb.weight")])
+        self.embed_bwd(dx)
+        if self.inv != 1.0:
+            torch._foreach_mul_(self.small, self.inv)
+        return loss, g
+
+    def embed(self):
+        """q_sample of the clean tokens, then token + position embedding -> x [M][D]; the caption rows' operand handle"""
+        dt, emb = self.dt, self.tr.content_emb
+        self.sched = dt._schedule_table()
+        self.xt = dt.q_sample_tokens(self.x0.contiguous(), self.t, self.noise)
+        pos = emb.position_table()
+        x = torch.empty(self.M, self.D, device=self.dev)
+        L_.check(L_.lib().ds_embed(L_.ptr(self.xt), L_.ptr(emb.emb.weight), L_.ptr(pos), L_.ptr(x), self.M, self.Lx, self.D,
+                                   L_.stream()))
+        cond = self.cond_emb.reshape(-1, self.cond_emb.shape[-1]).float().contiguous()
+        # operand handles (gemm.prep_x): the forward's GEMM input AND the X^T of the same layer's dW, made in one pass; the
+        # caption embedding feeds every block's cross K | V projection (same K, same padded contraction: one handle)
+        self.cond_h = self.gemm.prep_x(self.blocks[0]["kv2"], cond)
+        return x
+
+    def adaln_tables(self):
+        """The 2 n_layer AdaLN modulations  Linear(SiLU(Emb(t_b)))  (transformer_utils.py:145-147) as ONE grouped exact-fp32 GEMM
+        over the batch's OWN timesteps -- B rows per module, as the reference computes them (the sampling loop tabulates all T
+        rows once; here the weights change every iteration and a table of 100 rows was 5x the work: 416 -> 90 us, and as much
+        again in the backward).  The AdaLN kernels index the [B][2D] rows with sample_rows = 0 .. B-1."""
+        B, D = self.B, self.D
+        lns = [ln for blk in self.tr.blocks for ln in (blk.ln1, blk.ln1_1)]
+        self.ada_E = torch.stack([ln.emb.weight.detach() for ln in lns]).index_select(1, self.t)     # [G][B][D] = Emb(t_b)
+        self.ada_W = torch.stack([ln.linear.weight.detach() for ln in lns])                        # [G][2D][D]
+        self.sample_rows = torch.arange(B, device=self.dev)
+        self.tabs = torch.empty(len(lns), B, 2 * D, device=self.dev)
+        L_.gemm(torch.nn.functional.silu(self.ada_E), self.ada_W, self.tabs, B, 2 * D, D, groups=len(lns), a_gstride=B * D,
+                w_gstride=2 * D * D, c_gstride=B * 2 * D)
+        self.tabs += torch.stack([ln.linear.bias.detach() for ln in lns])[:, None, :]
+
+    def adaln_prefixes(self):
+        return ["transformer.blocks.%d.%s" % (li, n) for li in range(len(self.tr.blocks)) for n in ("ln1", "ln1_1")]
+
+    # ---- one block: forward, and its backward right below ----------------------------------------------------------------
+    def block_fwd(self, li, x):
+        """x -> x + proj1(attn1(qkv1(ln1 x))) -> + proj2(attn2(q2(ln1_1 .), kv2(caption))) -> + fc2(gelu2(fc1(ln2 .)))"""
+        G_, blk, ls = self.gemm, self.tr.blocks[li], self.blocks[li]
+        B, Lx, Lc, D, H, rows = self.B, self.Lx, self.Lc, self.D, self.H, self.sample_rows
+        attn, split = self.step.attn_cls, self.step.split_attention
+        s = _BlockActs()
+        s.x0 = x
+        s.h1 = G_.prep_x(ls["qkv1"], _norm_fwd(x, 0, Lx, table=self.tabs[2 * li], t=rows))
+        qkv = G_.fwd(ls["qkv1"], s.h1)                                            # [M][3D]: q | k | v
+        s.att1 = attn((qkv, 0, 3 * D), (qkv, D, 3 * D), (qkv, 2 * D, 3 * D), B, Lx, Lx, H, split=split)
+        s.o1 = G_.prep_x(ls["proj1"], s.att1.out)
+        s.x1 = x = G_.fwd(ls["proj1"], s.o1, R=x)
+        s.h2 = G_.prep_x(ls["q2"], _norm_fwd(x, 0, Lx, table=self.tabs[2 * li + 1], t=rows))
+        q = G_.fwd(ls["q2"], s.h2)
+        kv = G_.fwd(ls["kv2"], self.cond_h)                                       # [B*Lc][2D]: k | v
+        s.att2 = attn((q, 0, D), (kv, 0, 2 * D), (kv, D, 2 * D), B, Lx, Lc, H, split=split)
+        s.o2 = G_.prep_x(ls["proj2"], s.att2.out)
+        s.x2 = x = G_.fwd(ls["proj2"], s.o2, R=x)
+        s.h3 = G_.prep_x(ls["fc1"], _norm_fwd(x, 1, Lx, gamma=blk.ln2.weight, beta=blk.ln2.bias))
+        s.u = G_.fwd(ls["fc1"], s.h3)
+        s.g = G_.prep_x(ls["fc2"], s.u, pro=PACK_GELU2)                           # gelu2(u): the f16x2 backend never stores it in fp32
+        return s, G_.fwd(ls["fc2"], s.g, R=x)
+
+    def block_bwd(self, li, s, dx):
+        """dx: the gradient of the block's output, turned IN PLACE into that of its input (the residual stream's gradient: every
+        branch adds its norm-input gradient to it)"""
+        g, blk, ls = self.g, self.tr.blocks[li], self.blocks[li]
+        B, Lx, Lc, D, M, rows, dev = self.B, self.Lx, self.Lc, self.D, self.M, self.sample_rows, self.dev
+        p = "transformer.blocks.%d." % li
+        # x3 = x2 + fc2(gelu(fc1(ln2(x2))))
+        dgact, g[p + "mlp.2.weight"], g[p + "mlp.2.bias"] = self.lin_bwd(ls["fc2"], s.g, dx)
+        # d fc1-output = dgact * gelu2'(u): the prologue of fc1's gradient pack
+        dh, g[p + "mlp.0.weight"], g[p + "mlp.0.bias"] = self.lin_bwd(ls["fc1"], s.h3, dgact, pro=PACK_GELU2_BWD, aux=s.u)
+        _, sums = _norm_bwd(s.x2, dh, 1, Lx, gamma=blk.ln2.weight, add_to=dx)
+        self.norm_gain_grads(p + "ln2", sums)
+        # x2 = x1 + proj2(attn2(q(ln1_1(x1)), kv(cond)))
+        dao, g[p + "attn2.proj.weight"], g[p + "attn2.proj.bias"] = self.lin_bwd(ls["proj2"], s.o2, dx)
+        dq = torch.empty(M, D, device=dev)
+        dkv = torch.empty(B * Lc, 2 * D, device=dev)
+        slot, dsc = self.att_site("b%d.att2" % li, s.att2)
+        s.att2.backward(dao, (dq, 0, D), (dkv, 0, 2 * D), (dkv, D, 2 * D), amax=slot, do_scale=dsc)
+        dh, g[p + "attn2.query.weight"], g[p + "attn2.query.bias"] = self.lin_bwd(ls["q2"], s.h2, dq)
+        _, dWkv, dbkv = self.lin_bwd(ls["kv2"], self.cond_h, dkv, need_dx=False)
+        g[p + "attn2.key.weight"], g[p + "attn2.value.weight"] = dWkv[:D], dWkv[D:]
+        g[p + "attn2.key.bias"], g[p + "attn2.value.bias"] = dbkv[:D], dbkv[D:]
+        _, self.ada[2 * li + 1] = _norm_bwd(s.x1, dh, 0, Lx, table=self.tabs[2 * li + 1], t=rows, add_to=dx)
+        # x1 = x0 + proj1(attn1(qkv(ln1(x0))))
+        dao, g[p + "attn1.proj.weight"], g[p + "attn1.proj.bias"] = self.lin_bwd(ls["proj1"], s.o1, dx)
+        dqkv = torch.empty(M, 3 * D, device=dev)
+        slot, dsc = self.att_site("b%d.att1" % li, s.att1)
+        s.att1.backward(dao, (dqkv, 0, 3 * D), (dqkv, D, 3 * D), (dqkv, 2 * D, 3 * D), amax=slot, do_scale=dsc)
+        dh, dWqkv, dbqkv = self.lin_bwd(ls["qkv1"], s.h1, dqkv)
+        for j, nm in enumerate(("query", "key", "value")):
+            g[p + "attn1.%s.weight" % nm], g[p + "attn1.%s.bias" % nm] = dWqkv[j * D:(j + 1) * D], dbqkv[j * D:(j + 1) * D]
+        _, self.ada[2 * li] = _norm_bwd(s.x0, dh, 0, Lx, table=self.tabs[2 * li], t=rows, add_to=dx)
+
+    # ---- the pieces of the backward --------------------------------------------------------------------------------------
+    def site_slot(self, key):
+        """where max |operand| of this site goes: its own slot in the second calibration pass, the monitor's scalar otherwise
+        (every gradient that enters a GEMM passes gemm.prep_dy, whose pack folds max |dY 2^e| into it)"""
+        if self.site_amax is None:
+            return self.amax
+        return self.site_amax[self.site_index.setdefault(key, len(self.site_index))]
+
+    def att_site(self, key, att):
+        """(monitor slot, this attention backward's own power of two); the composed attention splits nothing: no site"""
+        if not att.site:
+            return None, 1.0
+        return self.site_slot(key), 1.0 if self.site_amax is not None else 2.0 ** self.site_exp.get(key, 0)
+
+    def lin_bwd(self, lin, xh, dy, need_dx=True, pro=PACK_PLAIN, aux=None):
+        """The three products of one linear layer for its output gradient dy (fp32; with pro = PACK_GELU2_BWD the
+        gradient of the layer's output is dy * gelu2'(aux)).  dy is packed ONCE (gemm.prep_dy: row form, transposed form,
+        bias column sums, max |dY|), then dX, dW and db.  (Rounds 2-4 could put dW / db on a second HIP stream; measured
+        slower in both rounds it was tried -- 15.6 vs 15.9 and 16.2 vs 16.6 it/s, the GEMMs fill the power-capped chip -- and
+        removed in round 5.)"""
+        G_ = self.gemm
+        # the site's own power of two on top of the loss scale (module docstring; 1 while calibrating)
+        e = self.site_exp.get(lin.key, 0)
+        up, down = 2.0 ** e, 2.0 ** -e
+        dyh = G_.prep_dy(lin, dy, pro=pro, aux=aux, amax=self.site_slot(lin.key), need_row=need_dx, scale=up)
+        dxo = G_.dx(lin, dyh, unscale=down) if need_dx else None
+        # dW is off the critical path: a backend that pairs products (pairs_dw) gets them collected, side by side (flush_dw)
+        dW = torch.empty(lin.N, lin.K, device=self.dev)
+        self.pending_dw.append((lin, xh, dyh, self.inv * down, dW))
+        if not G_.pairs_dw:
+            self.flush_dw()
+        db = G_.db(lin, dyh)
+        self.small.append(db)
+        return dxo, dW, db
+
+    def flush_dw(self):
+        if self.pending_dw:
+            self.gemm.dw_many(self.pending_dw)
+            self.pending_dw.clear()
+
+    def hand_over(self, names, now=True):
+        """Give the named gradients, final from here on, to on_grads.  now=False: the names wait until the weight gradients of
+        TWO blocks are collected (their products then pair up: two qkv gradients in one grid, four MLP ones, ...) -- the
+        overlapped reduction gets them one block later.  (A backend that collects nothing never reaches two blocks: the "fp32"
+        backend's block gradients all go out in the call after the block loop.)"""
+        self.pending_names.extend(names)
+        if not now and len(self.pending_dw) < 14:
+            return
+        self.flush_dw()                          # (the gradients handed over must be final)
+        if self.on_grads is not None:
+            self.on_grads({n: self.g[n] for n in self.pending_names}, ())
+        self.pending_names.clear()
+
+    def norm_gain_grads(self, prefix, sums):
+        """LayerNorm's d weight | d bias: the two halves of _norm_bwd's [1][2D] sums (un-scaled at the end)"""
+        dgam, dbet = sums[:, :self.D], sums[:, self.D:]
+        self.g[prefix + ".weight"], self.g[prefix + ".bias"] = dgam[0], dbet[0]
+        self.small += [dgam, dbet]
+
+    def loss_and_dlogits(self, logits):
+        """-> (loss as forward() reports it, d loss / d logits [M][K] times the loss scale); the importance-sampling statistics
+        of sample_time are updated unless calibrating"""
+        dt, x0, xt, t, pt, sched = self.dt, self.x0, self.xt, self.t, self.pt, self.sched
+        B, Lx, K, T, dev = self.B, self.Lx, self.K, self.T, self.dev
+        kl, nll, kl_aux = (torch.empty(B, Lx, device=dev) for _ in range(3))
+        L_.check(L_.lib().ds_loss_tail(L_.ptr(logits), L_.ptr(x0), L_.ptr(xt), L_.ptr(t), L_.ptr(sched), L_.ptr(kl), L_.ptr(nll),
+                                       L_.ptr(kl_aux), None, B, Lx, K, T, L_.stream()))
+        mask_region = (xt == K).float()
+        weight = mask_region * dt.mask_weight[0] + (1.0 - mask_region) * dt.mask_weight[1]
+        is0 = (t == 0).float()
+        kl_loss = is0 * nll.sum(-1) + (1.0 - is0) * (kl * weight).sum(-1)
+        if not self.calibrating:
+            lt2 = kl_loss.pow(2)                     # importance-sampling statistics of sample_time (:452-455)
+            dt.Lt_history.scatter_(dim=0, index=t, src=(0.1 * lt2 + 0.9 * dt.Lt_history.gather(dim=0, index=t)))
+            dt.Lt_count.scatter_add_(dim=0, index=t, src=torch.ones_like(lt2))
+        vb = kl_loss / pt
+        if dt.auxiliary_loss_weight != 0:
+            wa = t.float() / T + 1.0 if dt.adaptive_auxiliary_loss else 1.0
+            vb = vb + wa * dt.auxiliary_loss_weight * (is0 * nll.sum(-1) + (1.0 - is0) * (kl_aux * weight).sum(-1)) / pt
+        norm = 1.0 / (B * Lx)
+        loss = vb.sum() * norm
+        dlog = torch.empty(self.M, K, device=dev)
+        L_.check(L_.lib().ds_loss_tail_bwd(L_.ptr(logits), L_.ptr(x0), L_.ptr(xt), L_.ptr(t), L_.ptr(pt.contiguous()),
+                                           L_.ptr(sched), L_.ptr(dlog), B, Lx, K, T, float(dt.mask_weight[0]),
+                                           float(dt.mask_weight[1]), float(dt.auxiliary_loss_weight),
+                                           int(bool(dt.adaptive_auxiliary_loss)), L_.stream()))
+        dlog.mul_(norm * self.loss_scale)                                                # loss = sum(vb) / (B L); x loss scale
+        return loss, dlog
+
+    def adaln_param_grads_all(self):
+        """d modulation rows [B][2D] -> emb.weight / linear.{weight, bias} through  mod_b = Linear(SiLU(emb[t_b]))  (AdaLayerNorm,
+        transformer_utils.py:134-149) for ALL 2 n_layer AdaLN modules at once: dW = dmod^T silu(e_b) (ds_rows_outer), db = column
+        sums of dmod, de[t_b] += (dmod_b W) silu'(e_b) (ds_rows_times_matrix): two passes over the B samples for all modules
+        instead of two small GEMMs, three transposing copies and a dozen elementwise launches per module (4 ms of an 82 ms
+        iteration in round 4; grouped GEMMs over all T table rows until round 6).  self.ada, ada_E and ada_W are all in forward
+        order: the stacked parameters of the forward are used as they are."""
+        G, B, D, T, dev, g = len(self.ada), self.B, self.D, self.T, self.dev, self.g
+        if G == 0:
+            return
+        dmod = torch.stack(self.ada) * self.inv                                                # [G][B][2D]
+        E = self.ada_E                                                                         # [G][B][D]
+        sg = torch.sigmoid(E)
+        silu_e = (E * sg).contiguous()                                                         # dW[g] = dmod[g]^T silu(e_b[g]):
+        dw = _rows_outer(dmod, silu_e)                                                         # B outer products per module
+        # dmod[g] W[g]: B rows against the row-major weights where they lie (ds_rows_times_matrix: no transposed copy of the
+        # 38 matrices -- 0.38 ms per iteration -- and no tile program that is mostly padding rows)
+        KS = (2 * D) // 256
+        ds_ = torch.empty(G, B, D, device=dev)
+        for b0 in range(0, B, _ROWS_MAX):               # (the kernel takes <= 32 rows; every row's result is its own)
+            nb = min(B - b0, _ROWS_MAX)
+            xb = dmod if nb == B else dmod[:, b0:b0 + nb].contiguous()
+            part = torch.empty(KS, G, nb, D, device=dev)
+            L_.check(L_.lib().ds_rows_times_matrix(L_.ptr(xb), L_.ptr(self.ada_W), L_.ptr(part), G, nb, 2 * D, D, L_.stream()))
+            ob = ds_ if nb == B else torch.empty(G, nb, D, device=dev)
+            L_.check(L_.lib().ds_colsum(L_.ptr(part), L_.ptr(ob), 1, KS, G * nb * D, G * nb * D, 0, 0, L_.stream()))
+            if nb != B:
+                ds_[:, b0:b0 + nb] = ob
+        # de[g][tau] = sum over the b with t_b = tau of ds_[g][b] silu'(e_b): the same sum of outer products with one-hot rows
+        # (samples that share a timestep add up in sample order -- index_add_'s atomics made that order the hardware's)
+        onehot = (self.t[:, None] == torch.arange(T, device=dev)).float().expand(G, B, T).contiguous()   # [G][B][T]
+        de = _rows_outer(onehot, (ds_ * (sg * (1.0 + E * (1.0 - sg)))).contiguous())
+        dbias = dmod.sum(1)                                                                    # [G][2D]
+        for i, pfx in enumerate(self.adaln_prefixes()):
+            g[pfx + ".emb.weight"], g[pfx + ".linear.weight"], g[pfx + ".linear.bias"] = de[i], dw[i], dbias[i]
+
+    def embed_bwd(self, dx):
+        """dx [M][D] -> the token table's gradient (scatter-add over the noised tokens) and the two position tables' (sums of
+        dx over the batch, then over the other spatial axis)"""
+        emb, g, dev = self.tr.content_emb, self.g, self.dev
+        B, Lx, D, M = self.B, self.Lx, self.D, self.M
+        demb = torch.zeros_like(emb.emb.weight)
+        nw = L_.lib().ds_embed_bwd_work_floats(M, D, demb.shape[0])
+        ework = torch.empty(nw, device=dev)
+        L_.check(L_.lib().ds_embed_bwd_ws(L_.ptr(dx), L_.ptr(self.xt), L_.ptr(demb), M, D, demb.shape[0], L_.ptr(ework), nw,
+                                          L_.stream()))
+        g["transformer.content_emb.emb.weight"] = demb
+        dpos = torch.empty(Lx, D, device=dev)
+        L_.check(L_.lib().ds_colsum(L_.ptr(dx), L_.ptr(dpos), Lx, B, D, Lx * D, D, 0, L_.stream()))
+        Hh, Ww = emb.spatial_size
+        dhh = _colsum(dpos.view(Hh, Ww, D).reshape(Hh * Ww, D), Hh)                                     # sum over w
+        g["transformer.content_emb.height_emb.weight"] = dhh
+        dw = torch.empty(Ww, D, device=dev)
+        L_.check(L_.lib().ds_colsum(L_.ptr(dpos), L_.ptr(dw), Ww, Hh, D, Ww * D, D, 0, L_.stream()))   # sum over h
+        g["transformer.content_emb.width_emb.weight"] = dw
+        self.small += [demb, dhh, dw]
+
+
 class TrainStep:
     def __init__(self, diffusion_transformer, precision="fp32", rescale_interval=100, attention="fused"):
         assert precision in ("f16x2", "fp32") and attention in ("fused", "composed")
         self.attention = attention
+        self.attn_cls = _FusedAttn if attention == "fused" else _Attn
         # fused attention FORWARD on the streamed fp16-split kernel of the sampling path (ds_attention_f16x2) in the "f16x2"
         # backend: 122 -> ~35 us per self-attention launch at B = 20; gradient parity unchanged (tests/test_hip_train_kernels.py)
         self.split_attention = precision == "f16x2"
@@ -524,122 +582,42 @@ class TrainStep:
         self.precision = precision
         self.gemm = _SplitGemm() if precision == "f16x2" else _Fp32Gemm()
         self.rescale_interval = rescale_interval
-        self.loss_scale_exp = None if precision == "f16x2" else 0    # k of the loss scale 2^k; None: calibrate first
+        # the loss scale, the per-site exponents and the monitors that guard them (modeling/loss_scale.py); the "fp32" backend
+        # scales nothing: loss_scale_exp is 0 and every check answers False
+        self.policy = LossScalePolicy(enabled=precision == "f16x2")
         self.calibrated_amax = None
         self._steps = 0
         self._capturing = False     # set by GraphedIteration while a hipGraph records the step: no host syncs then
-        self._calib_norm = None     # global gradient norm at calibration time (observe_grad_norm)
-        # Saturation monitor of the split backend (ds_split_hi / _lo SATURATE at 65504 -- no inf / NaN ever shows that a
-        # gradient left the calibrated window): every step folds max |scaled dY| over all GEMM inputs into this device
-        # scalar (ds_amax, the calibration's own probe; captured into the graph like any other launch), and
-        # check_loss_scale() reads it on the host every `monitor_interval` steps -- whether or not clipping is configured.
-        self.monitor_interval = 16
-        # Where a calibration puts the largest value of every fp16-split gradient operand of ITS batch: 2^calib_log2 .. 2x that.
-        # What matters for precision is only that a tensor's largest element is >= 2^0 (a split value keeps 22 bits down to
-        # 2^-3 and 2^-25 absolutely under that: with the maximum at 2^T every element errs by <= 2^-(25+T) of it -- fp32's own
-        # 2^-24 at T = 0), and since round 6 EVERY site has its own power of two (calibrate: `_site_exp`), so the target can sit
-        # low and leave the room above to the batches: rounds 3-5 put ONE global maximum at 2^12, three bits under the window's
-        # upper bound, and the measured batch-to-batch spread of that maximum is three bits (most batches 2^-8.7, every fifth
-        # 2^-5.73 = (1 / pt) / (B L): one position whose d logit is ~1) -- a run re-captured as soon as its first large batch
-        # came by (profiles/r05last_monitor_ab.txt); per site the spread is another 2.5 bits (profiles/r06b_*).  6 leaves nine.
-        self.calib_log2 = 6
-        self.monitor_window = (0, 15)           # log2 bounds of max |scaled operand| outside which the calibration is dropped
-        self.monitor_log = []                   # log2 of the last readings (host floats; tools/bench_train.py prints them)
-        # what a HIGH reading teaches: by how many bits later calibrations aim lower (a calibration looks at ONE batch; the
-        # excursion that tripped the monitor is then put at 2^12).  Forgotten after `cap_decay_readings` quiet readings in a
-        # row, when a reading falls under the window, and when the weights are replaced.
-        self._target_drop = 0
-        self._site_exp = None                   # {linear key: e}: the site's own 2^e on top of the loss scale (calibrate)
-        self._site_order = []
-        self._clean_readings = 0                # consecutive readings under 2^11 while a drop is in force
-        self.cap_decay_readings = 32            # ... after that many (512 iterations) the drop is forgotten
-        self._amax_live = None
-        self._since_check = 0
-        # A calibration has seen ONE batch: the monitor is read after 1, 2, 4, 8 iterations before it settles at every
-        # `monitor_interval`-th -- on trained-like weights a batch 2^11 above the calibration batch came by within the first 16
-        # iterations (profiles/r06k_bench_train_long_runs.txt: reading 2^17.65, i.e. saturated planes until the check)
-        self._next_check = 1
         # weight swaps outside this class (checkpoint / EMA loads: solver._invalidate) must drop the cached pre-scales
         import weakref
         diffusion_transformer.__dict__.setdefault("_scale_clients", []).append(weakref.ref(self))
+
+    # ---- the loss-scale policy's public face (solver.py, train_bench.py and the tests address the step) -------------------
+    loss_scale_exp = property(lambda self: self.policy.loss_scale_exp, lambda self, v: setattr(self.policy, "loss_scale_exp", v))
+    calib_log2 = property(lambda self: self.policy.calib_log2, lambda self, v: setattr(self.policy, "calib_log2", v))
+    monitor_window = property(lambda self: self.policy.monitor_window, lambda self, v: setattr(self.policy, "monitor_window", v))
+    monitor_log = property(lambda self: self.policy.monitor_log)
+    last_trip = property(lambda self: self.policy.last_trip)
+
+    def check_loss_scale(self, force=False):
+        """The saturation monitor's host check (LossScalePolicy.check_loss_scale): True when the next step must re-calibrate"""
+        return self.policy.check_loss_scale(force=force)
+
+    def observe_grad_norm(self, norm):
+        """The gradient-norm guard (LossScalePolicy.observe_grad_norm): True when the next step must re-calibrate"""
+        return self.policy.observe_grad_norm(norm)
 
     def reset_scales(self, weights_replaced=True):
         """Forget the per-matrix weight pre-scales 2^s and the loss scale: the next step re-derives both (one calibration
         backward).  Called after the weights were replaced behind this object's back (solver._invalidate) -- then what the
         saturation monitor had learnt about the OLD weights' gradients (`_target_drop`) goes too -- and, with
         weights_replaced=False, by a re-capture of the same run (the bound is exactly what that re-calibration needs)."""
-        if weights_replaced:
-            self._target_drop, self._clean_readings = 0, 0
-        if hasattr(self.gemm, "wexp"):
-            self.gemm.wexp.clear()
+        self.policy.reset(weights_replaced)
         if self.precision == "f16x2":
-            self.loss_scale_exp = None
-            self._site_exp = None
-        self._calib_norm = None
-        if self._amax_live is not None:
-            self._amax_live.zero_()
+            self.gemm.wexp.clear()
         # a captured iteration (GraphedIteration) has the OLD pre-scales and loss scale baked into its graph: it must be
         # re-captured BEFORE its next replay (swapped-in weights a few times larger would saturate the fp16 planes silently)
         self._scales_epoch = getattr(self, "_scales_epoch", 0) + 1
-
-    def check_loss_scale(self, force=False):
-        """Host side of the saturation monitor: every `monitor_interval` calls (after 1, 2, 4, 8 calls right behind a
-        calibration; or when forced) read max |scaled operand| over all sites since the last check (one sync) and drop the
-        calibration when it has left `monitor_window` = [2^0, 2^15) -- fp16 saturates at 2^16, and a site whose largest element
-        is under 2^0 no longer has fp32-class planes.  Returns True when the next step must re-calibrate (a captured iteration
-        must then be re-captured)."""
-        if self.precision != "f16x2" or self._amax_live is None:
-            return False
-        self._since_check += 1
-        if not force and self._since_check < min(self._next_check, self.monitor_interval):
-            return False
-        self._since_check = 0
-        self._next_check = min(self.monitor_interval, 2 * self._next_check)
-        m = float(self._amax_live.item())
-        self._amax_live.zero_()
-        self.monitor_log = self.monitor_log[-63:] + [round(math.log2(m), 2) if m > 0.0 and math.isfinite(m) else m]
-        if m == 0.0:
-            # ds_amax never lets a NaN win and skips non-positive values, so 0 means EITHER genuinely zero gradients (nothing
-            # was scaled: no reason to re-calibrate / re-capture) OR an all-NaN scaled dY (a diverged loss).  The loss of the
-            # same step tells them apart at this very host sync.
-            last = getattr(self, "_last_loss", None)
-            if last is not None and not math.isfinite(float(last)):
-                # a diverged run: no loss scale repairs it, and answering True here would re-calibrate (and re-capture a graphed
-                # iteration) at every monitor interval for the rest of the run
-                raise FloatingPointError("training diverged: the loss is %r (every scaled gradient is NaN)" % float(last))
-            return False
-        lo, hi = self.monitor_window
-        if math.isfinite(m) and 2.0 ** lo <= m < 2.0 ** hi:
-            # inside the window.  What one excursion taught must not hold the target down for ever: once the readings have
-            # stayed under 2^11 for `cap_decay_readings` checks in a row it is forgotten (the scales themselves are left
-            # alone -- the next re-calibration, whenever something asks for one, aims at the full target again)
-            if self._target_drop:
-                self._clean_readings = self._clean_readings + 1 if m < 2.0 ** 11 else 0
-                if self._clean_readings >= self.cap_decay_readings:
-                    self._target_drop, self._clean_readings = 0, 0
-            return False
-        if math.isfinite(m) and m >= 2.0 ** hi:
-            # put THIS excursion at 2^12 from now on: aim that many bits lower (never under 2^1)
-            self._target_drop = min(self.calib_log2 - 1, self._target_drop + math.floor(math.log2(m)) - 12)
-            self._clean_readings = 0
-            self.last_trip = "monitor high: max |scaled operand| = 2^%.2f" % math.log2(m)
-        elif math.isfinite(m):
-            self._target_drop = 0                                              # gradients have shrunk: aim at the full target again
-            self.last_trip = "monitor low: max |scaled operand| = 2^%.2f" % math.log2(m)
-        else:
-            self.last_trip = "monitor: max |scaled operand| = %r" % m
-        self.loss_scale_exp, self._calib_norm = None, None
-        return True
-
-    def _target(self):
-        """log2 of where calibrations put a site's largest operand value right now (calib_log2 minus what excursions taught)"""
-        return max(1, self.calib_log2 - self._target_drop)
-
-    def _exp_from_amax(self, m):
-        """exponent k that puts a largest value m at 2^target .. 2^(target + 1)"""
-        if m == 0.0 or not math.isfinite(m):
-            return 0
-        return self._target() - math.floor(math.log2(m))
 
     @torch.no_grad()
     def prescales_drifted(self):
@@ -655,22 +633,6 @@ class TrainStep:
         blocks, lin_logits = self._linears()
         new = self.gemm.scales_of([l for b in blocks for l in b.values()] + [lin_logits])
         return any(k not in old or s < old[k] or s > old[k] + 2 for k, s in new.items())
-
-    def observe_grad_norm(self, norm):
-        """Second guard of the calibrated scales ("f16x2" backend, eager solver): the calibration leaves 2^9 of headroom below
-        fp16's range and 2^6 above the point where the largest element of an operand would fall under 2^0.  Gradients grow and
-        shrink together, so the global gradient norm the solver computes anyway is a monitor too: once it has moved by more
-        than 32x up or 64x down from its value at calibration time, the next step re-calibrates (returns True then).  Call
-        it with a HOST float (the solvers do, next to float(loss))."""
-        if self.precision != "f16x2" or not math.isfinite(norm) or norm <= 0.0:
-            return False
-        if self._calib_norm is None:
-            self._calib_norm = norm
-            return False
-        if norm > 32.0 * self._calib_norm or norm < self._calib_norm / 64.0:
-            self.loss_scale_exp, self._calib_norm = None, None
-            return True
-        return False
 
     # ---- the step's linears ------------------------------------------------------------------------------------------
     def _linears(self):
@@ -705,7 +667,7 @@ class TrainStep:
         the streams that wrote them.  The hook of the overlapped data-parallel reduction (shard.GradientReducer.ready)."""
         if self.loss_scale_exp is None:
             self.calibrate(x0, cond_emb, t, pt, noise)
-        return self._run(x0, cond_emb, t, pt, noise, calibrating=False, on_grads=on_grads)
+        return self._run(x0, cond_emb, t, pt, noise, on_grads=on_grads)
 
     @torch.no_grad()
     def calibrate(self, x0, cond_emb, t, pt, noise):
@@ -714,13 +676,12 @@ class TrainStep:
         importance-sampling statistics (Lt_history / Lt_count) are not touched."""
         if self.precision != "f16x2":
             return 0
-        self.loss_scale_exp, self._site_exp = 0, None
-        self._next_check, self._since_check = 1, 0
+        pol, batch = self.policy, (x0, cond_emb, t, pt, noise)
+        pol.begin_calibration()
         amax = torch.zeros(1, device=x0.device)
-        self._run(x0, cond_emb, t, pt, noise, calibrating=True, amax=amax)
+        _Pass(self, *batch, calibrating=True, amax=amax).run()
         m = float(amax.item())
         self.calibrated_amax = m
-        k0 = self._exp_from_amax(m)
         # Second pass, under that provisional scale (unscaled, the deep sites' operands flush to 0): the largest value of EVERY
         # operand the backward splits to fp16 under the loss scale -- max |dY| per linear (its dY feeds the dX and dW GEMMs)
         # and max |dO| over the attention backwards -- in one more host sync.  One scale for the whole backward leaves the small gradients
@@ -731,295 +692,22 @@ class TrainStep:
         # harm, whatever it is): a linear's dY 2^e is what is split (ds_pack_operand `scale`) and 2^-e goes into its dX / dW
         # epilogues; an attention backward's dO 2^e is what its kernels split and their stores take 2^-e out again (they
         # normalise their in-register dS by themselves) -- all exact.
-        self.loss_scale_exp = k0
+        pol.loss_scale_exp = pol._exp_from_amax(m)
         n_sites = 9 * len(self.tr.blocks) + 1                                # 7 linears + 2 attentions per block, + the logits layer
         sites = torch.zeros(n_sites, device=x0.device)                       # in the order the backward visits them
-        self._run(x0, cond_emb, t, pt, noise, calibrating=True, amax=torch.zeros(1, device=x0.device), site_amax=sites)
+        second = _Pass(self, *batch, calibrating=True, amax=torch.zeros(1, device=x0.device), site_amax=sites)
+        second.run()
         per_site = sites.tolist()
-        assert len(self._site_order) == n_sites or self.attention != "fused", (len(self._site_order), n_sites)
-        self._site_exp = {k: (0 if (v == 0.0 or not math.isfinite(v)) else
-                              max(-40, min(40, self._target() - math.floor(math.log2(v)))))
-                          for k, v in zip(self._site_order, per_site)}
-        return self.loss_scale_exp
+        assert len(second.site_index) == n_sites or self.attention != "fused", (len(second.site_index), n_sites)
+        pol._site_exp = pol.site_exponents(list(second.site_index), per_site)
+        return pol.loss_scale_exp
 
-    def _run(self, x0, cond_emb, t, pt, noise, calibrating, amax=None, on_grads=None, site_amax=None):
-        """site_amax: second calibration pass -- a zeroed f32[>= number of linears] whose slot i takes max |dY| of the i-th
-        linear's output gradient IN THE ORDER THE BACKWARD VISITS THEM (self._site_order receives the keys)"""
-        dt, tr, G_ = self.dt, self.tr, self.gemm
-        site_exp = {} if (calibrating or self._site_exp is None) else self._site_exp
-        site_index = {}
-        dev = x0.device
-        B, Lx = x0.shape
-        D, H, K = tr.n_embd, tr.n_head, tr.num_codes
-        M = B * Lx
-        T = dt.num_timesteps
-        G_.rows_per_sample = Lx
-        blocks, lin_logits = self._linears()
-        all_lins = [l for b in blocks for l in b.values()] + [lin_logits]
-        if self.precision == "f16x2" and (not G_.wexp or (self._steps % self.rescale_interval == 0 and not calibrating
-                                                           and not self._capturing)):
-            G_.refresh_scales(all_lins)
-        for l in all_lins:
-            G_.prepare(l)
-        scale = 2.0 ** self.loss_scale_exp
-        inv = 1.0 / scale
-        fused = self.attention == "fused"
-
-        if amax is None and self.precision == "f16x2":  # the saturation monitor (check_loss_scale)
-            if self._amax_live is None or self._amax_live.device != dev:
-                self._amax_live = torch.zeros(1, device=dev)
-            amax = self._amax_live
-
-        # (every gradient that enters a GEMM passes G_.prep_dy, whose pack folds max |dY 2^e| into `amax`: calibration / monitor)
-        def att_site(key):      # (monitor slot, this attention backward's own power of two)
-            if site_amax is not None:
-                return site_amax[site_index.setdefault(key, len(site_index))], 1.0
-            return amax, 2.0 ** site_exp.get(key, 0)
-
-        sched = dt._schedule_table()
-        xt = dt.q_sample_tokens(x0.contiguous(), t, noise)
-        emb = tr.content_emb
-        pos = emb.position_table()
-        x = torch.empty(M, D, device=dev)
-        L_.check(L_.lib().ds_embed(L_.ptr(xt), L_.ptr(emb.emb.weight), L_.ptr(pos), L_.ptr(x), M, Lx, D, L_.stream()))
-        cond = cond_emb.reshape(-1, cond_emb.shape[-1]).float().contiguous()
-        Lc = cond_emb.shape[1]
-        # operand handles (G_.prep_x): the forward's GEMM input AND the X^T of the same layer's dW, made in one pass; the
-        # caption embedding feeds every block's cross K | V projection (same K, same padded contraction: one handle)
-        cond_h = G_.prep_x(blocks[0]["kv2"], cond)
-        # the 2 n_layer AdaLN modulations  Linear(SiLU(Emb(t_b)))  (transformer_utils.py:145-147) as ONE grouped exact-fp32 GEMM over
-        # the batch's OWN timesteps -- B rows per module, as the reference computes them (the sampling loop tabulates all T rows
-        # once; here the weights change every iteration and a table of 100 rows was 5x the work: 416 -> 90 us, and as much again
-        # in the backward).  The AdaLN kernels index the [B][2D] rows with sample_rows = 0 .. B-1.
-        lns = [ln for blk in tr.blocks for ln in (blk.ln1, blk.ln1_1)]
-        ada_E = torch.stack([ln.emb.weight.detach() for ln in lns]).index_select(1, t)   # [G][B][D] = Emb(t_b)
-        ada_W = torch.stack([ln.linear.weight.detach() for ln in lns])                 # [G][2D][D]
-        sample_rows = torch.arange(B, device=dev)
-        tabs = torch.empty(len(lns), B, 2 * D, device=dev)
-        L_.gemm(torch.nn.functional.silu(ada_E), ada_W, tabs, B, 2 * D, D, groups=len(lns), a_gstride=B * D,
-                w_gstride=2 * D * D, c_gstride=B * 2 * D)
-        tabs += torch.stack([ln.linear.bias.detach() for ln in lns])[:, None, :]
-        saved = []
-        for li, (blk, ls) in enumerate(zip(tr.blocks, blocks)):
-            s = {"x0": x}
-            s["tab1"] = tabs[2 * li]
-            s["h1"] = h = G_.prep_x(ls["qkv1"], _norm_fwd(x, 0, Lx, table=s["tab1"], t=sample_rows))
-            qkv = G_.fwd(ls["qkv1"], h)                                             # [M][3D]: q | k | v
-            if fused:
-                s["att1"] = _FusedAttn((qkv, 0, 3 * D), (qkv, D, 3 * D), (qkv, 2 * D, 3 * D), B, Lx, Lx, H, split=self.split_attention)
-            else:
-                s["att1"] = _Attn(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B, Lx, Lx, H)
-            s["o1"] = G_.prep_x(ls["proj1"], s["att1"].out)
-            x = G_.fwd(ls["proj1"], s["o1"], R=x)
-            s["x1"] = x
-            s["tab2"] = tabs[2 * li + 1]
-            s["h2"] = h = G_.prep_x(ls["q2"], _norm_fwd(x, 0, Lx, table=s["tab2"], t=sample_rows))
-            q = G_.fwd(ls["q2"], h)
-            kv = G_.fwd(ls["kv2"], cond_h)                                          # [B*Lc][2D]: k | v
-            if fused:
-                s["att2"] = _FusedAttn((q, 0, D), (kv, 0, 2 * D), (kv, D, 2 * D), B, Lx, Lc, H, split=self.split_attention)
-            else:
-                s["att2"] = _Attn(q, kv[:, :D], kv[:, D:], B, Lx, Lc, H)
-            s["o2"] = G_.prep_x(ls["proj2"], s["att2"].out)
-            x = G_.fwd(ls["proj2"], s["o2"], R=x)
-            s["x2"] = x
-            s["h3"] = h = G_.prep_x(ls["fc1"], _norm_fwd(x, 1, Lx, gamma=blk.ln2.weight, beta=blk.ln2.bias))
-            u = G_.fwd(ls["fc1"], h)
-            s["u"] = u
-            s["g"] = G_.prep_x(ls["fc2"], u, pro=PACK_GELU2)                        # gelu2(u): the f16x2 backend never stores it in fp32
-            x = G_.fwd(ls["fc2"], s["g"], R=x)
-            saved.append(s)
-        xf = x
-        lnf = tr.to_logits[0]
-        hf = G_.prep_x(lin_logits, _norm_fwd(xf, 1, Lx, gamma=lnf.weight, beta=lnf.bias))
-        logits = G_.fwd(lin_logits, hf)                                             # [M, K]
-        # ---- loss (forward value) and d loss / d logits
-        kl, nll, kl_aux = (torch.empty(B, Lx, device=dev) for _ in range(3))
-        L_.check(L_.lib().ds_loss_tail(L_.ptr(logits), L_.ptr(x0), L_.ptr(xt), L_.ptr(t), L_.ptr(sched), L_.ptr(kl), L_.ptr(nll),
-                                       L_.ptr(kl_aux), None, B, Lx, K, T, L_.stream()))
-        mask_region = (xt == K).float()
-        weight = mask_region * dt.mask_weight[0] + (1.0 - mask_region) * dt.mask_weight[1]
-        is0 = (t == 0).float()
-        kl_loss = is0 * nll.sum(-1) + (1.0 - is0) * (kl * weight).sum(-1)
-        if not calibrating:
-            lt2 = kl_loss.pow(2)                     # importance-sampling statistics of sample_time (:452-455)
-            dt.Lt_history.scatter_(dim=0, index=t, src=(0.1 * lt2 + 0.9 * dt.Lt_history.gather(dim=0, index=t)))
-            dt.Lt_count.scatter_add_(dim=0, index=t, src=torch.ones_like(lt2))
-        vb = kl_loss / pt
-        if dt.auxiliary_loss_weight != 0:
-            wa = t.float() / T + 1.0 if dt.adaptive_auxiliary_loss else 1.0
-            vb = vb + wa * dt.auxiliary_loss_weight * (is0 * nll.sum(-1) + (1.0 - is0) * (kl_aux * weight).sum(-1)) / pt
-        norm = 1.0 / (B * Lx)
-        loss = vb.sum() * norm
-        dlog = torch.empty(M, K, device=dev)
-        L_.check(L_.lib().ds_loss_tail_bwd(L_.ptr(logits), L_.ptr(x0), L_.ptr(xt), L_.ptr(t), L_.ptr(pt.contiguous()),
-                                           L_.ptr(sched), L_.ptr(dlog), B, Lx, K, T, float(dt.mask_weight[0]),
-                                           float(dt.mask_weight[1]), float(dt.auxiliary_loss_weight),
-                                           int(bool(dt.adaptive_auxiliary_loss)), L_.stream()))
-        dlog.mul_(norm * scale)                                                      # loss = sum(vb) / (B L); x loss scale
-        # ---- backward (every d* below carries the loss scale; `small` collects what one multiply un-scales at the end)
-        g, small = {}, []
-
-        def lin_bwd(lin, xh, dy, need_dx=True, pro=PACK_PLAIN, aux=None):
-            """The three products of one linear layer for its output gradient dy (fp32; with pro = PACK_GELU2_BWD the
-            gradient of the layer's output is dy * gelu2'(aux)).  dy is packed ONCE (G_.prep_dy: row form, transposed form,
-            bias column sums, max |dY|), then dX, dW and db.  (Rounds 2-4 could put dW / db on a second HIP stream; measured
-            slower in both rounds it was tried -- 15.6 vs 15.9 and 16.2 vs 16.6 it/s, the GEMMs fill the power-capped chip -- and
-            removed in round 5.)"""
-            # the site's own power of two on top of the loss scale (module docstring; 1 while calibrating)
-            e = site_exp.get(lin.key, 0)
-            up, down = 2.0 ** e, 2.0 ** -e
-            site_slot = amax if site_amax is None else site_amax[site_index.setdefault(lin.key, len(site_index))]
-            dyh = G_.prep_dy(lin, dy, pro=pro, aux=aux, amax=site_slot, need_row=need_dx, scale=up)
-            dxo = G_.dx(lin, dyh, unscale=down) if need_dx else None
-            if hasattr(G_, "dw_many"):           # off the critical path: collected, launched side by side (flush_dw)
-                dW = torch.empty(lin.N, lin.K, device=dev)
-                pending_dw.append((lin, xh, dyh, inv * down, dW))
-            else:
-                dW = G_.dw(lin, xh, dyh, inv * down)
-            db = G_.db(lin, dyh)
-            small.append(db)
-            return dxo, dW, db
-
-        pending_dw, pending_names = [], []
-
-        def flush_dw():
-            if pending_dw:
-                G_.dw_many(pending_dw)
-                pending_dw.clear()
-
-        def hand_over(names, now=True):
-            """now=False: the names wait until the weight gradients of TWO blocks are collected (their products then pair up:
-            two qkv gradients in one grid, four MLP ones, ...) -- the overlapped reduction gets them one block later"""
-            pending_names.extend(names)
-            if not now and len(pending_dw) < 14:
-                return
-            flush_dw()                           # (the gradients handed over must be final)
-            if on_grads is not None and not calibrating:
-                on_grads({n: g[n] for n in pending_names}, ())
-            pending_names.clear()
-
-        dh, g["transformer.to_logits.1.weight"], g["transformer.to_logits.1.bias"] = lin_bwd(lin_logits, hf, dlog)
-        hand_over(["transformer.to_logits.1.weight"])
-        dx, dgam, dbet = _norm_bwd(xf, dh, 1, Lx, gamma=lnf.weight)
-        g["transformer.to_logits.0.weight"], g["transformer.to_logits.0.bias"] = dgam[0], dbet[0]
-        small += [dgam, dbet]
-
-        ada = []                    # (AdaLayerNorm module, d scale [B][D], d shift [B][D], parameter prefix): batched below
-
-        def adaln_param_grads(ln, d_scale, d_shift, pfx):
-            # (d_scale / d_shift are the two column halves of _norm_bwd's [B][2D] sums: ._base is [d scale | d shift] itself)
-            both = d_scale._base if d_scale._base is not None and d_scale._base is d_shift._base else torch.cat((d_scale, d_shift), dim=1)
-            ada.append((ln, both, None, pfx))
-
-        def adaln_param_grads_all():
-            """d modulation rows [B][2D] -> emb.weight / linear.{weight, bias} through  mod_b = Linear(SiLU(emb[t_b]))  (AdaLayerNorm,
-            transformer_utils.py:134-149) for ALL 2 n_layer AdaLN modules at once: dW = dmod^T silu(e_b) (ds_rows_outer), db = column
-            sums of dmod, de[t_b] += (dmod_b W) silu'(e_b) (ds_rows_times_matrix): two passes over the B samples for all modules
-            instead of two small GEMMs, three transposing copies and a dozen elementwise launches per module (4 ms of an 82 ms
-            iteration in round 4; grouped GEMMs over all T table rows until round 6)."""
-            G = len(ada)
-            if G == 0:
-                return
-            ada.sort(key=lambda a: lns.index(a[0]))             # forward order (the backward visited the blocks last first):
-            order = [lns.index(ln) for ln, _, _, _ in ada]      # the stacked parameters of the forward are used as they are
-            dmod = torch.stack([both for _, both, _, _ in ada]) * inv                               # [G][B][2D]
-            E = ada_E if order == list(range(len(lns))) else torch.stack([ada_E[i] for i in order])   # [G][B][D]
-            sg = torch.sigmoid(E)
-            silu_e = (E * sg).contiguous()                                                         # dW[g] = dmod[g]^T silu(e_b[g]):
-            dw = _rows_outer(dmod, silu_e)                                                         # B outer products per module
-            # dmod[g] W[g]: B rows against the row-major weights where they lie (ds_rows_times_matrix: no transposed copy of the
-            # 38 matrices -- 0.38 ms per iteration -- and no tile program that is mostly padding rows); ada_W is in forward order
-            Wg = ada_W if order == list(range(len(lns))) else torch.stack([ada_W[i] for i in order])
-            KS = (2 * D) // 256
-            ds_ = torch.empty(G, B, D, device=dev)
-            for b0 in range(0, B, _ROWS_MAX):               # (the kernel takes <= 32 rows; every row's result is its own)
-                nb = min(B - b0, _ROWS_MAX)
-                xb = dmod if nb == B else dmod[:, b0:b0 + nb].contiguous()
-                part = torch.empty(KS, G, nb, D, device=dev)
-                L_.check(L_.lib().ds_rows_times_matrix(L_.ptr(xb), L_.ptr(Wg), L_.ptr(part), G, nb, 2 * D, D, L_.stream()))
-                ob = ds_ if nb == B else torch.empty(G, nb, D, device=dev)
-                L_.check(L_.lib().ds_colsum(L_.ptr(part), L_.ptr(ob), 1, KS, G * nb * D, G * nb * D, 0, 0, L_.stream()))
-                if nb != B:
-                    ds_[:, b0:b0 + nb] = ob
-            # de[g][tau] = sum over the b with t_b = tau of ds_[g][b] silu'(e_b): the same sum of outer products with one-hot rows
-            # (samples that share a timestep add up in sample order -- index_add_'s atomics made that order the hardware's)
-            onehot = (t[:, None] == torch.arange(T, device=dev)).float().expand(G, B, T).contiguous()   # [G][B][T]
-            de = _rows_outer(onehot, (ds_ * (sg * (1.0 + E * (1.0 - sg)))).contiguous())
-            dbias = dmod.sum(1)                                                                    # [G][2D]
-            for i, (_, _, _, pfx) in enumerate(ada):
-                g[pfx + ".emb.weight"], g[pfx + ".linear.weight"], g[pfx + ".linear.bias"] = de[i], dw[i], dbias[i]
-
-        for li in reversed(range(len(saved))):
-            s, blk, ls = saved[li], tr.blocks[li], blocks[li]
-            p = "transformer.blocks.%d." % li
-            # x3 = x2 + fc2(gelu(fc1(ln2(x2))))
-            dgact, g[p + "mlp.2.weight"], g[p + "mlp.2.bias"] = lin_bwd(ls["fc2"], s["g"], dx)
-            # d fc1-output = dgact * gelu2'(u): the prologue of fc1's gradient pack
-            dh, g[p + "mlp.0.weight"], g[p + "mlp.0.bias"] = lin_bwd(ls["fc1"], s["h3"], dgact, pro=PACK_GELU2_BWD, aux=s["u"])
-            _, dgam, dbet = _norm_bwd(s["x2"], dh, 1, Lx, gamma=blk.ln2.weight, add_to=dx)
-            g[p + "ln2.weight"], g[p + "ln2.bias"] = dgam[0], dbet[0]
-            small += [dgam, dbet]
-            # x2 = x1 + proj2(attn2(q(ln1_1(x1)), kv(cond)))
-            dao, g[p + "attn2.proj.weight"], g[p + "attn2.proj.bias"] = lin_bwd(ls["proj2"], s["o2"], dx)
-            dq = torch.empty(M, D, device=dev)
-            dkv = torch.empty(B * Lc, 2 * D, device=dev)
-            if fused:
-                slot, dsc = att_site("b%d.att2" % li)
-                s["att2"].backward(dao, (dq, 0, D), (dkv, 0, 2 * D), (dkv, D, 2 * D), amax=slot, do_scale=dsc)
-            else:
-                s["att2"].backward(dao, dq, dkv[:, :D], dkv[:, D:])
-            dh, g[p + "attn2.query.weight"], g[p + "attn2.query.bias"] = lin_bwd(ls["q2"], s["h2"], dq)
-            _, dWkv, dbkv = lin_bwd(ls["kv2"], cond_h, dkv, need_dx=False)
-            g[p + "attn2.key.weight"], g[p + "attn2.value.weight"] = dWkv[:D], dWkv[D:]
-            g[p + "attn2.key.bias"], g[p + "attn2.value.bias"] = dbkv[:D], dbkv[D:]
-            _, dsc, dsh = _norm_bwd(s["x1"], dh, 0, Lx, table=s["tab2"], t=sample_rows, add_to=dx)
-            adaln_param_grads(blk.ln1_1, dsc, dsh, p + "ln1_1")
-            # x1 = x0 + proj1(attn1(qkv(ln1(x0))))
-            dao, g[p + "attn1.proj.weight"], g[p + "attn1.proj.bias"] = lin_bwd(ls["proj1"], s["o1"], dx)
-            dqkv = torch.empty(M, 3 * D, device=dev)
-            if fused:
-                slot, dsc = att_site("b%d.att1" % li)
-                s["att1"].backward(dao, (dqkv, 0, 3 * D), (dqkv, D, 3 * D), (dqkv, 2 * D, 3 * D), amax=slot, do_scale=dsc)
-            else:
-                s["att1"].backward(dao, dqkv[:, :D], dqkv[:, D:2 * D], dqkv[:, 2 * D:])
-            dh, dWqkv, dbqkv = lin_bwd(ls["qkv1"], s["h1"], dqkv)
-            for j, nm in enumerate(("query", "key", "value")):
-                g[p + "attn1.%s.weight" % nm], g[p + "attn1.%s.bias" % nm] = dWqkv[j * D:(j + 1) * D], dbqkv[j * D:(j + 1) * D]
-            _, dsc, dsh = _norm_bwd(s["x0"], dh, 0, Lx, table=s["tab1"], t=sample_rows, add_to=dx)
-            adaln_param_grads(blk.ln1, dsc, dsh, p + "ln1")
-            hand_over([p + n for n in ("mlp.2.weight", "mlp.0.weight", "attn2.proj.weight", "attn2.query.weight",
-                                       "attn2.key.weight", "attn2.value.weight", "attn1.proj.weight", "attn1.query.weight",
-                                       "attn1.key.weight", "attn1.value.weight")], now=False)
-        hand_over([])                            # the blocks still waiting
-        adaln_param_grads_all()
-        # the AdaLN parameter gradients (17 MB per block, 22 % of the gradient bytes) are final here: hand them to the
-        # overlapped reduction before the embedding backward and the closing un-scale instead of leaving them to finish()
-        hand_over([pfx + sfx for _, _, _, pfx in ada for sfx in (".linear.weight", ".emb.weight")])
-        # ---- embedding
-        demb = torch.zeros_like(emb.emb.weight)
-        nw = L_.lib().ds_embed_bwd_work_floats(M, D, demb.shape[0])
-        ework = torch.empty(nw, device=dev)
-        L_.check(L_.lib().ds_embed_bwd_ws(L_.ptr(dx), L_.ptr(xt), L_.ptr(demb), M, D, demb.shape[0], L_.ptr(ework), nw, L_.stream()))
-        g["transformer.content_emb.emb.weight"] = demb
-        dpos = torch.empty(Lx, D, device=dev)
-        L_.check(L_.lib().ds_colsum(L_.ptr(dx), L_.ptr(dpos), Lx, B, D, Lx * D, D, 0, L_.stream()))
-        Hh, Ww = emb.spatial_size
-        dpos3 = dpos.view(Hh, Ww, D)
-        dhh = _colsum(dpos3.reshape(Hh * Ww, D), Hh)                                                    # sum over w
-        g["transformer.content_emb.height_emb.weight"] = dhh
-        dw = torch.empty(Ww, D, device=dev)
-        L_.check(L_.lib().ds_colsum(L_.ptr(dpos), L_.ptr(dw), Ww, Hh, D, Ww * D, D, 0, L_.stream()))   # sum over h
-        g["transformer.content_emb.width_emb.weight"] = dw
-        small += [demb, dhh, dw]
-        if inv != 1.0:
-            torch._foreach_mul_(small, inv)
-        if site_amax is not None:
-            self._site_order = list(site_index)
-        if not calibrating:
-            self._steps += 1
-            self._last_loss = loss          # (device scalar; a captured iteration keeps updating this very tensor)
-        return loss, g
+    def _run(self, x0, cond_emb, t, pt, noise, on_grads=None):
+        """One training step under the calibrated scales (eager, or while a hipGraph records it: GraphedIteration)"""
+        loss, grads = _Pass(self, x0, cond_emb, t, pt, noise, calibrating=False, on_grads=on_grads).run()
+        self._steps += 1
+        self.policy._last_loss = loss       # (device scalar; a captured iteration keeps updating this very tensor)
+        return loss, grads
 
     # ---- optimizer -------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -1127,7 +815,7 @@ class GraphedIteration:
         self._body_update()
 
     def _body_grads(self):
-        self.loss, self.grads = self.step._run(*self.static, calibrating=False)
+        self.loss, self.grads = self.step._run(*self.static)
 
     def _body_update(self):
         st, loss, grads = self.step, self.loss, self.grads
@@ -1222,6 +910,6 @@ class GraphedIteration:
                 self.recapture(reason="a weight pre-scale 2^s left its place")
                 return True
         if st.check_loss_scale():
-            self.recapture(reason=getattr(st, "last_trip", "saturation monitor"))
+            self.recapture(reason=getattr(st, "last_trip", None) or "saturation monitor")
             return True
         return False

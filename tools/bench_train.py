@@ -32,7 +32,7 @@ def main():
     ap.add_argument("--ema-device", default="cuda", help="the reference keeps the EMA on the CPU (configs/caps.yaml:101)")
     ap.add_argument("--attention", default="fused", choices=("fused", "composed"),
                     help="fused: ds_attention + ds_attention_bwd (recompute); composed: grouped GEMMs with stored probabilities")
-    ap.add_argument("--monitor-hi", type=int, default=None, help="experiment: log2 upper bound of the saturation monitor's window")
+    ap.add_argument("--monitor-hi", type=int, default=None, help="experiment: log2 upper bound of the saturation monitor's window (LossScalePolicy.monitor_window)")
     ap.add_argument("--calib-log2", type=int, default=None, help="experiment: log2 of where a calibration puts the largest |dY|")
     ap.add_argument("--from-tokens", action="store_true", help="pre-made tokens + stand-in caption embedding (no prologue)")
     ap.add_argument("--weights", default="init", choices=("init", "trained"), help="synth.py weight profile of the denoiser")

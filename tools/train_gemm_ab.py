@@ -1,7 +1,7 @@
 """The training step's GEMM shapes (batch 20: M = 5300 rows; cross K|V: 1540 rows) on the packed-operand split kernel
 (gemm_f16x2.hip AMODE 2), per tile configuration -- and, for the weight-gradient products dW = dY^T X, per number of K-ranges
 S of the split-K launch INCLUDING the fixed-order reduction of the S partial results (ds_colsum).  Decides the dispatch
-thresholds of ds_launch_gemm_f16x2 for packed operands and modeling/train.py's _SplitGemm.split_k rule.
+thresholds of ds_launch_gemm_f16x2 for packed operands and modeling/train_gemm.py's _SplitGemm.split_k rule.
 Run on the GPU box:  python tools/train_gemm_ab.py"""
 import os
 import sys
