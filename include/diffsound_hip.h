@@ -210,6 +210,25 @@ int ds_sample_tail_rng(const float* logits, const int64_t* xt, const int64_t* t,
 int ds_q_sample_rng(const int64_t* x0, const int64_t* t, const int64_t* gids, unsigned long long seed, int call,
                     const float* sched, int64_t* out_tokens, int B, int L, int K, int T, ds_stream_t stream);
 
+/* ---- region-held tails (inpainting / continuation) -----------------------------------------------------------------
+ * ds_sample_tail_ex / ds_sample_tail_rng with keep u8[B][L] (non-zero: the position is held), known i64[B][L] (the token a
+ * held position carries) and mode.  Positions in content_token's time-major order (5 column + row).
+ *   mode 0 (clamp):   a held column writes known; a free column computes what the unheld entry computes from the same
+ *                     logits and the same uniforms (the noise is not re-indexed), so keep all zero == the unheld entry.
+ *   mode 1 (renoise): t is the posterior's timestep and the output x_{t-1}: a held column draws q(x_{t-1} | x_0 = known)
+ *                     (ds_q_sample's arithmetic, rng_stream 1, the call's own (pos, call, gid) counters), or writes known
+ *                     at t = 0.  In-kernel noise only: rejected by the entry on caller uniforms.
+ * keep == NULL runs the unheld kernel; keep without known is rejected.  Pass initial = 0 with keep: `initial` only affects
+ * non-[MASK] positions, and those of a mixed start state carry the ordinary log-one-hot. */
+int ds_sample_tail_hold(const float* logits, const int64_t* xt, const int64_t* t, const float* u, const float* sched,
+                        int64_t* out_tokens, float* dbg_log_pred, float* dbg_trunc, float* dbg_post, int B, int L, int K,
+                        int T, int initial, float trunc_r, int trunc_k, const unsigned char* keep, const int64_t* known,
+                        int mode, ds_stream_t stream);
+int ds_sample_tail_hold_rng(const float* logits, const int64_t* xt, const int64_t* t, const int64_t* gids,
+                            unsigned long long seed, int call, const float* sched, int64_t* out_tokens, int B, int L,
+                            int K, int T, int initial, float trunc_r, int trunc_k, const unsigned char* keep,
+                            const int64_t* known, int mode, ds_stream_t stream);
+
 /* forward terms of the training loss (DiffusionTransformer._train_loss, diffusion_transformer.py:408-476), one value
  * per grid position [B][L]: kl = KL(true posterior || model posterior) (:439-440), nll = the t == 0 decoder term
  * (:446), kl_aux = KL(x_0 || p(x_0|x_t)) over the K classes (:462); logits [B*L][K] of the network at (x_t, t),
@@ -416,6 +435,23 @@ int ds_denoiser_step_rng(const ds_denoiser* h, const int64_t* tokens_in, const i
 int ds_denoiser_sample_rng(const ds_denoiser* h, int64_t* tokens, int64_t* tokens_tmp, const int64_t* t_steps,
                            int n_calls, const float* kv, const int64_t* gids, unsigned long long seed, int call0, int B,
                            int initial, float trunc_r, int trunc_k, void* workspace, ds_stream_t stream);
+
+/* Region-held forms of ds_denoiser_step_ex, ds_denoiser_step_rng and ds_denoiser_sample_rng (see ds_sample_tail_hold):
+ * keep / known [B][seq_len], mode 0 clamp / 1 renoise (the *_rng entries only).  For the chain the caller supplies the
+ * start state in `tokens` (clamp: known where held, [MASK] elsewhere; renoise: held positions diffused to the first
+ * timestep), known stays constant over the calls, and call k uses Philox call index call0 + k on both streams. */
+int ds_denoiser_step_hold(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const int64_t* t_post,
+                          const float* kv, const float* u, int B, int initial, float trunc_r, int trunc_k,
+                          const unsigned char* keep, const int64_t* known, int mode, void* workspace,
+                          int64_t* tokens_out, ds_stream_t stream);
+int ds_denoiser_step_hold_rng(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const int64_t* t_post,
+                              const float* kv, const int64_t* gids, unsigned long long seed, int call, int B,
+                              int initial, float trunc_r, int trunc_k, const unsigned char* keep, const int64_t* known,
+                              int mode, void* workspace, int64_t* tokens_out, ds_stream_t stream);
+int ds_denoiser_sample_hold_rng(const ds_denoiser* h, int64_t* tokens, int64_t* tokens_tmp, const int64_t* t_steps,
+                                int n_calls, const float* kv, const int64_t* gids, unsigned long long seed, int call0,
+                                int B, int initial, float trunc_r, int trunc_k, const unsigned char* keep,
+                                const int64_t* known, int mode, void* workspace, ds_stream_t stream);
 
 /* per-launch HIP-event timing of the denoiser's GEMM launches (measurement only, bench.py) */
 int ds_profile_enable(int on);

@@ -410,19 +410,29 @@ extern "C" int ds_denoiser_forward(const ds_denoiser* h, const int64_t* tokens, 
     return forward_impl(h, tokens, t, kv, B, w, logits, logits_layout, (hipStream_t)stream, h->d.seq_len);
 }
 
+int ds_sample_tail_rows_hold(const float* logits, int logits_rows, const int64_t* xt, const int64_t* t, const float* u,
+                             const float* sched, int64_t* out_tokens, float* dbg_log_pred, float* dbg_trunc, float* dbg_post,
+                             int B, int L, int K, int T, int initial, float trunc_r, int trunc_k, ds_stream_t stream,
+                             const int64_t* gids, unsigned long long seed, int call, const unsigned char* keep,
+                             const int64_t* known, int mode);   // sampler.hip: ds_sample_tail_rows + the region-held form
+
 // t drives the network (AdaLN), t_post the posterior: they differ only for the skip-step sampler
 // (sample_fast, diffusion_transformer.py:796-803 calls q_posterior with t - skip_step)
 static int step_impl(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const int64_t* t_post,
                      const float* kv, const float* u, const int64_t* gids, unsigned long long seed, int call, int B,
                      int initial, float trunc_r, int trunc_k, void* workspace, int64_t* tokens_out, ds_stream_t stream,
-                     bool zero_kv_pad = true) {
+                     bool zero_kv_pad = true, const unsigned char* keep = nullptr, const int64_t* known = nullptr,
+                     int mode = 0) {
+    DS_CHECK_ARG(mode == 0 || mode == 1, "mode is 0 (clamp) or 1 (renoise)");      // before the forward is enqueued
+    DS_CHECK_ARG(!(mode == 1 && !gids), "renoise draws from the caption's Philox stream: not with caller uniforms");
+    DS_CHECK_ARG(!keep || known, "keep without known");
     Carve w;
     const int Lp = rows_per_sample(h, B);
     carve(h, B, workspace, &w, Lp);
     TRY(forward_impl(h, tokens_in, t, kv, B, w, w.logits, 0, (hipStream_t)stream, Lp, zero_kv_pad));
-    return ds_sample_tail_rows(w.logits, Lp, tokens_in, t_post ? t_post : t, u, h->d.sched, tokens_out, nullptr, nullptr,
-                               nullptr, B, h->d.seq_len, h->d.n_codes, h->d.n_steps, initial, trunc_r, trunc_k, stream,
-                               gids, seed, call);
+    return ds_sample_tail_rows_hold(w.logits, Lp, tokens_in, t_post ? t_post : t, u, h->d.sched, tokens_out, nullptr, nullptr,
+                                    nullptr, B, h->d.seq_len, h->d.n_codes, h->d.n_steps, initial, trunc_r, trunc_k, stream,
+                                    gids, seed, call, keep, known, mode);
 }
 
 extern "C" int ds_denoiser_step_ex(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t,
@@ -468,6 +478,57 @@ extern "C" int ds_denoiser_sample_rng(const ds_denoiser* h, int64_t* tokens, int
                                       (hipStream_t)stream);
         if (e != hipSuccess) {
             ds_set_error("ds_denoiser_sample_rng: hipMemcpyAsync: %s", hipGetErrorString(e));
+            return -2;
+        }
+    }
+    return 0;
+}
+
+// ---- region-held sampling (inpainting / continuation; sampler.hip SampleHold): the three entries above with keep u8[B][seq_len]
+// (non-zero: the position is held), known i64[B][seq_len] (its token) and mode (0 clamp, 1 renoise: in-kernel noise only).
+// keep == NULL runs the unheld kernels.
+extern "C" int ds_denoiser_step_hold(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t,
+                                     const int64_t* t_post, const float* kv, const float* u, int B, int initial,
+                                     float trunc_r, int trunc_k, const unsigned char* keep, const int64_t* known, int mode,
+                                     void* workspace, int64_t* tokens_out, ds_stream_t stream) {
+    DS_CHECK_ARG(h && tokens_in && t && kv && u && workspace && tokens_out && B > 0, "bad arguments");
+    return step_impl(h, tokens_in, t, t_post, kv, u, nullptr, 0ull, 0, B, initial, trunc_r, trunc_k, workspace, tokens_out,
+                     stream, true, keep, known, mode);
+}
+
+extern "C" int ds_denoiser_step_hold_rng(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t,
+                                         const int64_t* t_post, const float* kv, const int64_t* gids,
+                                         unsigned long long seed, int call, int B, int initial, float trunc_r, int trunc_k,
+                                         const unsigned char* keep, const int64_t* known, int mode, void* workspace,
+                                         int64_t* tokens_out, ds_stream_t stream) {
+    DS_CHECK_ARG(h && tokens_in && t && kv && gids && workspace && tokens_out && B > 0, "bad arguments");
+    return step_impl(h, tokens_in, t, t_post, kv, nullptr, gids, seed, call, B, initial, trunc_r, trunc_k, workspace,
+                     tokens_out, stream, true, keep, known, mode);
+}
+
+// the whole chain: `tokens` holds the caller's start state (held positions included), known stays constant over the calls;
+// in renoise mode call k re-draws the held positions at the posterior timestep of that call minus one (stream 1, call
+// call0 + k: the counters of the reverse step itself)
+extern "C" int ds_denoiser_sample_hold_rng(const ds_denoiser* h, int64_t* tokens, int64_t* tokens_tmp,
+                                           const int64_t* t_steps, int n_calls, const float* kv, const int64_t* gids,
+                                           unsigned long long seed, int call0, int B, int initial, float trunc_r,
+                                           int trunc_k, const unsigned char* keep, const int64_t* known, int mode,
+                                           void* workspace, ds_stream_t stream) {
+    DS_CHECK_ARG(h && tokens && tokens_tmp && t_steps && kv && gids && workspace && B > 0 && n_calls >= 0, "bad arguments");
+    DS_CHECK_ARG(mode == 0 || mode == 1, "mode is 0 (clamp) or 1 (renoise)");
+    DS_CHECK_ARG(!keep || known, "keep without known");
+    int64_t *cur = tokens, *nxt = tokens_tmp;
+    for (int k = 0; k < n_calls; ++k) {
+        const int64_t* tk = t_steps + (size_t)k * 2 * B;
+        TRY(step_impl(h, cur, tk, tk + B, kv, nullptr, gids, seed, call0 + k, B, initial && k == 0, trunc_r, trunc_k,
+                      workspace, nxt, stream, k == 0, keep, known, mode));
+        int64_t* sw = cur; cur = nxt; nxt = sw;
+    }
+    if (cur != tokens) {
+        hipError_t e = hipMemcpyAsync(tokens, cur, (size_t)B * h->d.seq_len * sizeof(int64_t), hipMemcpyDeviceToDevice,
+                                      (hipStream_t)stream);
+        if (e != hipSuccess) {
+            ds_set_error("ds_denoiser_sample_hold_rng: hipMemcpyAsync: %s", hipGetErrorString(e));
             return -2;
         }
     }

@@ -93,8 +93,29 @@ struct SampleRng {
     int call;
 };
 
-template <int NPL, bool RNG>
-__global__ __launch_bounds__(256) void ds_sample_tail_kernel(const SampleParams p, const SampleRng g) {
+// REGION-HELD form (inpainting / continuation: the *_hold entries).  keep[b][pos] != 0: the position is held and carries
+// known[b][pos]; positions in content_token's time-major order (5 column + row).  A held column's wave writes its token and
+// exits before the log-softmax; a free column runs the body below unchanged -- same logits, same uniforms (the [B][K+1][L]
+// tensor keeps its shape, the Philox counters are positional), so with keep all zero the tokens are those of the unheld
+// kernels bit for bit.  mode 0 (clamp): a held column writes known.  mode 1 (renoise, in-kernel noise only): the call's
+// output is x_{t_post - 1} (t_post = p.t), and a held column draws q(x_{t_post-1} | x_0 = known) -- ds_q_sample_column, on
+// stream 1 of the caption with the (pos, call, gid) counters of this call -- or writes known when t_post = 0.
+// `initial` has no per-position form and callers pass 0 with keep: it is read for a non-[MASK] x_t only (`off` below; every
+// is_mask branch ignores it), and a mixed start state only adds non-[MASK] positions with the ordinary 0 / log 1e-30 one-hot.
+// A separate kernel argument and separate __global__ wrappers over one body: the unheld kernels keep their arguments,
+// registers and (zero) private segment.
+struct SampleHold {
+    const unsigned char* keep;   // [B][L]
+    const int64_t* known;        // [B][L]
+    int mode;                    // 0: clamp, 1: renoise
+};
+
+__device__ __forceinline__ int ds_q_sample_column(int x, int tt, const float* __restrict__ sched, int T1, int K, int lane,
+                                                  const float* up, int L, int pos, unsigned gid, unsigned seed_lo,
+                                                  unsigned seed_hi, int call);
+
+template <int NPL, bool RNG, bool HOLD>
+__device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const SampleRng& g, const SampleHold& h) {
     constexpr int K = NPL * 64;
     __shared__ float s_lp[4][K];
     __shared__ __attribute__((aligned(16))) float s_pr[4][K];
@@ -104,6 +125,19 @@ __global__ __launch_bounds__(256) void ds_sample_tail_kernel(const SampleParams 
     const bool live = col < p.B * p.L;  // a dead wave shadows the last column and writes nothing
     if (!live) col = p.B * p.L - 1;
     const int b = col / p.L, pos = col - b * p.L;
+    if constexpr (HOLD) {
+        if (h.keep[col]) {       // wave-uniform: the whole wave leaves (no block-wide barrier below in this form)
+            int tok = (int)h.known[col];
+            if constexpr (RNG) {
+                const int tp = (int)p.t[b];
+                if (h.mode == 1 && tp > 0)
+                    tok = ds_q_sample_column(tok, tp - 1, p.sched, p.T + 1, K, lane, nullptr, p.L, pos, (unsigned)g.gid[b],
+                                             g.seed_lo, g.seed_hi, g.call);
+            }
+            if (lane == 0 && live) p.out_tokens[col] = tok;
+            return;
+        }
+    }
 
     // ---- predict_start: float64 log-softmax over the K real classes ----
     float v[NPL];
@@ -139,7 +173,8 @@ __global__ __launch_bounds__(256) void ds_sample_tail_kernel(const SampleParams 
     if (p.trunc_k > 0) {
 #pragma unroll
         for (int j = 0; j < NPL; ++j) s_lp[w][j * 64 + lane] = lp[j];
-        __syncthreads();
+        if constexpr (HOLD) __builtin_amdgcn_wave_barrier();   // s_lp[w] is this wave's own; held waves have left
+        else __syncthreads();
         int rank[NPL];
 #pragma unroll
         for (int j = 0; j < NPL; ++j) rank[j] = 0;
@@ -328,6 +363,15 @@ __global__ __launch_bounds__(256) void ds_sample_tail_kernel(const SampleParams 
         if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
     }
     if (lane == 0 && live) p.out_tokens[col] = bidx;
+}
+
+template <int NPL, bool RNG>
+__global__ __launch_bounds__(256) void ds_sample_tail_kernel(const SampleParams p, const SampleRng g) {
+    ds_sample_tail_body<NPL, RNG, false>(p, g, SampleHold{nullptr, nullptr, 0});
+}
+template <int NPL, bool RNG>
+__global__ __launch_bounds__(256) void ds_sample_tail_hold_kernel(const SampleParams p, const SampleRng g, const SampleHold h) {
+    ds_sample_tail_body<NPL, RNG, true>(p, g, h);
 }
 
 // ---- training-loss terms (DiffusionTransformer._train_loss, diffusion_transformer.py:408-476), forward only ----
@@ -573,21 +617,15 @@ extern "C" int ds_loss_tail(const float* logits, const int64_t* x0, const int64_
 // ---- q_sample (diffusion_transformer.py:370-377): x_t ~ q(x_t | x_0) for token ids, Gumbel-argmax ----------
 // log q(x_t = c | x_0) = log_add_exp(log_onehot(x_0)[c] + log_cumprod_at[t], log_cumprod_bt[t]) for the K classes,
 // log_add_exp(log_onehot(x_0)[K] + log_1_min_cumprod_ct[t], log_cumprod_ct[t]) for [MASK]  (q_pred, :253-267)
-__global__ __launch_bounds__(256) void ds_q_sample_kernel(const int64_t* __restrict__ x0, const int64_t* __restrict__ t,
-                                                          const float* __restrict__ u, const float* __restrict__ sched,
-                                                          int64_t* __restrict__ out, int B, int L, int K, int T,
-                                                          const int64_t* __restrict__ gid, unsigned seed_lo,
-                                                          unsigned seed_hi, int call) {
-    const int col = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (col >= B * L) return;
-    const int lane = threadIdx.x & 63;
-    const int b = col / L, pos = col - b * L;
-    const int T1 = T + 1, tt = (int)t[b];
+// One column, one wavefront: the draw for x_0 = x at timestep tt, every lane returns the token.  up != nullptr: the column's
+// uniforms in the [B][K+1][L] layout (up = u + b (K+1) L + pos); else stream 1 of caption gid's Philox draws (ds_u01 above).
+// Shared by ds_q_sample_kernel and the renoise mode of the region-held sampling tail.
+__device__ __forceinline__ int ds_q_sample_column(int x, int tt, const float* __restrict__ sched, int T1, int K, int lane,
+                                                  const float* up, int L, int pos, unsigned gid, unsigned seed_lo,
+                                                  unsigned seed_hi, int call) {
     const float lcat = sched[4 * T1 + tt], lcbt = sched[5 * T1 + tt], lcct = sched[6 * T1 + tt],
                 l1mcct = sched[7 * T1 + tt];
-    const int x = (int)x0[col];
     const float hit = lae(0.f + lcat, lcbt), off = lae(LOG_ZERO_F + lcat, lcbt);
-    const float* up = u ? u + (size_t)b * (K + 1) * L + pos : nullptr;
     float best = -INFINITY;
     int bi = 0x7fffffff;
     ds_u32x4 w4 = {0u, 0u, 0u, 0u};
@@ -596,9 +634,9 @@ __global__ __launch_bounds__(256) void ds_q_sample_kernel(const int64_t* __restr
         float uu;
         if (up) {
             uu = up[(size_t)c * L];
-        } else {                                   // stream 1 of the caption's Philox draws (ds_u01 above)
+        } else {
             const int j = c >> 6;
-            if ((j & 3) == 0) w4 = ds_philox4x32_10((j >> 2) * 64 + (c & 63), pos | (1u << 16), call, (unsigned)gid[b], seed_lo, seed_hi);
+            if ((j & 3) == 0) w4 = ds_philox4x32_10((j >> 2) * 64 + (c & 63), pos | (1u << 16), call, gid, seed_lo, seed_hi);
             uu = ds_u01((j & 3) == 0 ? w4.x : (j & 3) == 1 ? w4.y : (j & 3) == 2 ? w4.z : w4.w);
         }
         const float g = -logf(-logf(uu + 1e-30f) + 1e-30f) + lq;
@@ -610,6 +648,21 @@ __global__ __launch_bounds__(256) void ds_q_sample_kernel(const int64_t* __restr
         const int oi = __shfl_xor(bi, o);
         if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
     }
+    return bi;
+}
+
+__global__ __launch_bounds__(256) void ds_q_sample_kernel(const int64_t* __restrict__ x0, const int64_t* __restrict__ t,
+                                                          const float* __restrict__ u, const float* __restrict__ sched,
+                                                          int64_t* __restrict__ out, int B, int L, int K, int T,
+                                                          const int64_t* __restrict__ gid, unsigned seed_lo,
+                                                          unsigned seed_hi, int call) {
+    const int col = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (col >= B * L) return;
+    const int lane = threadIdx.x & 63;
+    const int b = col / L, pos = col - b * L;
+    const float* up = u ? u + (size_t)b * (K + 1) * L + pos : nullptr;
+    const int bi = ds_q_sample_column((int)x0[col], (int)t[b], sched, T + 1, K, lane, up, L, pos, u ? 0u : (unsigned)gid[b],
+                                      seed_lo, seed_hi, call);
     if (lane == 0) out[col] = bi;
 }
 
@@ -665,27 +718,65 @@ extern "C" int ds_philox_uniforms(const int64_t* gids, unsigned long long seed, 
     return 0;
 }
 
-// logits_rows >= L: rows of `logits` per sample ([B * logits_rows][K]; the denoiser's padded-row mode, api.hip)
-int ds_sample_tail_rows(const float* logits, int logits_rows, const int64_t* xt, const int64_t* t, const float* u,
+// logits_rows >= L: rows of `logits` per sample ([B * logits_rows][K]; the denoiser's padded-row mode, api.hip).
+// keep != nullptr: the region-held kernels (known [B][L], mode 0 clamp / 1 renoise); nullptr: the unheld ones.
+int ds_sample_tail_rows_hold(const float* logits, int logits_rows, const int64_t* xt, const int64_t* t, const float* u,
                         const float* sched, int64_t* out_tokens, float* dbg_log_pred, float* dbg_trunc, float* dbg_post,
                         int B, int L, int K, int T, int initial, float trunc_r, int trunc_k, ds_stream_t stream_,
-                        const int64_t* gids, unsigned long long seed, int call) {
+                             const int64_t* gids, unsigned long long seed, int call, const unsigned char* keep,
+                             const int64_t* known, int mode) {
     hipStream_t stream = (hipStream_t)stream_;
     DS_CHECK_ARG(logits && xt && t && (u || gids) && sched && out_tokens, "null pointer");
     DS_CHECK_ARG(K == 256 || K == 512, "codebook size must be 256 or 512");
     DS_CHECK_ARG(trunc_k >= 0 && !(trunc_k > 0 && trunc_r >= 0.f), "top-k and top-r truncation are exclusive");
     DS_CHECK_ARG(logits_rows >= L && L < 65536, "logits rows per sample");
+    DS_CHECK_ARG(mode == 0 || mode == 1, "mode is 0 (clamp) or 1 (renoise)");
+    DS_CHECK_ARG(!(mode == 1 && u), "renoise draws from the caption's Philox stream: not with caller uniforms");
+    DS_CHECK_ARG(!keep || known, "keep without known");
     SampleParams p{logits, xt, t, u, sched, out_tokens, dbg_log_pred, dbg_trunc, dbg_post, B, L, T, initial, trunc_r,
                    trunc_k, logits_rows};
     const SampleRng g{gids, (unsigned)seed, (unsigned)(seed >> 32), call};
     const int cols = B * L;
     const dim3 grid((cols + 3) / 4);
-    if (K == 256 && u) hipLaunchKernelGGL((ds_sample_tail_kernel<4, false>), grid, dim3(256), 0, stream, p, g);
+    if (keep) {
+        const SampleHold h{keep, known, mode};
+        if (K == 256 && u) hipLaunchKernelGGL((ds_sample_tail_hold_kernel<4, false>), grid, dim3(256), 0, stream, p, g, h);
+        else if (K == 256) hipLaunchKernelGGL((ds_sample_tail_hold_kernel<4, true>), grid, dim3(256), 0, stream, p, g, h);
+        else if (u) hipLaunchKernelGGL((ds_sample_tail_hold_kernel<8, false>), grid, dim3(256), 0, stream, p, g, h);
+        else hipLaunchKernelGGL((ds_sample_tail_hold_kernel<8, true>), grid, dim3(256), 0, stream, p, g, h);
+    } else if (K == 256 && u) hipLaunchKernelGGL((ds_sample_tail_kernel<4, false>), grid, dim3(256), 0, stream, p, g);
     else if (K == 256) hipLaunchKernelGGL((ds_sample_tail_kernel<4, true>), grid, dim3(256), 0, stream, p, g);
     else if (u) hipLaunchKernelGGL((ds_sample_tail_kernel<8, false>), grid, dim3(256), 0, stream, p, g);
     else hipLaunchKernelGGL((ds_sample_tail_kernel<8, true>), grid, dim3(256), 0, stream, p, g);
     DS_CHECK_LAUNCH();
     return 0;
+}
+
+int ds_sample_tail_rows(const float* logits, int logits_rows, const int64_t* xt, const int64_t* t, const float* u,
+                        const float* sched, int64_t* out_tokens, float* dbg_log_pred, float* dbg_trunc, float* dbg_post,
+                        int B, int L, int K, int T, int initial, float trunc_r, int trunc_k, ds_stream_t stream,
+                        const int64_t* gids, unsigned long long seed, int call) {
+    return ds_sample_tail_rows_hold(logits, logits_rows, xt, t, u, sched, out_tokens, dbg_log_pred, dbg_trunc, dbg_post, B, L, K,
+                                    T, initial, trunc_r, trunc_k, stream, gids, seed, call, nullptr, nullptr, 0);
+}
+
+// region-held tails (see SampleHold): ds_sample_tail_ex / ds_sample_tail_rng + keep, known, mode
+extern "C" int ds_sample_tail_hold(const float* logits, const int64_t* xt, const int64_t* t, const float* u,
+                                   const float* sched, int64_t* out_tokens, float* dbg_log_pred, float* dbg_trunc,
+                                   float* dbg_post, int B, int L, int K, int T, int initial, float trunc_r, int trunc_k,
+                                   const unsigned char* keep, const int64_t* known, int mode, ds_stream_t stream) {
+    DS_CHECK_ARG(u, "null pointer");
+    return ds_sample_tail_rows_hold(logits, L, xt, t, u, sched, out_tokens, dbg_log_pred, dbg_trunc, dbg_post, B, L, K, T,
+                                    initial, trunc_r, trunc_k, stream, nullptr, 0ull, 0, keep, known, mode);
+}
+
+extern "C" int ds_sample_tail_hold_rng(const float* logits, const int64_t* xt, const int64_t* t, const int64_t* gids,
+                                       unsigned long long seed, int call, const float* sched, int64_t* out_tokens, int B,
+                                       int L, int K, int T, int initial, float trunc_r, int trunc_k,
+                                       const unsigned char* keep, const int64_t* known, int mode, ds_stream_t stream) {
+    DS_CHECK_ARG(gids, "null pointer");
+    return ds_sample_tail_rows_hold(logits, L, xt, t, nullptr, sched, out_tokens, nullptr, nullptr, nullptr, B, L, K, T,
+                                    initial, trunc_r, trunc_k, stream, gids, seed, call, keep, known, mode);
 }
 
 extern "C" int ds_sample_tail_ex(const float* logits, const int64_t* xt, const int64_t* t, const float* u,

@@ -104,15 +104,8 @@ class DALLE(nn.Module):
                 "batch={'condition_embed_token': f32[B,77,512]} or {'condition_token': i64[B,77]}")
         return cond
 
-    @torch.no_grad()
-    def generate_content(self, *, batch, condition=None, filter_ratio=0.5, temperature=1.0, content_ratio=0.0,
-                         replicate=1, return_att_weight=False, sample_type="top0.85r"):
-        self.eval()
-        condition = self.prepare_condition(batch=batch, condition=condition)
-        if replicate != 1:
-            for k in condition:
-                if condition[k] is not None:
-                    condition[k] = torch.cat([condition[k] for _ in range(replicate)], dim=0)
+    def _install_sample_type(self, sample_type):
+        """The `sample_type` mini-language (:179-247) applied to the transformer; returns its comma-separated parts."""
         parts = sample_type.split(",")
         tr = self.transformer
         if len(parts) > 1 and parts[1][:1] == "q":           # repeat-step sampler (:135-143, :205-206)
@@ -126,14 +119,76 @@ class DALLE(nn.Module):
             else:
                 print("wrong sample type")                    # the reference's reaction (:176-177)
             self.truncation_forward = True
+        return parts
+
+    @staticmethod
+    def _replicated_caption_ids(batch, replicate):
+        ids = torch.as_tensor(batch["caption_ids"], dtype=torch.long)
+        return torch.cat([ids for _ in range(replicate)]) + \
+            torch.arange(replicate).repeat_interleave(ids.numel()) * int(batch.get("caption_id_stride", 1 << 24))
+
+    @torch.no_grad()
+    def inpaint_content(self, *, batch, keep_mask, keep_mode="clamp", replicate=1, sample_type="top0.85r"):
+        """Region-held generation (not in the reference, whose content_ratio slices the token vector and cannot run for any
+        value but 1): the positions of `keep_mask` (bool[B, 265], True = held, time-major like content_token;
+        pipeline.spans_to_keep_mask builds it from seconds) keep the tokens of the batch's content, the others are generated
+        from [MASK] under the batch's caption with the held ones as context of the denoiser.  batch: the caption as in
+        prepare_condition ('text', 'condition_token' or 'condition_embed_token') and the content as in prepare_content
+        ('image', or 'audio' with 'audio_rate') or already encoded ('content_token' i64[B, 265]); 'caption_ids' / 'seed' as in
+        generate_content.  keep_mode "clamp" | "renoise": DiffusionTransformer.sample.  Every sample_type of generate_content
+        works.  Returns {'content': mel image [B r, 1, 80, 848], 'content_token'}.
+
+        The held TOKENS of the result are exactly the input's.  The mel is the codec's rendering of the whole grid, held
+        region included: not the input's samples (the decoder's lowest level attends over all 265 positions), and the
+        original mel or audio is not pasted back."""
+        self.eval()
+        condition = self.prepare_condition(batch=batch)
+        tokens = batch.get("content_token")
+        if tokens is None:
+            tokens = self.prepare_content(batch)["content_token"]
+        tokens = tokens.to(self.device)
+        keep = torch.as_tensor(keep_mask).to(self.device)
+        if replicate != 1:
+            for k in condition:
+                if torch.is_tensor(condition[k]):
+                    condition[k] = torch.cat([condition[k] for _ in range(replicate)], dim=0)
+            tokens = torch.cat([tokens for _ in range(replicate)], dim=0)
+            keep = torch.cat([keep for _ in range(replicate)], dim=0)
+        parts = self._install_sample_type(sample_type)
+        tr = self.transformer
+        kw = dict(condition_token=condition.get("condition_token"), condition_mask=condition.get("condition_mask"),
+                  condition_embed=condition.get("condition_embed_token"), content_token=tokens, filter_ratio=0,
+                  return_logits=False, print_log=False, keep_mask=keep, keep_mode=keep_mode)
+        if batch.get("caption_ids") is not None:
+            kw["caption_ids"] = self._replicated_caption_ids(batch, replicate)
+        if batch.get("seed") is not None:
+            kw["seed"] = int(batch["seed"])
+        if len(parts) == 2 and parts[1][:4] == "fast":
+            trans_out = tr.sample_fast(skip_step=int(parts[1][4:]), **kw)
+        else:
+            trans_out = tr.sample(**kw)
+        out_tokens = trans_out["content_token"]
+        content = self.decode_to_img(out_tokens, (out_tokens.shape[0], 256, 5, 53))
+        self.train()
+        return {"content": content, "content_token": out_tokens}
+
+    @torch.no_grad()
+    def generate_content(self, *, batch, condition=None, filter_ratio=0.5, temperature=1.0, content_ratio=0.0,
+                         replicate=1, return_att_weight=False, sample_type="top0.85r"):
+        self.eval()
+        condition = self.prepare_condition(batch=batch, condition=condition)
+        if replicate != 1:
+            for k in condition:
+                if condition[k] is not None:
+                    condition[k] = torch.cat([condition[k] for _ in range(replicate)], dim=0)
+        parts = self._install_sample_type(sample_type)
+        tr = self.transformer
         kw = dict(condition_token=condition.get("condition_token"), condition_mask=condition.get("condition_mask"),
                   condition_embed=condition.get("condition_embed_token"), content_token=None,
                   filter_ratio=filter_ratio, temperature=temperature, return_att_weight=return_att_weight,
                   return_logits=False, print_log=False, sample_type=sample_type)
         if batch.get("caption_ids") is not None:             # per-caption in-kernel noise (diffusion.py rng_mode)
-            ids = torch.as_tensor(batch["caption_ids"], dtype=torch.long)
-            kw["caption_ids"] = torch.cat([ids for _ in range(replicate)]) + \
-                torch.arange(replicate).repeat_interleave(ids.numel()) * int(batch.get("caption_id_stride", 1 << 24))
+            kw["caption_ids"] = self._replicated_caption_ids(batch, replicate)
         if batch.get("seed") is not None:
             kw["seed"] = int(batch["seed"])
         if len(parts) == 2 and parts[1][:4] == "fast":       # skip-step sampler (:211-222)

@@ -159,9 +159,10 @@ class DiffusionTransformer(nn.Module):
         return torch.log(oh.clamp(min=1e-30))
 
     @torch.no_grad()
-    def p_sample_tokens(self, x_t, kv, t, u, initial, out=None, t_post=None, slot=0):
+    def p_sample_tokens(self, x_t, kv, t, u, initial, out=None, t_post=None, slot=0, hold=None):
         """x_t i64[B,L] -> x_{t-1} i64[B,L]; kv from transformer.condition_kv().  t_post: the posterior's timestep
-        vector when it differs from the network's (sample_fast)."""
+        vector when it differs from the network's (sample_fast).  hold: (keep u8[B,L], known i64[B,L], mode) of the
+        region-held step (_hold_start); on caller uniforms only mode 0 (clamp) exists."""
         tr = self.transformer
         sched = self._schedule_table()
         p = tr.packed(sched)
@@ -169,14 +170,22 @@ class DiffusionTransformer(nn.Module):
         if out is None:
             out = torch.empty_like(x_t)
         r, k = self._truncation()
+        if hold is not None:
+            _lib.check(_lib.lib().ds_denoiser_step_hold(
+                p["handle"], _lib.ptr(x_t), _lib.ptr(t), _lib.ptr(t_post), _lib.ptr(kv), _lib.ptr(u), B, 0, r, k,
+                _lib.ptr(hold[0]), _lib.ptr(hold[1]), int(hold[2]), _lib.ptr(tr.workspace(B, sched, slot)), _lib.ptr(out),
+                _lib.stream()))
+            return out
         _lib.check(_lib.lib().ds_denoiser_step_ex(p["handle"], _lib.ptr(x_t), _lib.ptr(t), _lib.ptr(t_post), _lib.ptr(kv),
                                                   _lib.ptr(u), B, int(initial), r, k,
                                                   _lib.ptr(tr.workspace(B, sched, slot)), _lib.ptr(out), _lib.stream()))
         return out
 
     @torch.no_grad()
-    def p_sample_tokens_rng(self, x_t, kv, t, caption_ids, call, initial, out=None, t_post=None, slot=0, seed=None):
-        """p_sample_tokens with the noise drawn in the kernel: Philox stream of (seed, caption_ids[b], call)."""
+    def p_sample_tokens_rng(self, x_t, kv, t, caption_ids, call, initial, out=None, t_post=None, slot=0, seed=None,
+                            hold=None):
+        """p_sample_tokens with the noise drawn in the kernel: Philox stream of (seed, caption_ids[b], call).  hold as in
+        p_sample_tokens, mode 1 (renoise) included."""
         tr = self.transformer
         sched = self._schedule_table()
         p = tr.packed(sched)
@@ -184,6 +193,12 @@ class DiffusionTransformer(nn.Module):
         if out is None:
             out = torch.empty_like(x_t)
         r, k = self._truncation()
+        if hold is not None:
+            _lib.check(_lib.lib().ds_denoiser_step_hold_rng(
+                p["handle"], _lib.ptr(x_t), _lib.ptr(t), _lib.ptr(t_post), _lib.ptr(kv), _lib.ptr(caption_ids),
+                int(self.sample_seed if seed is None else seed), int(call), B, 0, r, k, _lib.ptr(hold[0]),
+                _lib.ptr(hold[1]), int(hold[2]), _lib.ptr(tr.workspace(B, sched, slot)), _lib.ptr(out), _lib.stream()))
+            return out
         _lib.check(_lib.lib().ds_denoiser_step_rng(
             p["handle"], _lib.ptr(x_t), _lib.ptr(t), _lib.ptr(t_post), _lib.ptr(kv), _lib.ptr(caption_ids),
             int(self.sample_seed if seed is None else seed), int(call), B, int(initial), r, k,
@@ -331,9 +346,46 @@ class DiffusionTransformer(nn.Module):
         oh = torch.nn.functional.one_hot(xt, self.num_classes).permute(0, 2, 1).float()
         return torch.log(oh.clamp(min=1e-30))
 
-    def _reverse(self, cond_emb, steps, noise_fn, return_logits, start_tokens=None, caption_ids=None, seed=None):
+    KEEP_MODES = {"clamp": 0, "renoise": 1}
+
+    def _hold_start(self, keep_mask, keep_mode, content_token, B, noise_fn, caption_ids, seed):
+        """Region-held sampling (inpainting / continuation): keep_mask bool[B, L] (True = held), content_token supplies the
+        held tokens.  Returns (hold, start tokens, caption ids): hold = (keep u8, known i64, mode) for the *_hold entries.
+        clamp: the start state is known where held, [MASK] elsewhere.  renoise: the held positions follow the forward
+        process -- they start from q_sample(known, T - 1) on stream 1 of the caption's Philox draws (call 0), and reverse
+        call k (Philox call k + 1 on both streams) re-draws them at that call's posterior timestep minus one; this mode
+        exists with in-kernel noise only, so it always samples per caption (caption_ids default 0 .. B-1)."""
+        if keep_mode not in self.KEEP_MODES:
+            raise ValueError("keep_mode is 'clamp' or 'renoise', got %r" % (keep_mode,))
+        if content_token is None:
+            raise ValueError("keep_mask holds positions of given content: pass content_token i64[B, %d]" % self.content_seq_len)
+        device, L, K = self.device, self.content_seq_len, self.num_classes - 1
+        known = content_token.to(device).long().contiguous()
+        keep = torch.as_tensor(keep_mask).to(device)
+        if tuple(known.shape) != (B, L) or tuple(keep.shape) != (B, L):
+            raise ValueError("keep_mask and content_token must be [%d, %d]: got %s and %s"
+                             % (B, L, tuple(keep.shape), tuple(known.shape)))
+        keep = keep != 0
+        mode = self.KEEP_MODES[keep_mode]
+        if mode == 0:
+            x = torch.where(keep, known, torch.full_like(known, K))
+        else:
+            if noise_fn is not None:
+                raise ValueError("keep_mode='renoise' draws the held positions' noise inside the kernel: not with noise_fn")
+            caption_ids = self._caption_ids(caption_ids, B, device)
+            t = torch.full((B,), self.num_timesteps - 1, device=device, dtype=torch.long)
+            xs = torch.empty_like(known)
+            _lib.check(_lib.lib().ds_q_sample_rng(_lib.ptr(known), _lib.ptr(t), _lib.ptr(caption_ids),
+                                                  int(self.sample_seed if seed is None else seed), 0,
+                                                  _lib.ptr(self._schedule_table()), _lib.ptr(xs), B, L, K,
+                                                  self.num_timesteps, _lib.stream()))
+            x = torch.where(keep, xs, torch.full_like(known, K))
+        return (keep.to(torch.uint8).contiguous(), known, mode), x, caption_ids
+
+    def _reverse(self, cond_emb, steps, noise_fn, return_logits, start_tokens=None, caption_ids=None, seed=None, hold=None):
         """steps: list of (t, t_post) pairs, first one from the all-[MASK] state (or from start_tokens, already
-        diffused to the first t).  The 'q' repeat sampler
+        diffused to the first t).  hold: (keep, known, mode) of _hold_start -- every call then runs the region-held
+        kernels and start_tokens is the mixed start state.  The 'q' repeat sampler
         (dalle_spec.py:135-143: with probability `repeat_rate` a step is applied twice at the same t) draws from
         Python's `random` exactly like the reference's wrapper: one random.random() per step."""
         import random
@@ -359,10 +411,16 @@ class DiffusionTransformer(nn.Module):
             t_steps = torch.tensor(calls, dtype=torch.long, device=device).view(-1, 2, 1).expand(-1, 2, B).contiguous()
             tmp = torch.empty_like(x)
             r, k = self._truncation()
-            _lib.check(_lib.lib().ds_denoiser_sample_rng(
-                p["handle"], _lib.ptr(x), _lib.ptr(tmp), _lib.ptr(t_steps), len(calls), _lib.ptr(kv), _lib.ptr(gids),
-                int(self.sample_seed if seed is None else seed), 0, B, int(start_tokens is None), r, k,
-                _lib.ptr(tr.workspace(B, sched, 0)), _lib.stream()))
+            if hold is not None:        # (renoise: stream-1 call 0 was the start state's q_sample, so the calls start at 1)
+                _lib.check(_lib.lib().ds_denoiser_sample_hold_rng(
+                    p["handle"], _lib.ptr(x), _lib.ptr(tmp), _lib.ptr(t_steps), len(calls), _lib.ptr(kv), _lib.ptr(gids),
+                    int(self.sample_seed if seed is None else seed), 1 if hold[2] == 1 else 0, B, 0, r, k,
+                    _lib.ptr(hold[0]), _lib.ptr(hold[1]), int(hold[2]), _lib.ptr(tr.workspace(B, sched, 0)), _lib.stream()))
+            else:
+                _lib.check(_lib.lib().ds_denoiser_sample_rng(
+                    p["handle"], _lib.ptr(x), _lib.ptr(tmp), _lib.ptr(t_steps), len(calls), _lib.ptr(kv), _lib.ptr(gids),
+                    int(self.sample_seed if seed is None else seed), 0, B, int(start_tokens is None), r, k,
+                    _lib.ptr(tr.workspace(B, sched, 0)), _lib.stream()))
             out = {"content_token": x}
             if return_logits:
                 out["logits"] = torch.nn.functional.one_hot(x, K1).permute(0, 2, 1).float()
@@ -382,7 +440,8 @@ class DiffusionTransformer(nn.Module):
                 calls += 1
                 t = torch.full((B,), step, device=device, dtype=torch.long)
                 tp = None if step_post == step else torch.full((B,), step_post, device=device, dtype=torch.long)
-                self.p_sample_tokens(x, kv, t, u, initial=(start_tokens is None and i == 0 and rep == 0), out=nxt, t_post=tp)
+                self.p_sample_tokens(x, kv, t, u, initial=(start_tokens is None and i == 0 and rep == 0), out=nxt, t_post=tp,
+                                     hold=hold)
                 x, nxt = nxt, x
         out = {"content_token": x}
         if return_logits:
@@ -392,15 +451,27 @@ class DiffusionTransformer(nn.Module):
     @torch.no_grad()
     def sample(self, condition_token, condition_mask, condition_embed, content_token=None, filter_ratio=0.5,
                temperature=1.0, return_att_weight=False, return_logits=False, content_logits=None,
-               print_log=True, noise_fn=None, caption_ids=None, seed=None, **kwargs):
+               print_log=True, noise_fn=None, caption_ids=None, seed=None, keep_mask=None, keep_mode="clamp", **kwargs):
         """Reverse diffusion from the all-[MASK] state (:587-659, filter_ratio == 0 branch).
 
         noise_fn(step, shape) may supply the uniforms (tests inject the oracle's noise; with the 'q' repeat sampler
         active the first argument is the running p_sample call index instead of the timestep).  caption_ids (i64[B],
-        global caption indices) selects the in-kernel per-caption noise (see rng_mode); seed overrides sample_seed."""
+        global caption indices) selects the in-kernel per-caption noise (see rng_mode); seed overrides sample_seed.
+
+        keep_mask (bool[B, L], True = held; not in the reference): region-held sampling -- the held positions carry
+        content_token's tokens through the whole chain as context of the denoiser, the others are generated from [MASK]
+        (filter_ratio must resolve to step 0).  keep_mode "clamp" keeps them clean, "renoise" lets them follow the forward
+        process (_hold_start).  The held TOKENS of the result are exactly content_token's."""
         cond_emb = self._cond(condition_token, condition_embed)
         T = self.num_timesteps
         start_step = int(T * filter_ratio)
+        if keep_mask is not None:
+            if start_step != 0:
+                raise ValueError("keep_mask samples the free positions from [MASK]: filter_ratio must resolve to step 0")
+            hold, x, caption_ids = self._hold_start(keep_mask, keep_mode, content_token, cond_emb.shape[0], noise_fn,
+                                                    caption_ids, seed)
+            return self._reverse(cond_emb, [(s_, s_) for s_ in range(T - 1, -1, -1)], noise_fn, return_logits,
+                                 start_tokens=x, caption_ids=caption_ids, seed=seed, hold=hold)
         if start_step == 0:
             return self._reverse(cond_emb, [(s_, s_) for s_ in range(T - 1, -1, -1)], noise_fn, return_logits,
                                  caption_ids=caption_ids, seed=seed)
@@ -433,18 +504,26 @@ class DiffusionTransformer(nn.Module):
     @torch.no_grad()
     def sample_fast(self, condition_token, condition_mask, condition_embed, content_token=None, filter_ratio=0.5,
                     temperature=1.0, return_att_weight=False, return_logits=False, content_logits=None,
-                    print_log=True, skip_step=1, noise_fn=None, caption_ids=None, seed=None, **kwargs):
+                    print_log=True, skip_step=1, noise_fn=None, caption_ids=None, seed=None, keep_mask=None,
+                    keep_mode="clamp", **kwargs):
         """Skip-step sampler (:748-812): timesteps T-1, T-2-skip, ... (0 appended), the network sees t, the
         posterior t - skip_step while t > skip_step.  The reference calls p_pred's pieces directly, so the 'q'
-        wrapper on p_sample never applies here."""
+        wrapper on p_sample never applies here.  keep_mask / keep_mode: region-held sampling as in sample(); the
+        posterior's timestep governs what a renoised position is drawn at."""
         cond_emb = self._cond(condition_token, condition_embed)
+        if keep_mask is not None and int(self.num_timesteps * filter_ratio) != 0:
+            raise ValueError("keep_mask samples the free positions from [MASK]: filter_ratio must resolve to step 0")
         assert int(self.num_timesteps * filter_ratio) == 0     # the reference asserts start_step == 0 (:787)
         lst = list(range(self.num_timesteps - 1, -1, -1 - skip_step))
         if lst[-1] != 0:
             lst.append(0)
+        hold = x = None
+        if keep_mask is not None:
+            hold, x, caption_ids = self._hold_start(keep_mask, keep_mode, content_token, cond_emb.shape[0], noise_fn,
+                                                    caption_ids, seed)
         keep, self.repeat_rate = self.repeat_rate, None
         try:
             return self._reverse(cond_emb, [(s_, s_ - skip_step if s_ > skip_step else s_) for s_ in lst], noise_fn,
-                                 return_logits, caption_ids=caption_ids, seed=seed)
+                                 return_logits, start_tokens=x, caption_ids=caption_ids, seed=seed, hold=hold)
         finally:
             self.repeat_rate = keep

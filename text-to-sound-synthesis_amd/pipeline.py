@@ -44,6 +44,62 @@ def load_vocoder(ckpt_vocoder, eval_mode=True):
 
 
 VOCODER_RATE = 22050          # the rate the vocoder generates at
+GRID_ROWS, GRID_COLS = 5, 53  # the token grid of one clip; content_token is time-major: position 5 column + row
+COLUMN_SAMPLES = 4096         # a column covers 16 mel frames = 4096 samples at 22 050 Hz (217 088 / 53)
+CLIP_SAMPLES = GRID_COLS * COLUMN_SAMPLES
+
+
+def _seconds_to_samples(t):
+    """seconds -> samples at 22 050 Hz; a value within 1e-6 of a whole sample IS that sample (a column edge spelled as
+    4096 c / 22050 must not fall to either side of it by the rounding of the division)"""
+    s = float(t) * VOCODER_RATE
+    return float(round(s)) if abs(s - round(s)) < 1e-6 else s
+
+
+def spans_to_keep_mask(spans, batch, device="cpu"):
+    """The keep mask of DALLE.inpaint_content from the time spans to REGENERATE.  spans: a list of (t0, t1) in seconds
+    shared by the `batch` clips, or a list of `batch` such lists, one per clip.  Column c (all five rows of it) is regenerated
+    iff [4096 c, 4096 (c + 1)) intersects a half-open span [t0, t1) in samples at 22 050 Hz.  Returns bool[batch, 265], True =
+    held, in content_token's time-major order.  A span outside [0, 217088 / 22050] or with t1 <= t0 raises ValueError."""
+    is_seq = lambda x: isinstance(x, (list, tuple))
+    spans = list(spans)
+    per_clip = len(spans) > 0 and all(is_seq(s) and (len(s) == 0 or is_seq(s[0])) for s in spans)
+    if per_clip and len(spans) != batch:
+        raise ValueError("per-clip spans: %d lists for a batch of %d" % (len(spans), batch))
+    keep = torch.ones(batch, GRID_COLS, dtype=torch.bool)
+    for b in range(batch):
+        for span in (spans[b] if per_clip else spans):
+            if not is_seq(span) or len(span) != 2:
+                raise ValueError("a span is (t0, t1) in seconds, got %r" % (span,))
+            s0, s1 = _seconds_to_samples(span[0]), _seconds_to_samples(span[1])
+            if not (0.0 <= s0 and s1 <= CLIP_SAMPLES):
+                raise ValueError("span %r is outside the clip [0, %d / %d s]" % (span, CLIP_SAMPLES, VOCODER_RATE))
+            if not s1 > s0:
+                raise ValueError("span %r is empty: t1 must be greater than t0" % (span,))
+            for c in range(GRID_COLS):
+                if s0 < COLUMN_SAMPLES * (c + 1) and s1 > COLUMN_SAMPLES * c:
+                    keep[b, c] = False
+    return keep[:, :, None].expand(batch, GRID_COLS, GRID_ROWS).reshape(batch, GRID_COLS * GRID_ROWS).to(device)
+
+
+def continuation_columns(keep_seconds):
+    """columns of a recording's tail that continue_audio carries over: ceil(keep_seconds 22050 / 4096), in 1 .. 52"""
+    import math
+    n = int(math.ceil(_seconds_to_samples(keep_seconds) / COLUMN_SAMPLES))
+    if not 0 < n < GRID_COLS:
+        raise ValueError("keep_seconds must cover 1 .. %d columns of %d samples, got %r" % (GRID_COLS - 1, COLUMN_SAMPLES, keep_seconds))
+    return n
+
+
+def continuation_tokens(tokens, n_cols):
+    """tokens i64[B, 265] of a recording -> (tokens of the next clip, keep mask): the last n_cols columns become the first
+    ones (a shift by 5 (53 - n_cols) tokens), held; the rest (zeros here) is to be generated."""
+    n = GRID_ROWS * n_cols
+    out = torch.zeros_like(tokens)
+    out[:, :n] = tokens[:, tokens.shape[1] - n:]
+    keep = torch.zeros(tokens.shape, dtype=torch.bool, device=tokens.device)
+    keep[:, :n] = True
+    return out, keep
 
 
 class Diffsound:
@@ -118,15 +174,8 @@ class Diffsound:
         t = int(T * filter_ratio) - 1 and denoised from there under `text` (a list of B captions, token ids or embeddings, as in
         generate_sample_with_condition) -> decode -> vocoder.  Returns (mel01 f32[B,80,848], wave f32[B,1,217088] or None,
         tokens); with save_root also writes `{i:06d}.npy` and, with a vocoder, `{i:06d}.wav` like the other drivers."""
-        import numpy as np
-        if isinstance(text, (list, tuple, str)):
-            batch = {"text": [text] if isinstance(text, str) else list(text)}
-        elif text.dtype == torch.long:
-            batch = {"condition_token": text}
-        else:
-            batch = {"condition_embed_token": text}
         model = self.model
-        cond = model.prepare_condition(batch)
+        cond = model.prepare_condition(self._caption_batch(text))
         content = model.prepare_content({"audio": audio, "audio_rate": audio_rate})
         tr = model.transformer
         keep = tr.truncation_r, tr.truncation_k
@@ -137,9 +186,15 @@ class Diffsound:
                             filter_ratio=filter_ratio, print_log=False)
         finally:
             tr.truncation_r, tr.truncation_k = keep
-        tokens = out["content_token"]
-        mel = model.decode_to_img(tokens, content["content_quant"].shape)
+        return self._render(out["content_token"], content["content_quant"].shape, save_root)
+
+    def _render(self, tokens, zshape, save_root=None, sample_rate=None):
+        """tokens -> decode -> vocoder (-> sample_rate): the tail the audio-in drivers share.  Returns (mel01, wave or None,
+        tokens); with save_root also writes `{i:06d}.npy` and, with a vocoder, `{i:06d}.wav`."""
+        import numpy as np
+        mel = self.model.decode_to_img(tokens, zshape)
         wave = None if self.vocoder is None else self.vocoder(mel[:, 0], scale=0.5, shift=0.5)
+        wave = self._at_rate(wave, sample_rate)
         mel01 = (mel[:, 0] + 1) / 2
         if save_root is not None:
             os.makedirs(save_root, exist_ok=True)
@@ -148,8 +203,65 @@ class Diffsound:
                 path = os.path.join(save_root, str(i).zfill(6))
                 np.save(path + ".npy", m_[i])
                 if w_ is not None:
-                    write_wav_pcm24(path + ".wav", w_[i], 22050)
+                    write_wav_pcm24(path + ".wav", w_[i], VOCODER_RATE if sample_rate is None else int(sample_rate))
         return mel01, wave, tokens
+
+    @staticmethod
+    def _caption_batch(text):
+        if isinstance(text, (list, tuple, str)):
+            return {"text": [text] if isinstance(text, str) else list(text)}
+        return {"condition_token": text} if text.dtype == torch.long else {"condition_embed_token": text}
+
+    def _inpaint_tokens(self, tokens, keep, text, keep_mode, truncation_rate, caption_ids, seed):
+        """DALLE.inpaint_content at this call's truncation rate (the facade installs a rate once and keeps it: set and
+        restored around the call, like generate_sample_from_audio does)."""
+        batch = dict(self._caption_batch(text), content_token=tokens)
+        if caption_ids is not None:
+            batch["caption_ids"] = caption_ids
+        if seed is not None:
+            batch["seed"] = seed
+        model, tr = self.model, self.model.transformer
+        saved = tr.truncation_r, tr.truncation_k, tr.repeat_rate, model.truncation_forward
+        tr.truncation_r, tr.truncation_k, model.truncation_forward = float(truncation_rate), None, True
+        try:
+            out = model.inpaint_content(batch=batch, keep_mask=keep, keep_mode=keep_mode,
+                                        sample_type="top" + str(truncation_rate) + "r")
+        finally:
+            tr.truncation_r, tr.truncation_k, tr.repeat_rate, model.truncation_forward = saved
+        return out["content_token"]
+
+    @torch.no_grad()
+    def inpaint_audio(self, audio, text, spans, keep_mode="clamp", truncation_rate=0.85, save_root=None, audio_rate=None,
+                      caption_ids=None, seed=None, sample_rate=None):
+        """Regenerate time spans of given recordings under a caption and keep the rest: audio / audio_rate / text as in
+        generate_sample_from_audio; spans = the (t0, t1) seconds to regenerate, shared or one list per clip
+        (spans_to_keep_mask: whole grid columns of 4096 samples at 22 050 Hz).  The recording is encoded to its 5 x 53 tokens,
+        the tokens outside the spans are held through the whole reverse chain (keep_mode "clamp": clean; "renoise": following
+        the forward process, per-caption in-kernel noise) and the spans are generated from [MASK] with them as context.
+        caption_ids / seed / sample_rate as in generate_sample_with_condition.  Returns (mel01, wave or None, tokens) and
+        writes the files generate_sample_from_audio writes.
+
+        What is kept is the TOKENS: exact.  The returned audio is the codec's and the vocoder's rendering everywhere -- the
+        held region is not the input's samples (the decoder's lowest level attends over all 265 positions), and the original
+        mel or audio is not pasted back."""
+        content = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})
+        known = content["content_token"]
+        keep = spans_to_keep_mask(spans, known.shape[0], known.device)
+        tokens = self._inpaint_tokens(known, keep, text, keep_mode, truncation_rate, caption_ids, seed)
+        return self._render(tokens, content["content_quant"].shape, save_root, sample_rate)
+
+    @torch.no_grad()
+    def continue_audio(self, audio, text, keep_seconds, keep_mode="clamp", truncation_rate=0.85, save_root=None,
+                       audio_rate=None, caption_ids=None, seed=None, sample_rate=None):
+        """Generate the clip that follows given recordings: the last ceil(keep_seconds 22050 / 4096) token columns of the
+        recording become the first columns of a new 10-s clip (a shift by 5 (53 - n) tokens), held, and the remaining columns
+        are generated under `text`.  Arguments and return as inpaint_audio.  The new clip's head is the codec's rendering of
+        the kept tail (exact tokens, not the input's samples); stitching the two waveforms across the seam is left to the
+        caller."""
+        content = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})
+        known, keep = continuation_tokens(content["content_token"], continuation_columns(keep_seconds))
+        tokens = self._inpaint_tokens(known, keep, text, keep_mode, truncation_rate, caption_ids, seed)
+        return self._render(tokens, content["content_quant"].shape, save_root, sample_rate)
 
     @torch.no_grad()
     def inference_generate_sample_with_condition(self, text, truncation_rate, save_root, batch_size, fast=False):
