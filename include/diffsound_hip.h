@@ -229,6 +229,23 @@ int ds_sample_tail_hold_rng(const float* logits, const int64_t* xt, const int64_
                             int K, int T, int initial, float trunc_r, int trunc_k, const unsigned char* keep,
                             const int64_t* known, int mode, ds_stream_t stream);
 
+/* Classifier-free guidance in the tail.  Two logit rows per grid position: logits_c from the denoiser run with the caption,
+ * logits_u from the run with the null condition (both [B*L][K], same x_t and t).  With lc / lu = predict_start of each row
+ * (float64 log-softmax, rounded to f32, clamped to [-70, 0]):
+ *     g = lu + scale (lc - lu),   g <- g - logsumexp(g)      in float64, max-shifted,
+ * rounded to f32 and clamped to [-70, 0] ([MASK] row -70) is the log_pred that truncation, posterior and Gumbel-argmax
+ * consume unchanged; dbg_log_pred dumps it.  scale 0: the null prediction, 1: the captioned one.  keep / known / mode as in
+ * ds_sample_tail_hold (a held column leaves before any of this); keep == NULL: unheld.  Rejected (-1, nothing launched):
+ * a null logits_u, a non-finite scale, and what ds_sample_tail_hold rejects. */
+int ds_sample_tail_guided(const float* logits_c, const float* logits_u, const int64_t* xt, const int64_t* t, const float* u,
+                          const float* sched, int64_t* out_tokens, float* dbg_log_pred, float* dbg_trunc, float* dbg_post,
+                          int B, int L, int K, int T, int initial, float trunc_r, int trunc_k, float scale,
+                          const unsigned char* keep, const int64_t* known, int mode, ds_stream_t stream);
+int ds_sample_tail_guided_rng(const float* logits_c, const float* logits_u, const int64_t* xt, const int64_t* t,
+                              const int64_t* gids, unsigned long long seed, int call, const float* sched,
+                              int64_t* out_tokens, int B, int L, int K, int T, int initial, float trunc_r, int trunc_k,
+                              float scale, const unsigned char* keep, const int64_t* known, int mode, ds_stream_t stream);
+
 /* forward terms of the training loss (DiffusionTransformer._train_loss, diffusion_transformer.py:408-476), one value
  * per grid position [B][L]: kl = KL(true posterior || model posterior) (:439-440), nll = the t == 0 decoder term
  * (:446), kl_aux = KL(x_0 || p(x_0|x_t)) over the K classes (:462); logits [B*L][K] of the network at (x_t, t),
@@ -452,6 +469,29 @@ int ds_denoiser_sample_hold_rng(const ds_denoiser* h, int64_t* tokens, int64_t* 
                                 int n_calls, const float* kv, const int64_t* gids, unsigned long long seed, int call0,
                                 int B, int initial, float trunc_r, int trunc_k, const unsigned char* keep,
                                 const int64_t* known, int mode, void* workspace, ds_stream_t stream);
+
+/* Guided forms (see ds_sample_tail_guided) of ds_denoiser_step_hold, ds_denoiser_step_hold_rng and
+ * ds_denoiser_sample_hold_rng: one forward at batch 2B and the guided tail on the two halves of its logits.
+ *   kv         ds_denoiser_cond_kv at batch 2B of the B caption embeddings followed by the B null embeddings
+ *   workspace  ds_denoiser_workspace_bytes(h, 2B)
+ *   tokens2    i64[2B][seq_len] scratch of the caller: receives the duplicated tokens of every step (on the call's stream)
+ *   t, t_post  2B entries, the caller's B repeated (the posterior reads the first B); for the chain t_steps is
+ *              i64[n_calls][2][2B]
+ * tokens_in / tokens_out / tokens / tokens_tmp / keep / known stay [B][seq_len]; keep == NULL: unheld.  Argument checks
+ * (a non-finite scale, the mode / keep / known rules) come before anything is enqueued. */
+int ds_denoiser_step_guided(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const int64_t* t_post,
+                            const float* kv, const float* u, int B, int initial, float trunc_r, int trunc_k, float scale,
+                            const unsigned char* keep, const int64_t* known, int mode, int64_t* tokens2, void* workspace,
+                            int64_t* tokens_out, ds_stream_t stream);
+int ds_denoiser_step_guided_rng(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const int64_t* t_post,
+                                const float* kv, const int64_t* gids, unsigned long long seed, int call, int B,
+                                int initial, float trunc_r, int trunc_k, float scale, const unsigned char* keep,
+                                const int64_t* known, int mode, int64_t* tokens2, void* workspace, int64_t* tokens_out,
+                                ds_stream_t stream);
+int ds_denoiser_sample_guided_rng(const ds_denoiser* h, int64_t* tokens, int64_t* tokens_tmp, const int64_t* t_steps,
+                                  int n_calls, const float* kv, const int64_t* gids, unsigned long long seed, int call0,
+                                  int B, int initial, float trunc_r, int trunc_k, float scale, const unsigned char* keep,
+                                  const int64_t* known, int mode, int64_t* tokens2, void* workspace, ds_stream_t stream);
 
 /* per-launch HIP-event timing of the denoiser's GEMM launches (measurement only, bench.py) */
 int ds_profile_enable(int on);

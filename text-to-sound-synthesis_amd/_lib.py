@@ -137,6 +137,16 @@ _PROTOS = {
                                             C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "ds_denoiser_sample_hold_rng": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_uint64, C.c_int, C.c_int, C.c_int,
                                               _f, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),
+    "ds_sample_tail_guided": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f, C.c_int, _f, _vp, _vp, C.c_int, _vp]),
+    "ds_sample_tail_guided_rng": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.c_int, _f, C.c_int, _f, _vp, _vp, C.c_int, _vp]),
+    "ds_denoiser_step_guided": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _f, C.c_int, _f, _vp, _vp, C.c_int,
+                                          _vp, _vp, _vp, _vp]),
+    "ds_denoiser_step_guided_rng": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, C.c_int, C.c_int, C.c_int, _f,
+                                              C.c_int, _f, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "ds_denoiser_sample_guided_rng": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_uint64, C.c_int, C.c_int, C.c_int,
+                                                _f, C.c_int, _f, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "ds_profile_enable": (C.c_int, [C.c_int]),
     "ds_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i64)]),
     "ds_profile_collect_n": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i64), C.c_int]),

@@ -535,6 +535,103 @@ extern "C" int ds_denoiser_sample_hold_rng(const ds_denoiser* h, int64_t* tokens
     return 0;
 }
 
+// ---- classifier-free guidance (sampler.hip SampleGuide): ONE forward at batch 2B -- rows 0 .. B-1 under the captions, rows
+// B .. 2B-1 under the null condition, on the same tokens and timesteps -- and the guided tail on the two halves of the logits.
+// kv: ds_denoiser_cond_kv at batch 2B of the caption embeddings followed by the null embeddings; workspace:
+// ds_denoiser_workspace_bytes(h, 2B); tokens2 i64[2B][seq_len]: caller's scratch, receives the duplicated tokens of each
+// step (two async copies on the call's stream); t / t_post: 2B entries, the caller's B repeated (the posterior reads the
+// first B).  keep == NULL: unheld.
+int ds_sample_tail_rows_guided(const char* who, const float* logits, const float* logits_u, int logits_rows, const int64_t* xt,
+                               const int64_t* t, const float* u, const float* sched, int64_t* out_tokens, float* dbg_log_pred,
+                               float* dbg_trunc, float* dbg_post, int B, int L, int K, int T, int initial, float trunc_r,
+                               int trunc_k, float scale, ds_stream_t stream, const int64_t* gids, unsigned long long seed,
+                               int call, const unsigned char* keep, const int64_t* known, int mode);   // sampler.hip
+
+static int guided_check(const char* who, bool pointers, float scale, const void* gids, const unsigned char* keep,
+                        const int64_t* known, int mode) {
+    const char* msg = !pointers                ? "bad arguments"
+                      : !(scale - scale == 0.f) ? "the guidance scale must be finite"
+                      : !(mode == 0 || mode == 1) ? "mode is 0 (clamp) or 1 (renoise)"
+                      : (mode == 1 && !gids)    ? "renoise draws from the caption's Philox stream: not with caller uniforms"
+                      : (keep && !known)        ? "keep without known"
+                                                : nullptr;
+    if (!msg) return 0;
+    ds_set_error("%s: %s", who, msg);
+    return -1;
+}
+
+static int guided_step_impl(const char* who, const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t,
+                            const int64_t* t_post, const float* kv, const float* u, const int64_t* gids,
+                            unsigned long long seed, int call, int B, int initial, float trunc_r, int trunc_k, float scale,
+                            const unsigned char* keep, const int64_t* known, int mode, int64_t* tokens2, void* workspace,
+                            int64_t* tokens_out, ds_stream_t stream, bool zero_kv_pad = true) {
+    const size_t tok_bytes = (size_t)B * h->d.seq_len * sizeof(int64_t);
+    for (int half = 0; half < 2; ++half) {
+        hipError_t e = hipMemcpyAsync(tokens2 + (size_t)half * B * h->d.seq_len, tokens_in, tok_bytes, hipMemcpyDeviceToDevice,
+                                      (hipStream_t)stream);
+        if (e != hipSuccess) {
+            ds_set_error("%s: hipMemcpyAsync: %s", who, hipGetErrorString(e));
+            return -2;
+        }
+    }
+    Carve w;
+    const int Lp = rows_per_sample(h, 2 * B);
+    carve(h, 2 * B, workspace, &w, Lp);
+    TRY(forward_impl(h, tokens2, t, kv, 2 * B, w, w.logits, 0, (hipStream_t)stream, Lp, zero_kv_pad));
+    return ds_sample_tail_rows_guided(who, w.logits, w.logits + (size_t)B * Lp * h->d.n_codes, Lp, tokens_in,
+                                      t_post ? t_post : t, u, h->d.sched, tokens_out, nullptr, nullptr, nullptr, B,
+                                      h->d.seq_len, h->d.n_codes, h->d.n_steps, initial, trunc_r, trunc_k, scale, stream, gids,
+                                      seed, call, keep, known, mode);
+}
+
+extern "C" int ds_denoiser_step_guided(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t,
+                                       const int64_t* t_post, const float* kv, const float* u, int B, int initial,
+                                       float trunc_r, int trunc_k, float scale, const unsigned char* keep,
+                                       const int64_t* known, int mode, int64_t* tokens2, void* workspace,
+                                       int64_t* tokens_out, ds_stream_t stream) {
+    TRY(guided_check(__func__, h && tokens_in && t && kv && u && tokens2 && workspace && tokens_out && B > 0, scale, nullptr,
+                     keep, known, mode));
+    return guided_step_impl(__func__, h, tokens_in, t, t_post, kv, u, nullptr, 0ull, 0, B, initial, trunc_r, trunc_k, scale,
+                            keep, known, mode, tokens2, workspace, tokens_out, stream);
+}
+
+extern "C" int ds_denoiser_step_guided_rng(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t,
+                                           const int64_t* t_post, const float* kv, const int64_t* gids,
+                                           unsigned long long seed, int call, int B, int initial, float trunc_r, int trunc_k,
+                                           float scale, const unsigned char* keep, const int64_t* known, int mode,
+                                           int64_t* tokens2, void* workspace, int64_t* tokens_out, ds_stream_t stream) {
+    TRY(guided_check(__func__, h && tokens_in && t && kv && gids && tokens2 && workspace && tokens_out && B > 0, scale, gids,
+                     keep, known, mode));
+    return guided_step_impl(__func__, h, tokens_in, t, t_post, kv, nullptr, gids, seed, call, B, initial, trunc_r, trunc_k,
+                            scale, keep, known, mode, tokens2, workspace, tokens_out, stream);
+}
+
+// the whole guided chain: ds_denoiser_sample_hold_rng's ping-pong and call0 rules; t_steps is i64[n_calls][2][2B]
+extern "C" int ds_denoiser_sample_guided_rng(const ds_denoiser* h, int64_t* tokens, int64_t* tokens_tmp,
+                                             const int64_t* t_steps, int n_calls, const float* kv, const int64_t* gids,
+                                             unsigned long long seed, int call0, int B, int initial, float trunc_r,
+                                             int trunc_k, float scale, const unsigned char* keep, const int64_t* known,
+                                             int mode, int64_t* tokens2, void* workspace, ds_stream_t stream) {
+    TRY(guided_check(__func__, h && tokens && tokens_tmp && t_steps && kv && gids && tokens2 && workspace && B > 0 &&
+                                   n_calls >= 0, scale, gids, keep, known, mode));
+    int64_t *cur = tokens, *nxt = tokens_tmp;
+    for (int k = 0; k < n_calls; ++k) {
+        const int64_t* tk = t_steps + (size_t)k * 4 * B;
+        TRY(guided_step_impl(__func__, h, cur, tk, tk + 2 * B, kv, nullptr, gids, seed, call0 + k, B, initial && k == 0,
+                             trunc_r, trunc_k, scale, keep, known, mode, tokens2, workspace, nxt, stream, k == 0));
+        int64_t* sw = cur; cur = nxt; nxt = sw;
+    }
+    if (cur != tokens) {
+        hipError_t e = hipMemcpyAsync(tokens, cur, (size_t)B * h->d.seq_len * sizeof(int64_t), hipMemcpyDeviceToDevice,
+                                      (hipStream_t)stream);
+        if (e != hipSuccess) {
+            ds_set_error("ds_denoiser_sample_guided_rng: hipMemcpyAsync: %s", hipGetErrorString(e));
+            return -2;
+        }
+    }
+    return 0;
+}
+
 extern "C" int ds_denoiser_step(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const float* kv,
                                 const float* u, int B, int initial, float trunc_r, void* workspace,
                                 int64_t* tokens_out, ds_stream_t stream) {

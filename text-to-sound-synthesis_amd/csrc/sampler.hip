@@ -114,8 +114,50 @@ __device__ __forceinline__ int ds_q_sample_column(int x, int tt, const float* __
                                                   const float* up, int L, int pos, unsigned gid, unsigned seed_lo,
                                                   unsigned seed_hi, int call);
 
-template <int NPL, bool RNG, bool HOLD>
-__device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const SampleRng& g, const SampleHold& h) {
+// GUIDED form (classifier-free guidance: the *_guided entries).  Every column has two logit rows: p.logits from the denoiser
+// run with the caption (zc), logits_u -- same row layout, same lrows -- from the run with the null condition (zu), both on
+// the same x_t and t.  After predict_start of each row (lc, lu: the f64 log-softmax rounded to f32 and clamped, as above)
+//   g = lu + scale (lc - lu),  g <- g - logsumexp(g)   in float64 (max-shifted),
+// rounded to f32 and clamped to [-70, 0], is the log_pred that truncation, posterior and Gumbel-argmax consume unchanged
+// (VQ-Diffusion's improved sampler on this kernel's f64 conventions).  scale 0: the null prediction, 1: the captioned one.
+// A separate kernel argument and ONE separate __global__ wrapper per (K, noise source), which takes SampleHold with
+// keep == nullptr meaning unheld (one wave-uniform pointer test): the unguided kernels keep their arguments and registers.
+struct SampleGuide {
+    const float* logits_u;       // [B * lrows][K]
+    float scale;
+};
+
+__device__ __forceinline__ double wmaxd(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+
+// predict_start of one column (diffusion_transformer.py:285-289) into float lp[NPL]: float64 log-softmax over the K real classes
+// of the row at lg_, rounded to f32 and clamped to [-70, 0]; the lane owns classes 64 j + lane.  A macro, not a function: the
+// guided kernel runs it on both rows, and through a function taking lp by reference the unguided kernels' device code changed
+// (register allocation and schedule); expanded in place it is the code they always had, instruction for instruction.
+#define DS_PREDICT_START_ROW(lg_, lp_)                                                   \
+    {                                                                                    \
+        float v[NPL];                                                                    \
+        const float* lg = (lg_);                                                         \
+        _Pragma("unroll") for (int j = 0; j < NPL; ++j) v[j] = lg[j * 64 + lane];        \
+        float mx = v[0];                                                                 \
+        _Pragma("unroll") for (int j = 1; j < NPL; ++j) mx = fmaxf(mx, v[j]);            \
+        mx = wmaxf(mx);                                                                  \
+        double se = 0.0;                                                                 \
+        _Pragma("unroll") for (int j = 0; j < NPL; ++j) se += exp((double)v[j] - (double)mx); \
+        se = wsumd(se);                                                                  \
+        const double lse64 = log(se);                                                    \
+        _Pragma("unroll") for (int j = 0; j < NPL; ++j) {                                \
+            float x = (float)(((double)v[j] - (double)mx) - lse64);                      \
+            lp_[j] = fminf(fmaxf(x, -70.f), 0.f);                                        \
+        }                                                                                \
+    }
+
+template <int NPL, bool RNG, bool HOLD, bool GUIDED = false>
+__device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const SampleRng& g, const SampleHold& h,
+                                                    const SampleGuide& gd = SampleGuide{nullptr, 1.f}) {
     constexpr int K = NPL * 64;
     __shared__ float s_lp[4][K];
     __shared__ __attribute__((aligned(16))) float s_pr[4][K];
@@ -126,7 +168,7 @@ __device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const
     if (!live) col = p.B * p.L - 1;
     const int b = col / p.L, pos = col - b * p.L;
     if constexpr (HOLD) {
-        if (h.keep[col]) {       // wave-uniform: the whole wave leaves (no block-wide barrier below in this form)
+        if ((!GUIDED || h.keep) && h.keep[col]) {       // wave-uniform: the whole wave leaves (no block-wide barrier below in this form)
             int tok = (int)h.known[col];
             if constexpr (RNG) {
                 const int tp = (int)p.t[b];
@@ -140,24 +182,28 @@ __device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const
     }
 
     // ---- predict_start: float64 log-softmax over the K real classes ----
-    float v[NPL];
-    const float* lg = p.logits + ((size_t)b * p.lrows + pos) * K;
-#pragma unroll
-    for (int j = 0; j < NPL; ++j) v[j] = lg[j * 64 + lane];
-    float mx = v[0];
-#pragma unroll
-    for (int j = 1; j < NPL; ++j) mx = fmaxf(mx, v[j]);
-    mx = wmaxf(mx);
-    double se = 0.0;
-#pragma unroll
-    for (int j = 0; j < NPL; ++j) se += exp((double)v[j] - (double)mx);
-    se = wsumd(se);
-    const double lse64 = log(se);
     float lp[NPL];
+    DS_PREDICT_START_ROW(p.logits + ((size_t)b * p.lrows + pos) * K, lp)
+    if constexpr (GUIDED) {
+        // ---- guidance: lc (in lp), then lu, then the f64 mix and its renormalisation; lp becomes the guided log_pred ----
+        double gv[NPL];
+        {
+            float lu[NPL];
+            DS_PREDICT_START_ROW(gd.logits_u + ((size_t)b * p.lrows + pos) * K, lu)
+            const double s = (double)gd.scale;
 #pragma unroll
-    for (int j = 0; j < NPL; ++j) {
-        float x = (float)(((double)v[j] - (double)mx) - lse64);
-        lp[j] = fminf(fmaxf(x, -70.f), 0.f);
+            for (int j = 0; j < NPL; ++j) gv[j] = (double)lu[j] + s * ((double)lp[j] - (double)lu[j]);
+        }
+        double gm = gv[0];
+#pragma unroll
+        for (int j = 1; j < NPL; ++j) gm = fmax(gm, gv[j]);
+        gm = wmaxd(gm);
+        double gs = 0.0;
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) gs += exp(gv[j] - gm);
+        const double glse = log(wsumd(gs));
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) lp[j] = fminf(fmaxf((float)((gv[j] - gm) - glse), -70.f), 0.f);
     }
     const size_t dbg_base = (size_t)b * (K + 1) * p.L + pos;
     if (p.dbg_log_pred && live) {
@@ -372,6 +418,14 @@ __global__ __launch_bounds__(256) void ds_sample_tail_kernel(const SampleParams 
 template <int NPL, bool RNG>
 __global__ __launch_bounds__(256) void ds_sample_tail_hold_kernel(const SampleParams p, const SampleRng g, const SampleHold h) {
     ds_sample_tail_body<NPL, RNG, true>(p, g, h);
+}
+
+#undef DS_PREDICT_START_ROW
+
+template <int NPL, bool RNG>
+__global__ __launch_bounds__(256) void ds_sample_tail_guided_kernel(const SampleParams p, const SampleRng g, const SampleHold h,
+                                                                    const SampleGuide gd) {
+    ds_sample_tail_body<NPL, RNG, true, true>(p, g, h, gd);
 }
 
 // ---- training-loss terms (DiffusionTransformer._train_loss, diffusion_transformer.py:408-476), forward only ----
@@ -750,6 +804,67 @@ int ds_sample_tail_rows_hold(const float* logits, int logits_rows, const int64_t
     else hipLaunchKernelGGL((ds_sample_tail_kernel<8, true>), grid, dim3(256), 0, stream, p, g);
     DS_CHECK_LAUNCH();
     return 0;
+}
+
+// the guided tails (see SampleGuide): logits_u has the rows of `logits` (same logits_rows); keep == nullptr: unheld.  `who`:
+// the public entry the messages name.
+int ds_sample_tail_rows_guided(const char* who, const float* logits, const float* logits_u, int logits_rows, const int64_t* xt,
+                               const int64_t* t, const float* u, const float* sched, int64_t* out_tokens, float* dbg_log_pred,
+                               float* dbg_trunc, float* dbg_post, int B, int L, int K, int T, int initial, float trunc_r,
+                               int trunc_k, float scale, ds_stream_t stream_, const int64_t* gids, unsigned long long seed,
+                               int call, const unsigned char* keep, const int64_t* known, int mode) {
+    hipStream_t stream = (hipStream_t)stream_;
+#define DS_GUIDED_ARG(cond, msg)                   \
+    do {                                           \
+        if (!(cond)) {                             \
+            ds_set_error("%s: %s", who, msg);      \
+            return -1;                             \
+        }                                          \
+    } while (0)
+    DS_GUIDED_ARG(logits && xt && t && (u || gids) && sched && out_tokens && B > 0 && L > 0 && T > 0, "null pointer");
+    DS_GUIDED_ARG(logits_u, "null logits_u (the null-condition logits)");
+    DS_GUIDED_ARG(scale - scale == 0.f, "the guidance scale must be finite");
+    DS_GUIDED_ARG(K == 256 || K == 512, "codebook size must be 256 or 512");
+    DS_GUIDED_ARG(trunc_k >= 0 && !(trunc_k > 0 && trunc_r >= 0.f), "top-k and top-r truncation are exclusive");
+    DS_GUIDED_ARG(logits_rows >= L && L < 65536, "logits rows per sample");
+    DS_GUIDED_ARG(mode == 0 || mode == 1, "mode is 0 (clamp) or 1 (renoise)");
+    DS_GUIDED_ARG(!(mode == 1 && u), "renoise draws from the caption's Philox stream: not with caller uniforms");
+    DS_GUIDED_ARG(!keep || known, "keep without known");
+#undef DS_GUIDED_ARG
+    SampleParams p{logits, xt, t, u, sched, out_tokens, dbg_log_pred, dbg_trunc, dbg_post, B, L, T, initial, trunc_r,
+                   trunc_k, logits_rows};
+    const SampleRng g{gids, (unsigned)seed, (unsigned)(seed >> 32), call};
+    const SampleHold h{keep, known, mode};
+    const SampleGuide gd{logits_u, scale};
+    const dim3 grid((B * L + 3) / 4);
+    if (K == 256 && u) hipLaunchKernelGGL((ds_sample_tail_guided_kernel<4, false>), grid, dim3(256), 0, stream, p, g, h, gd);
+    else if (K == 256) hipLaunchKernelGGL((ds_sample_tail_guided_kernel<4, true>), grid, dim3(256), 0, stream, p, g, h, gd);
+    else if (u) hipLaunchKernelGGL((ds_sample_tail_guided_kernel<8, false>), grid, dim3(256), 0, stream, p, g, h, gd);
+    else hipLaunchKernelGGL((ds_sample_tail_guided_kernel<8, true>), grid, dim3(256), 0, stream, p, g, h, gd);
+    DS_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int ds_sample_tail_guided(const float* logits_c, const float* logits_u, const int64_t* xt, const int64_t* t,
+                                     const float* u, const float* sched, int64_t* out_tokens, float* dbg_log_pred,
+                                     float* dbg_trunc, float* dbg_post, int B, int L, int K, int T, int initial,
+                                     float trunc_r, int trunc_k, float scale, const unsigned char* keep,
+                                     const int64_t* known, int mode, ds_stream_t stream) {
+    DS_CHECK_ARG(u, "null pointer");
+    return ds_sample_tail_rows_guided(__func__, logits_c, logits_u, L, xt, t, u, sched, out_tokens, dbg_log_pred, dbg_trunc,
+                                      dbg_post, B, L, K, T, initial, trunc_r, trunc_k, scale, stream, nullptr, 0ull, 0, keep,
+                                      known, mode);
+}
+
+extern "C" int ds_sample_tail_guided_rng(const float* logits_c, const float* logits_u, const int64_t* xt, const int64_t* t,
+                                         const int64_t* gids, unsigned long long seed, int call, const float* sched,
+                                         int64_t* out_tokens, int B, int L, int K, int T, int initial, float trunc_r,
+                                         int trunc_k, float scale, const unsigned char* keep, const int64_t* known, int mode,
+                                         ds_stream_t stream) {
+    DS_CHECK_ARG(gids, "null pointer");
+    return ds_sample_tail_rows_guided(__func__, logits_c, logits_u, L, xt, t, nullptr, sched, out_tokens, nullptr, nullptr,
+                                      nullptr, B, L, K, T, initial, trunc_r, trunc_k, scale, stream, gids, seed, call, keep,
+                                      known, mode);
 }
 
 int ds_sample_tail_rows(const float* logits, int logits_rows, const int64_t* xt, const int64_t* t, const float* u,

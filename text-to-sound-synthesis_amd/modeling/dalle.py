@@ -104,6 +104,46 @@ class DALLE(nn.Module):
                 "batch={'condition_embed_token': f32[B,77,512]} or {'condition_token': i64[B,77]}")
         return cond
 
+    @torch.no_grad()
+    def null_condition(self, negative=None, batch=None):
+        """The null condition of classifier-free guidance (DiffusionTransformer.sample: guidance_scale): the CLIP embedding
+        of the empty caption "" -- f32[77, 512], computed once per device and cached -- or of `negative`, a caption
+        (f32[77, 512]) or a list of B captions (f32[B, 77, 512]); through condition_codec + transformer.condition_emb.  A
+        model built without a text stage takes batch['null_condition_embed_token'] (f32[77, 512] or [B, 77, 512]) instead."""
+        tr = self.transformer
+        if self.condition_codec is None or tr.condition_emb is None:
+            emb = None if batch is None else batch.get("null_condition_embed_token")
+            if emb is None:
+                raise ValueError("classifier-free guidance needs a null condition: this model has no text stage "
+                                 "(condition_codec / condition_emb), so pass batch['null_condition_embed_token'] "
+                                 "f32[77,512] or [B,77,512]")
+            if negative is not None:
+                raise ValueError("negative_text needs the text stage (condition_codec + condition_emb) this model lacks")
+            return torch.as_tensor(emb).float().to(self.device)
+        if negative is None:
+            cache = self.__dict__.setdefault("_null_condition", {})
+            key = str(self.device)
+            if key not in cache:
+                cache[key] = self._embed_captions([""])[0]
+            return cache[key]
+        if isinstance(negative, str):
+            return self._embed_captions([negative])[0]
+        return self._embed_captions(list(negative))
+
+    def _embed_captions(self, captions):
+        tok = self.condition_codec.get_tokens(captions)["token"]
+        return self.transformer.condition_emb(tok.to(self.device)).float()
+
+    def _guidance(self, batch, guidance_scale, replicate):
+        """sample()'s guidance keywords: the null embedding from batch['negative_text'] (or the empty caption), replicated
+        with the captions.  guidance_scale None or exactly 1: no keywords, today's path."""
+        if guidance_scale is None or float(guidance_scale) == 1.0:
+            return {}
+        null = self.null_condition(batch.get("negative_text"), batch=batch)
+        if null.dim() == 3 and replicate != 1:
+            null = torch.cat([null for _ in range(replicate)], dim=0)
+        return {"guidance_scale": float(guidance_scale), "null_condition_embed": null}
+
     def _install_sample_type(self, sample_type):
         """The `sample_type` mini-language (:179-247) applied to the transformer; returns its comma-separated parts."""
         parts = sample_type.split(",")
@@ -128,7 +168,7 @@ class DALLE(nn.Module):
             torch.arange(replicate).repeat_interleave(ids.numel()) * int(batch.get("caption_id_stride", 1 << 24))
 
     @torch.no_grad()
-    def inpaint_content(self, *, batch, keep_mask, keep_mode="clamp", replicate=1, sample_type="top0.85r"):
+    def inpaint_content(self, *, batch, keep_mask, keep_mode="clamp", replicate=1, sample_type="top0.85r", guidance_scale=None):
         """Region-held generation (not in the reference, whose content_ratio slices the token vector and cannot run for any
         value but 1): the positions of `keep_mask` (bool[B, 265], True = held, time-major like content_token;
         pipeline.spans_to_keep_mask builds it from seconds) keep the tokens of the batch's content, the others are generated
@@ -136,7 +176,7 @@ class DALLE(nn.Module):
         prepare_condition ('text', 'condition_token' or 'condition_embed_token') and the content as in prepare_content
         ('image', or 'audio' with 'audio_rate') or already encoded ('content_token' i64[B, 265]); 'caption_ids' / 'seed' as in
         generate_content.  keep_mode "clamp" | "renoise": DiffusionTransformer.sample.  Every sample_type of generate_content
-        works.  Returns {'content': mel image [B r, 1, 80, 848], 'content_token'}.
+        works.  guidance_scale: classifier-free guidance as in generate_content.  Returns {'content': mel image [B r, 1, 80, 848], 'content_token'}.
 
         The held TOKENS of the result are exactly the input's.  The mel is the codec's rendering of the whole grid, held
         region included: not the input's samples (the decoder's lowest level attends over all 265 positions), and the
@@ -159,6 +199,7 @@ class DALLE(nn.Module):
         kw = dict(condition_token=condition.get("condition_token"), condition_mask=condition.get("condition_mask"),
                   condition_embed=condition.get("condition_embed_token"), content_token=tokens, filter_ratio=0,
                   return_logits=False, print_log=False, keep_mask=keep, keep_mode=keep_mode)
+        kw.update(self._guidance(batch, guidance_scale, replicate))
         if batch.get("caption_ids") is not None:
             kw["caption_ids"] = self._replicated_caption_ids(batch, replicate)
         if batch.get("seed") is not None:
@@ -174,7 +215,10 @@ class DALLE(nn.Module):
 
     @torch.no_grad()
     def generate_content(self, *, batch, condition=None, filter_ratio=0.5, temperature=1.0, content_ratio=0.0,
-                         replicate=1, return_att_weight=False, sample_type="top0.85r"):
+                         replicate=1, return_att_weight=False, sample_type="top0.85r", guidance_scale=None):
+        """guidance_scale (not in the reference): classifier-free guidance of every sampler step against the null condition
+        -- the empty caption, or batch['negative_text'] (a caption or a list of B) -- see DiffusionTransformer.sample and
+        null_condition; None or exactly 1 is the unguided path."""
         self.eval()
         condition = self.prepare_condition(batch=batch, condition=condition)
         if replicate != 1:
@@ -187,6 +231,7 @@ class DALLE(nn.Module):
                   condition_embed=condition.get("condition_embed_token"), content_token=None,
                   filter_ratio=filter_ratio, temperature=temperature, return_att_weight=return_att_weight,
                   return_logits=False, print_log=False, sample_type=sample_type)
+        kw.update(self._guidance(batch, guidance_scale, replicate))
         if batch.get("caption_ids") is not None:             # per-caption in-kernel noise (diffusion.py rng_mode)
             kw["caption_ids"] = self._replicated_caption_ids(batch, replicate)
         if batch.get("seed") is not None:

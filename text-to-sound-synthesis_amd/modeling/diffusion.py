@@ -159,10 +159,12 @@ class DiffusionTransformer(nn.Module):
         return torch.log(oh.clamp(min=1e-30))
 
     @torch.no_grad()
-    def p_sample_tokens(self, x_t, kv, t, u, initial, out=None, t_post=None, slot=0, hold=None):
+    def p_sample_tokens(self, x_t, kv, t, u, initial, out=None, t_post=None, slot=0, hold=None, guide=None):
         """x_t i64[B,L] -> x_{t-1} i64[B,L]; kv from transformer.condition_kv().  t_post: the posterior's timestep
         vector when it differs from the network's (sample_fast).  hold: (keep u8[B,L], known i64[B,L], mode) of the
-        region-held step (_hold_start); on caller uniforms only mode 0 (clamp) exists."""
+        region-held step (_hold_start); on caller uniforms only mode 0 (clamp) exists.  guide: (kv2, scale, tokens2) of
+        the guided step (_guide_start: the K/V of captions + null conditions at batch 2B, the guidance scale, an
+        i64[2B,L] scratch); kv is not read then."""
         tr = self.transformer
         sched = self._schedule_table()
         p = tr.packed(sched)
@@ -170,6 +172,15 @@ class DiffusionTransformer(nn.Module):
         if out is None:
             out = torch.empty_like(x_t)
         r, k = self._truncation()
+        if guide is not None:
+            kv2, scale, tokens2 = guide
+            t2, tp2 = t.repeat(2), None if t_post is None else t_post.repeat(2)     # named: alive until the launch is enqueued
+            keep, known, mode = hold if hold is not None else (None, None, 0)
+            _lib.check(_lib.lib().ds_denoiser_step_guided(
+                p["handle"], _lib.ptr(x_t), _lib.ptr(t2), _lib.ptr(tp2), _lib.ptr(kv2), _lib.ptr(u), B,
+                0 if hold is not None else int(initial), r, k, float(scale), _lib.ptr(keep), _lib.ptr(known), int(mode),
+                _lib.ptr(tokens2), _lib.ptr(tr.workspace(2 * B, sched, slot)), _lib.ptr(out), _lib.stream()))
+            return out
         if hold is not None:
             _lib.check(_lib.lib().ds_denoiser_step_hold(
                 p["handle"], _lib.ptr(x_t), _lib.ptr(t), _lib.ptr(t_post), _lib.ptr(kv), _lib.ptr(u), B, 0, r, k,
@@ -183,9 +194,9 @@ class DiffusionTransformer(nn.Module):
 
     @torch.no_grad()
     def p_sample_tokens_rng(self, x_t, kv, t, caption_ids, call, initial, out=None, t_post=None, slot=0, seed=None,
-                            hold=None):
-        """p_sample_tokens with the noise drawn in the kernel: Philox stream of (seed, caption_ids[b], call).  hold as in
-        p_sample_tokens, mode 1 (renoise) included."""
+                            hold=None, guide=None):
+        """p_sample_tokens with the noise drawn in the kernel: Philox stream of (seed, caption_ids[b], call).  hold and
+        guide as in p_sample_tokens, mode 1 (renoise) included."""
         tr = self.transformer
         sched = self._schedule_table()
         p = tr.packed(sched)
@@ -193,6 +204,16 @@ class DiffusionTransformer(nn.Module):
         if out is None:
             out = torch.empty_like(x_t)
         r, k = self._truncation()
+        if guide is not None:
+            kv2, scale, tokens2 = guide
+            t2, tp2 = t.repeat(2), None if t_post is None else t_post.repeat(2)
+            keep, known, mode = hold if hold is not None else (None, None, 0)
+            _lib.check(_lib.lib().ds_denoiser_step_guided_rng(
+                p["handle"], _lib.ptr(x_t), _lib.ptr(t2), _lib.ptr(tp2), _lib.ptr(kv2), _lib.ptr(caption_ids),
+                int(self.sample_seed if seed is None else seed), int(call), B, 0 if hold is not None else int(initial), r, k,
+                float(scale), _lib.ptr(keep), _lib.ptr(known), int(mode), _lib.ptr(tokens2),
+                _lib.ptr(tr.workspace(2 * B, sched, slot)), _lib.ptr(out), _lib.stream()))
+            return out
         if hold is not None:
             _lib.check(_lib.lib().ds_denoiser_step_hold_rng(
                 p["handle"], _lib.ptr(x_t), _lib.ptr(t), _lib.ptr(t_post), _lib.ptr(kv), _lib.ptr(caption_ids),
@@ -382,8 +403,39 @@ class DiffusionTransformer(nn.Module):
             x = torch.where(keep, xs, torch.full_like(known, K))
         return (keep.to(torch.uint8).contiguous(), known, mode), x, caption_ids
 
-    def _reverse(self, cond_emb, steps, noise_fn, return_logits, start_tokens=None, caption_ids=None, seed=None, hold=None):
-        """steps: list of (t, t_post) pairs, first one from the all-[MASK] state (or from start_tokens, already
+    def _guide(self, guidance_scale, null_condition_embed, cond_emb):
+        """Classifier-free guidance of sample() / sample_fast(): None (today's path, no null forward) for a scale of None
+        or exactly 1, else (null embeddings f32[B,77,512] on the model's device, scale).  null_condition_embed is
+        f32[77,512], broadcast over the batch, or f32[B,77,512] (DALLE.null_condition)."""
+        if guidance_scale is None or float(guidance_scale) == 1.0:
+            return None
+        scale = float(guidance_scale)
+        if scale != scale or scale in (float("inf"), float("-inf")):
+            raise ValueError("guidance_scale must be finite, got %r" % (guidance_scale,))
+        if null_condition_embed is None:
+            raise ValueError("guidance_scale = %g needs the null condition: pass null_condition_embed f32[77,512] or "
+                             "[B,77,512] (DALLE.null_condition())" % scale)
+        null = torch.as_tensor(null_condition_embed).float()
+        want = tuple(cond_emb.shape)
+        if null.dim() == 2:
+            null = null[None].expand(want[0], -1, -1)
+        if tuple(null.shape) != want:
+            raise ValueError("null_condition_embed must be %s or %s: got %s"
+                             % (want[1:], want, tuple(torch.as_tensor(null_condition_embed).shape)))
+        return null.to(self.device), scale
+
+    def _guide_start(self, guide, cond_emb, sched):
+        """(kv2, scale, tokens2) of the guided entries: the cross-attention K/V at batch 2B of the captions followed by the
+        null conditions, and the scratch that receives the duplicated tokens of every step."""
+        null, scale = guide
+        B = cond_emb.shape[0]
+        kv2 = self.transformer.condition_kv(torch.cat((cond_emb.float(), null), 0).contiguous(), sched)
+        return kv2, scale, torch.empty(2 * B, self.content_seq_len, device=self.device, dtype=torch.long)
+
+    def _reverse(self, cond_emb, steps, noise_fn, return_logits, start_tokens=None, caption_ids=None, seed=None, hold=None,
+                 guide=None):
+        """guide: (null embeddings, scale) of _guide -- every call then runs one forward at batch 2B and the guided tail.
+        steps: list of (t, t_post) pairs, first one from the all-[MASK] state (or from start_tokens, already
         diffused to the first t).  hold: (keep, known, mode) of _hold_start -- every call then runs the region-held
         kernels and start_tokens is the mixed start state.  The 'q' repeat sampler
         (dalle_spec.py:135-143: with probability `repeat_rate` a step is applied twice at the same t) draws from
@@ -406,11 +458,26 @@ class DiffusionTransformer(nn.Module):
             sched = self._schedule_table()
             tr = self.transformer
             p = tr.packed(sched)
-            kv = tr.condition_kv(cond_emb.contiguous(), sched)
             gids = self._caption_ids(caption_ids, B, device)
-            t_steps = torch.tensor(calls, dtype=torch.long, device=device).view(-1, 2, 1).expand(-1, 2, B).contiguous()
             tmp = torch.empty_like(x)
             r, k = self._truncation()
+            sd = int(self.sample_seed if seed is None else seed)
+            t_steps = torch.tensor(calls, dtype=torch.long, device=device).view(-1, 2, 1)
+            if guide is not None:
+                kv2, scale, tokens2 = self._guide_start(guide, cond_emb, sched)
+                t_steps = t_steps.expand(-1, 2, 2 * B).contiguous()
+                keep_, known_, mode_ = hold if hold is not None else (None, None, 0)
+                _lib.check(_lib.lib().ds_denoiser_sample_guided_rng(
+                    p["handle"], _lib.ptr(x), _lib.ptr(tmp), _lib.ptr(t_steps), len(calls), _lib.ptr(kv2), _lib.ptr(gids), sd,
+                    1 if mode_ == 1 else 0, B, 0 if hold is not None else int(start_tokens is None), r, k, scale,
+                    _lib.ptr(keep_), _lib.ptr(known_), int(mode_), _lib.ptr(tokens2), _lib.ptr(tr.workspace(2 * B, sched, 0)),
+                    _lib.stream()))
+                out = {"content_token": x}
+                if return_logits:
+                    out["logits"] = torch.nn.functional.one_hot(x, K1).permute(0, 2, 1).float()
+                return out
+            kv = tr.condition_kv(cond_emb.contiguous(), sched)
+            t_steps = t_steps.expand(-1, 2, B).contiguous()
             if hold is not None:        # (renoise: stream-1 call 0 was the start state's q_sample, so the calls start at 1)
                 _lib.check(_lib.lib().ds_denoiser_sample_hold_rng(
                     p["handle"], _lib.ptr(x), _lib.ptr(tmp), _lib.ptr(t_steps), len(calls), _lib.ptr(kv), _lib.ptr(gids),
@@ -426,7 +493,10 @@ class DiffusionTransformer(nn.Module):
                 out["logits"] = torch.nn.functional.one_hot(x, K1).permute(0, 2, 1).float()
             return out
         sched = self._schedule_table()
-        kv = self.transformer.condition_kv(cond_emb.contiguous(), sched)
+        if guide is not None:
+            kv, guide = None, self._guide_start(guide, cond_emb, sched)
+        else:
+            kv = self.transformer.condition_kv(cond_emb.contiguous(), sched)
         nxt = torch.empty_like(x)
         calls = 0
         for i, (step, step_post) in enumerate(steps):
@@ -440,8 +510,9 @@ class DiffusionTransformer(nn.Module):
                 calls += 1
                 t = torch.full((B,), step, device=device, dtype=torch.long)
                 tp = None if step_post == step else torch.full((B,), step_post, device=device, dtype=torch.long)
+                kw = {} if guide is None else {"guide": guide}      # (unguided: the call as it always was)
                 self.p_sample_tokens(x, kv, t, u, initial=(start_tokens is None and i == 0 and rep == 0), out=nxt, t_post=tp,
-                                     hold=hold)
+                                     hold=hold, **kw)
                 x, nxt = nxt, x
         out = {"content_token": x}
         if return_logits:
@@ -451,7 +522,8 @@ class DiffusionTransformer(nn.Module):
     @torch.no_grad()
     def sample(self, condition_token, condition_mask, condition_embed, content_token=None, filter_ratio=0.5,
                temperature=1.0, return_att_weight=False, return_logits=False, content_logits=None,
-               print_log=True, noise_fn=None, caption_ids=None, seed=None, keep_mask=None, keep_mode="clamp", **kwargs):
+               print_log=True, noise_fn=None, caption_ids=None, seed=None, keep_mask=None, keep_mode="clamp",
+               guidance_scale=None, null_condition_embed=None, **kwargs):
         """Reverse diffusion from the all-[MASK] state (:587-659, filter_ratio == 0 branch).
 
         noise_fn(step, shape) may supply the uniforms (tests inject the oracle's noise; with the 'q' repeat sampler
@@ -461,8 +533,14 @@ class DiffusionTransformer(nn.Module):
         keep_mask (bool[B, L], True = held; not in the reference): region-held sampling -- the held positions carry
         content_token's tokens through the whole chain as context of the denoiser, the others are generated from [MASK]
         (filter_ratio must resolve to step 0).  keep_mode "clamp" keeps them clean, "renoise" lets them follow the forward
-        process (_hold_start).  The held TOKENS of the result are exactly content_token's."""
+        process (_hold_start).  The held TOKENS of the result are exactly content_token's.
+
+        guidance_scale (not in the reference): classifier-free guidance -- every step evaluates the denoiser under the
+        caption and under null_condition_embed (f32[77,512] or [B,77,512]) in one forward at batch 2B and samples from
+        the renormalised mix  log p_null + scale (log p_caption - log p_null)  (csrc/sampler.hip SampleGuide).  None or
+        exactly 1: today's path, untouched, no null forward."""
         cond_emb = self._cond(condition_token, condition_embed)
+        guide = self._guide(guidance_scale, null_condition_embed, cond_emb)
         T = self.num_timesteps
         start_step = int(T * filter_ratio)
         if keep_mask is not None:
@@ -471,10 +549,10 @@ class DiffusionTransformer(nn.Module):
             hold, x, caption_ids = self._hold_start(keep_mask, keep_mode, content_token, cond_emb.shape[0], noise_fn,
                                                     caption_ids, seed)
             return self._reverse(cond_emb, [(s_, s_) for s_ in range(T - 1, -1, -1)], noise_fn, return_logits,
-                                 start_tokens=x, caption_ids=caption_ids, seed=seed, hold=hold)
+                                 start_tokens=x, caption_ids=caption_ids, seed=seed, hold=hold, guide=guide)
         if start_step == 0:
             return self._reverse(cond_emb, [(s_, s_) for s_ in range(T - 1, -1, -1)], noise_fn, return_logits,
-                                 caption_ids=caption_ids, seed=seed)
+                                 caption_ids=caption_ids, seed=seed, guide=guide)
         # partial re-sampling (:643-651): diffuse the given tokens (e.g. DALLE.get_tokens of a mel) forward to
         # t = start_step - 1, then run the reverse chain from there.  With noise_fn, call 0 is q_sample's draw and
         # the reverse steps get the running call index 1.. instead of the timestep.
@@ -494,23 +572,25 @@ class DiffusionTransformer(nn.Module):
                                                   _lib.ptr(self._schedule_table()), _lib.ptr(x), B, self.content_seq_len,
                                                   self.num_classes - 1, self.num_timesteps, _lib.stream()))
             return self._reverse(cond_emb, [(s_, s_) for s_ in steps], None, return_logits, start_tokens=x,
-                                 caption_ids=gids, seed=seed)
+                                 caption_ids=gids, seed=seed, guide=guide)
         u = noise_fn(0, shape).to(device) if noise_fn is not None else torch.rand(shape, device=device)
         x = self.q_sample_tokens(content_token.to(device), t, u)
         nf = None if noise_fn is None else (lambda st, shp: noise_fn(1 + steps.index(st), shp)) \
             if self.repeat_rate is None else (lambda c, shp: noise_fn(1 + c, shp))
-        return self._reverse(cond_emb, [(s_, s_) for s_ in steps], nf, return_logits, start_tokens=x)
+        return self._reverse(cond_emb, [(s_, s_) for s_ in steps], nf, return_logits, start_tokens=x, guide=guide)
 
     @torch.no_grad()
     def sample_fast(self, condition_token, condition_mask, condition_embed, content_token=None, filter_ratio=0.5,
                     temperature=1.0, return_att_weight=False, return_logits=False, content_logits=None,
                     print_log=True, skip_step=1, noise_fn=None, caption_ids=None, seed=None, keep_mask=None,
-                    keep_mode="clamp", **kwargs):
+                    keep_mode="clamp", guidance_scale=None, null_condition_embed=None, **kwargs):
         """Skip-step sampler (:748-812): timesteps T-1, T-2-skip, ... (0 appended), the network sees t, the
         posterior t - skip_step while t > skip_step.  The reference calls p_pred's pieces directly, so the 'q'
         wrapper on p_sample never applies here.  keep_mask / keep_mode: region-held sampling as in sample(); the
-        posterior's timestep governs what a renoised position is drawn at."""
+        posterior's timestep governs what a renoised position is drawn at.  guidance_scale / null_condition_embed:
+        classifier-free guidance as in sample()."""
         cond_emb = self._cond(condition_token, condition_embed)
+        guide = self._guide(guidance_scale, null_condition_embed, cond_emb)
         if keep_mask is not None and int(self.num_timesteps * filter_ratio) != 0:
             raise ValueError("keep_mask samples the free positions from [MASK]: filter_ratio must resolve to step 0")
         assert int(self.num_timesteps * filter_ratio) == 0     # the reference asserts start_step == 0 (:787)
@@ -524,6 +604,6 @@ class DiffusionTransformer(nn.Module):
         keep, self.repeat_rate = self.repeat_rate, None
         try:
             return self._reverse(cond_emb, [(s_, s_ - skip_step if s_ > skip_step else s_) for s_ in lst], noise_fn,
-                                 return_logits, start_tokens=x, caption_ids=caption_ids, seed=seed, hold=hold)
+                                 return_logits, start_tokens=x, caption_ids=caption_ids, seed=seed, hold=hold, guide=guide)
         finally:
             self.repeat_rate = keep

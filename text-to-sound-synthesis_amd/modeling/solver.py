@@ -226,8 +226,22 @@ def _batch_tensors(solver, batch):
             cond_emb.record_stream(cur)
         else:
             x0, cond_emb = training_prologue(solver.model, batch[0])
+        if getattr(solver, "cond_drop_prob", 0.0) > 0:
+            return training_draws(solver.model, x0, cond_emb, generator=solver.generator,
+                                  cond_drop_prob=solver.cond_drop_prob, null_cond=solver.null_cond)
         return training_draws(solver.model, x0, cond_emb, generator=solver.generator)
     return batch
+
+
+def _condition_dropout(solver, cond_drop_prob):
+    """Condition dropout of step(batch dict) (modeling.train.training_draws): the probability, and the null embedding --
+    DALLE.null_condition(), computed once here."""
+    solver.cond_drop_prob = float(cond_drop_prob)
+    solver.null_cond = None
+    if solver.cond_drop_prob > 0:
+        if solver.model is None:
+            raise ValueError("cond_drop_prob > 0 needs the DALLE model (its null condition): Solver(..., model=dalle)")
+        solver.null_cond = solver.model.null_condition()
 
 
 def _prefetch(solver, batch, ready=None):
@@ -266,15 +280,18 @@ class Solver:
     all-reduce, shard.allreduce_gradients) before clipping, which is where DDP's reduction lands too."""
 
     def __init__(self, train_step, lr=3.0e-6, betas=(0.9, 0.96), eps=1e-8, weight_decay=4.5e-2, scheduler=None,
-                 clip_grad_norm=None, ema=None, allreduce=None, reducer=None, model=None, generator=None):
+                 clip_grad_norm=None, ema=None, allreduce=None, reducer=None, model=None, generator=None, cond_drop_prob=0.0):
         """allreduce: callable(grads) run after the backward (shard.allreduce_gradients); reducer: a shard.GradientReducer --
         the same reduction overlapped with the backward (buckets are all-reduced while earlier blocks are still being
         differentiated).  Give one or neither.
         model: the DALLE drop-in whose `transformer` the train_step differentiates -- with it `step(batch)` takes the
         reference's batch dict {'image': mel, 'text': captions} (modeling.train.training_inputs: BPE -> CLIP -> VQ encode ->
-        sample_time -> noise); generator: torch.Generator for the timesteps and the q_sample noise."""
+        sample_time -> noise); generator: torch.Generator for the timesteps and the q_sample noise.
+        cond_drop_prob: step(batch dict) replaces each sample's caption by the null condition with this probability (what a
+        model needs to have seen for classifier-free guidance); 0 draws nothing."""
         assert allreduce is None or reducer is None
         self.model, self.generator = model, generator
+        _condition_dropout(self, cond_drop_prob)
         self.train_step, self.lr = train_step, float(lr)
         self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
         self.scheduler, self.clip_grad_norm, self.ema, self.allreduce = scheduler, clip_grad_norm, ema, allreduce
@@ -344,10 +361,12 @@ class GraphSolver:
     captured on the first batch (shapes are fixed from then on)."""
 
     def __init__(self, train_step, lr=3.0e-6, betas=(0.9, 0.96), eps=1e-8, weight_decay=4.5e-2, scheduler=None,
-                 clip_grad_norm=None, ema=None, reduce=None, model=None, generator=None):
+                 clip_grad_norm=None, ema=None, reduce=None, model=None, generator=None, cond_drop_prob=0.0):
         """model / generator: as in Solver -- `step(batch_dict)` then runs the caption / mel prologue eagerly on the current
-        stream (it is enqueued while the previous replay is still executing) and replays the captured iteration on its output."""
+        stream (it is enqueued while the previous replay is still executing) and replays the captured iteration on its output.
+        cond_drop_prob: as in Solver."""
         self.model, self.generator = model, generator
+        _condition_dropout(self, cond_drop_prob)
         self.train_step, self.lr = train_step, float(lr)
         self.reduce = reduce
         self.betas, self.eps, self.weight_decay = betas, eps, weight_decay

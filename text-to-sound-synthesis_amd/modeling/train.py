@@ -202,7 +202,7 @@ class _FusedAttn:
 
 
 @torch.no_grad()
-def training_inputs(model, batch, generator=None):
+def training_inputs(model, batch, generator=None, cond_drop_prob=0.0, null_cond=None):
     """The reference's training batch -> the five tensors of `TrainStep.loss_and_grads`: what happens between
     `self.model(batch, return_loss=True)` (engine/solver_spec.py:308-331) and the loss arithmetic.
 
@@ -218,9 +218,9 @@ def training_inputs(model, batch, generator=None):
     'content_token' skips the respective stage; one that carries 'audio' (waveforms at 22 050 Hz, or at batch['audio_rate']) instead of 'image' gets the mel
     from the HIP front end first (DALLE.content_image -> modeling/melspec.py).  generator: torch.Generator of the model's device for t and the noise.
     Everything is enqueued on the current stream; the only host synchronisation is sample_time's Lt_count test while it
-    is still false."""
+    is still false.  cond_drop_prob / null_cond: condition dropout, see training_draws."""
     x0, cond_emb = training_prologue(model, batch)
-    return training_draws(model, x0, cond_emb, generator=generator)
+    return training_draws(model, x0, cond_emb, generator=generator, cond_drop_prob=cond_drop_prob, null_cond=null_cond)
 
 
 @torch.no_grad()
@@ -240,14 +240,25 @@ def training_prologue(model, batch):
 
 
 @torch.no_grad()
-def training_draws(model, x0, cond_emb, generator=None):
+def training_draws(model, x0, cond_emb, generator=None, cond_drop_prob=0.0, null_cond=None):
     """... and the part that depends on the training state: sample_time reads the importance-sampling statistics the previous
-    iteration updated.  -> (x0, cond_emb, t, pt, noise)"""
+    iteration updated.  -> (x0, cond_emb, t, pt, noise)
+
+    cond_drop_prob > 0: condition dropout, what makes a model usable with classifier-free guidance -- after the draws of t and
+    the noise, one uniform per sample from `generator`; the samples below cond_drop_prob get null_cond (f32[77,512], DALLE.
+    null_condition()) as their condition.  With probability 0 no draw is made: the generator's state and every returned tensor
+    are those of a call without the keywords."""
     dt = model.transformer
     dev = dt.device
     B = x0.shape[0]
     t, pt = dt.sample_time(B, dev, "importance", generator=generator)
     noise = torch.rand((B, dt.num_classes, dt.content_seq_len), device=dev, generator=generator)
+    if cond_drop_prob > 0:
+        if null_cond is None:
+            raise ValueError("cond_drop_prob > 0 needs null_cond f32[77,512] (DALLE.null_condition())")
+        drop = torch.rand((B,), device=dev, generator=generator) < cond_drop_prob
+        null = torch.as_tensor(null_cond).to(device=cond_emb.device, dtype=cond_emb.dtype).expand_as(cond_emb)
+        cond_emb = torch.where(drop.to(cond_emb.device)[:, None, None], null, cond_emb).contiguous()
     return x0, cond_emb, t.to(dev), pt.to(dev), noise
 
 

@@ -132,7 +132,7 @@ class Diffsound:
 
     @torch.no_grad()
     def generate_sample_with_condition(self, cond, truncation_rate=0.85, replicate=1, fast=False, caption_ids=None,
-                                       seed=None, sample_rate=None):
+                                       seed=None, sample_rate=None, guidance_scale=None, negative_text=None):
         """Captions -> (mel01 f32[B,80,848], wave f32[B,1,217088] -- None without a vocoder --, tokens), everything left on the GPU.
         `cond` is a list of caption strings (needs the text stage: tokenizer + CLIP in the config),
         token ids i64[B,77], or caption embeddings f32[B,77,512].  fast=n selects the skip-step sampler with
@@ -140,7 +140,9 @@ class Diffsound:
         caption_ids (one global index per caption) switches the sampler to per-caption in-kernel noise: a caption's clip
         then does not depend on the batch it is generated in (DiffusionTransformer.rng_mode); replicate r of caption i
         draws as caption id ids[i] + r * 2^24.  sample_rate: the rate of the returned waveform; another one than 22 050 Hz is the
-        vocoder's output resampled on the device (audio.resample): f32[B,1,ceil(217088 sample_rate / 22050)]."""
+        vocoder's output resampled on the device (audio.resample): f32[B,1,ceil(217088 sample_rate / 22050)].
+        guidance_scale: classifier-free guidance (DALLE.generate_content) against the empty caption or negative_text (a
+        caption, or one per caption); None or 1: unguided."""
         if isinstance(cond, (list, tuple, str)):
             batch = {"text": [cond] if isinstance(cond, str) else list(cond)}
         elif cond.dtype == torch.long:
@@ -151,8 +153,10 @@ class Diffsound:
             batch["caption_ids"] = caption_ids
         if seed is not None:
             batch["seed"] = seed
+        if negative_text is not None:
+            batch["negative_text"] = negative_text
         out = self.model.generate_content(batch=batch, filter_ratio=0, replicate=replicate, content_ratio=1,
-                                          return_att_weight=False,
+                                          return_att_weight=False, guidance_scale=guidance_scale,
                                           sample_type="top" + str(truncation_rate) + ("r,fast" + str(fast - 1) if fast else "r"))
         mel = out["content"]                                   # [B,1,80,848] in ~[-1,1]
         wave = None if self.vocoder is None else self.vocoder(mel[:, 0], scale=0.5, shift=0.5)   # spec = (x+1)/2, :182
@@ -212,7 +216,8 @@ class Diffsound:
             return {"text": [text] if isinstance(text, str) else list(text)}
         return {"condition_token": text} if text.dtype == torch.long else {"condition_embed_token": text}
 
-    def _inpaint_tokens(self, tokens, keep, text, keep_mode, truncation_rate, caption_ids, seed):
+    def _inpaint_tokens(self, tokens, keep, text, keep_mode, truncation_rate, caption_ids, seed, guidance_scale=None,
+                        negative_text=None):
         """DALLE.inpaint_content at this call's truncation rate (the facade installs a rate once and keeps it: set and
         restored around the call, like generate_sample_from_audio does)."""
         batch = dict(self._caption_batch(text), content_token=tokens)
@@ -220,11 +225,13 @@ class Diffsound:
             batch["caption_ids"] = caption_ids
         if seed is not None:
             batch["seed"] = seed
+        if negative_text is not None:
+            batch["negative_text"] = negative_text
         model, tr = self.model, self.model.transformer
         saved = tr.truncation_r, tr.truncation_k, tr.repeat_rate, model.truncation_forward
         tr.truncation_r, tr.truncation_k, model.truncation_forward = float(truncation_rate), None, True
         try:
-            out = model.inpaint_content(batch=batch, keep_mask=keep, keep_mode=keep_mode,
+            out = model.inpaint_content(batch=batch, keep_mask=keep, keep_mode=keep_mode, guidance_scale=guidance_scale,
                                         sample_type="top" + str(truncation_rate) + "r")
         finally:
             tr.truncation_r, tr.truncation_k, tr.repeat_rate, model.truncation_forward = saved
@@ -232,14 +239,14 @@ class Diffsound:
 
     @torch.no_grad()
     def inpaint_audio(self, audio, text, spans, keep_mode="clamp", truncation_rate=0.85, save_root=None, audio_rate=None,
-                      caption_ids=None, seed=None, sample_rate=None):
+                      caption_ids=None, seed=None, sample_rate=None, guidance_scale=None, negative_text=None):
         """Regenerate time spans of given recordings under a caption and keep the rest: audio / audio_rate / text as in
         generate_sample_from_audio; spans = the (t0, t1) seconds to regenerate, shared or one list per clip
         (spans_to_keep_mask: whole grid columns of 4096 samples at 22 050 Hz).  The recording is encoded to its 5 x 53 tokens,
         the tokens outside the spans are held through the whole reverse chain (keep_mode "clamp": clean; "renoise": following
         the forward process, per-caption in-kernel noise) and the spans are generated from [MASK] with them as context.
-        caption_ids / seed / sample_rate as in generate_sample_with_condition.  Returns (mel01, wave or None, tokens) and
-        writes the files generate_sample_from_audio writes.
+        caption_ids / seed / sample_rate / guidance_scale / negative_text as in generate_sample_with_condition.  Returns
+        (mel01, wave or None, tokens) and writes the files generate_sample_from_audio writes.
 
         What is kept is the TOKENS: exact.  The returned audio is the codec's and the vocoder's rendering everywhere -- the
         held region is not the input's samples (the decoder's lowest level attends over all 265 positions), and the original
@@ -247,12 +254,13 @@ class Diffsound:
         content = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})
         known = content["content_token"]
         keep = spans_to_keep_mask(spans, known.shape[0], known.device)
-        tokens = self._inpaint_tokens(known, keep, text, keep_mode, truncation_rate, caption_ids, seed)
+        tokens = self._inpaint_tokens(known, keep, text, keep_mode, truncation_rate, caption_ids, seed, guidance_scale,
+                                      negative_text)
         return self._render(tokens, content["content_quant"].shape, save_root, sample_rate)
 
     @torch.no_grad()
     def continue_audio(self, audio, text, keep_seconds, keep_mode="clamp", truncation_rate=0.85, save_root=None,
-                       audio_rate=None, caption_ids=None, seed=None, sample_rate=None):
+                       audio_rate=None, caption_ids=None, seed=None, sample_rate=None, guidance_scale=None, negative_text=None):
         """Generate the clip that follows given recordings: the last ceil(keep_seconds 22050 / 4096) token columns of the
         recording become the first columns of a new 10-s clip (a shift by 5 (53 - n) tokens), held, and the remaining columns
         are generated under `text`.  Arguments and return as inpaint_audio.  The new clip's head is the codec's rendering of
@@ -260,11 +268,13 @@ class Diffsound:
         caller."""
         content = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})
         known, keep = continuation_tokens(content["content_token"], continuation_columns(keep_seconds))
-        tokens = self._inpaint_tokens(known, keep, text, keep_mode, truncation_rate, caption_ids, seed)
+        tokens = self._inpaint_tokens(known, keep, text, keep_mode, truncation_rate, caption_ids, seed, guidance_scale,
+                                      negative_text)
         return self._render(tokens, content["content_quant"].shape, save_root, sample_rate)
 
     @torch.no_grad()
-    def inference_generate_sample_with_condition(self, text, truncation_rate, save_root, batch_size, fast=False):
+    def inference_generate_sample_with_condition(self, text, truncation_rate, save_root, batch_size, fast=False,
+                                                 guidance_scale=None, negative_text=None):
         """The reference's single-caption driver, same signature and behaviour (generate_samples_batch.py:89-123):
         ONE caption `text`, sampled `replicate = 10` times (hard-coded there, :111; `batch_size` is accepted and
         unused, as in the reference), results written under `save_root/str(text)/` as `000000`, `000001`, ...
@@ -275,7 +285,8 @@ class Diffsound:
         os.makedirs(save_root, exist_ok=True)
         save_root_ = os.path.join(save_root, str(text))
         os.makedirs(save_root_, exist_ok=True)
-        mel01, wave, _ = self.generate_sample_with_condition([text], truncation_rate, replicate=10, fast=fast)
+        mel01, wave, _ = self.generate_sample_with_condition([text], truncation_rate, replicate=10, fast=fast,
+                                                             guidance_scale=guidance_scale, negative_text=negative_text)
         mel01, wave = mel01.cpu().numpy(), None if wave is None else wave[:, 0].cpu().numpy()
         written = []
         for b in range(mel01.shape[0]):
@@ -297,7 +308,8 @@ class Diffsound:
         return caps
 
     @torch.no_grad()
-    def generate_sample(self, val_path, truncation_rate, save_root, fast=False, replicate=2, sample_rate=None):
+    def generate_sample(self, val_path, truncation_rate, save_root, fast=False, replicate=2, sample_rate=None,
+                        guidance_scale=None):
         """The reference's file-writing driver (generate_samples_batch.py:143-187): per audio file, all of
         its captions x `replicate` are sampled in one batch; every sample is written as
         `{base}_mel_sample_{i}.npy` (mel in [0,1], f32[80,848]) and -- if there is a vocoder (:183) --
@@ -313,7 +325,8 @@ class Diffsound:
             ids = list(range(n_seen, n_seen + len(captions))) if philox else None
             n_seen += len(captions)
             mel01, wave, _ = self.generate_sample_with_condition(list(captions), truncation_rate, replicate, fast=fast,
-                                                                 caption_ids=ids, sample_rate=sample_rate)
+                                                                 caption_ids=ids, sample_rate=sample_rate,
+                                                                 guidance_scale=guidance_scale)
             mel01, wave = mel01.cpu().numpy(), None if wave is None else wave[:, 0].cpu().numpy()
             for i in range(mel01.shape[0]):
                 path = os.path.join(save_root, base + str(i))
