@@ -421,6 +421,11 @@ int ds_denoiser_set_split_weights(ds_denoiser* h, int mode, const void* const* s
  * the sampler.  Tokens agree with the unpadded step except on exact near-ties (rows 256..264 of a sample are summed in
  * another order: ~1e-7 relative).  0 switches it off (A/B, bit-for-bit comparisons across batch sizes). */
 int ds_denoiser_set_row_padding(ds_denoiser* h, int on);
+/* f16x2 range monitor.  FC2's operand (the GELU2 outputs) is the one split site of the denoiser that no normalisation
+ * bounds.  With `peak` set (one device float, zeroed by the caller) every forward, step and chain folds max |hi plane| of
+ * every layer's GELU2 output into it; the hi plane clamps at 65504, so a peak >= 65504 means the split saturated and the
+ * result should be recomputed in the fp32 mode.  NULL (the default) switches the monitor off. */
+int ds_denoiser_set_range_monitor(ds_denoiser* h, float* peak);
 /* rows per sample of the activation matrices ds_denoiser_step(_ex) would use at batch B: seq_len, or 272 in padded-row mode */
 int ds_denoiser_rows_per_sample(const ds_denoiser* h, int B);
 /* cross-attention K/V depend only on the caption: computed once per batch (CrossAttention.key/value,

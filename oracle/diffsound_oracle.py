@@ -96,34 +96,52 @@ def _mha(q, k, v, n_head):
     return (att @ vh).transpose(1, 2).reshape(B, Lq, C)
 
 
-def transformer_block(sd, pfx, x, cond, t, n_head=16):
+def _rec_mha(record, name, q, k, v, n_head):
+    """_mha with q, k, v and the pre-softmax scores (scaled by 1 / sqrt(hd)) recorded under name + ".q" / ".k" / ".v" / ".scores":
+    the operands the f16x2 attention kernels split un-scaled, and the spread that decides how sharp the softmax is"""
+    if record is not None:
+        B, Lq, C = q.shape
+        hd = C // n_head
+        qh = q.view(B, Lq, n_head, hd).transpose(1, 2)
+        kh = k.view(B, k.shape[1], n_head, hd).transpose(1, 2)
+        _rec(record, name + ".q", q), _rec(record, name + ".k", k), _rec(record, name + ".v", v)
+        _rec(record, name + ".scores", (qh @ kh.transpose(-2, -1)) * (1.0 / math.sqrt(hd)))
+    return _mha(q, k, v, n_head)
+
+
+def transformer_block(sd, pfx, x, cond, t, n_head=16, record=None):
     """transformer_utils.py:255-272 ('selfcross'): x += attn1(ln1(x,t)); x += attn2(ln1_1(x,t),
-    cond); x += mlp(ln2(x)); mlp = Linear, GELU2 (x*sigmoid(1.702x), :111-115), Linear."""
-    h = _ada_ln(sd, pfx + "ln1", x, t)
-    a = _mha(_linear(sd, pfx + "attn1.query", h), _linear(sd, pfx + "attn1.key", h),
-             _linear(sd, pfx + "attn1.value", h), n_head)
-    x = x + _linear(sd, pfx + "attn1.proj", a)
-    h = _ada_ln(sd, pfx + "ln1_1", x, t)
-    a = _mha(_linear(sd, pfx + "attn2.query", h), _linear(sd, pfx + "attn2.key", cond),
-             _linear(sd, pfx + "attn2.value", cond), n_head)
-    x = x + _linear(sd, pfx + "attn2.proj", a)
+    cond); x += mlp(ln2(x)); mlp = Linear, GELU2 (x*sigmoid(1.702x), :111-115), Linear.
+    `record` (a dict) receives (max, median) of |operand| at every site whose HIP counterpart splits the operand into two
+    un-scaled fp16 planes: the A operands of the seven GEMMs (pfx + "attn1.qkv", "attn1.proj", "attn2.query", "attn2.kv" =
+    the caption embedding, "attn2.proj", "mlp.0", "mlp.2") and q, k, v and the scores of both attentions (_rec_mha)."""
+    h = _rec(record, pfx + "attn1.qkv", _ada_ln(sd, pfx + "ln1", x, t))
+    a = _rec_mha(record, pfx + "attn1", _linear(sd, pfx + "attn1.query", h), _linear(sd, pfx + "attn1.key", h),
+                 _linear(sd, pfx + "attn1.value", h), n_head)
+    x = x + _linear(sd, pfx + "attn1.proj", _rec(record, pfx + "attn1.proj", a))
+    h = _rec(record, pfx + "attn2.query", _ada_ln(sd, pfx + "ln1_1", x, t))
+    _rec(record, pfx + "attn2.kv", cond)
+    a = _rec_mha(record, pfx + "attn2", _linear(sd, pfx + "attn2.query", h), _linear(sd, pfx + "attn2.key", cond),
+                 _linear(sd, pfx + "attn2.value", cond), n_head)
+    x = x + _linear(sd, pfx + "attn2.proj", _rec(record, pfx + "attn2.proj", a))
     h = F.layer_norm(x, (x.shape[-1],), sd[pfx + "ln2.weight"], sd[pfx + "ln2.bias"], eps=1e-5)
-    h = _linear(sd, pfx + "mlp.0", h)
+    h = _linear(sd, pfx + "mlp.0", _rec(record, pfx + "mlp.0", h))
     h = h * torch.sigmoid(1.702 * h)
-    return x + _linear(sd, pfx + "mlp.2", h)
+    return x + _linear(sd, pfx + "mlp.2", _rec(record, pfx + "mlp.2", h))
 
 
 def transformer_forward(sd, tokens, cond_emb, t, pfx="transformer.transformer.", n_head=16,
-                        hw=(5, 53)):
-    """Text2ImageTransformer.forward, transformer_utils.py:421-443 -> logits [B, K, L]."""
+                        hw=(5, 53), record=None):
+    """Text2ImageTransformer.forward, transformer_utils.py:421-443 -> logits [B, K, L].  `record`: as transformer_block's,
+    per block, plus the logits GEMM's operand (pfx + "to_logits.1")."""
     x = content_embed(sd, tokens, pfx + "content_emb.", hw)
     i = 0
     while (pfx + "blocks.%d.ln2.weight" % i) in sd:
-        x = transformer_block(sd, pfx + "blocks.%d." % i, x, cond_emb, t, n_head)
+        x = transformer_block(sd, pfx + "blocks.%d." % i, x, cond_emb, t, n_head, record)
         i += 1
     x = F.layer_norm(x, (x.shape[-1],), sd[pfx + "to_logits.0.weight"],
                      sd[pfx + "to_logits.0.bias"], eps=1e-5)
-    return _linear(sd, pfx + "to_logits.1", x).transpose(1, 2).contiguous()
+    return _linear(sd, pfx + "to_logits.1", _rec(record, pfx + "to_logits.1", x)).transpose(1, 2).contiguous()
 
 
 # --------------------------------------------------------------------------- A6 / A3

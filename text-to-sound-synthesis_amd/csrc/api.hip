@@ -102,6 +102,7 @@ struct ds_denoiser {
     float logits_osc = 1.f;
     int split_mode = DS_SPLIT_NONE;
     int pad_rows = 1;              // padded-row mode allowed (ds_denoiser_set_row_padding; see rows_per_sample())
+    float* range_peak = nullptr;   // f16x2 range monitor (ds_denoiser_set_range_monitor): max |GELU2 output| of every forward
     float S3(int layer, int slot) const { return osc.empty() ? 1.f : osc[(size_t)layer * DS_LP_COUNT + slot]; }
     const float* P(int layer, int slot) const { return lp[(size_t)layer * DS_LP_COUNT + slot]; }
     const void* P3(int layer, int slot) const { return lp3.empty() ? nullptr : lp3[(size_t)layer * DS_LP_COUNT + slot]; }
@@ -176,6 +177,18 @@ extern "C" int ds_denoiser_rows_per_sample(const ds_denoiser* h, int B) { return
 extern "C" int ds_denoiser_set_row_padding(ds_denoiser* h, int on) {
     DS_CHECK_ARG(h, "null handle");
     h->pad_rows = on != 0;
+    return 0;
+}
+
+// Range monitor of the f16x2 mode.  FC2's operand, the GELU2 outputs, is the one split site of the denoiser that is not
+// bounded by a normalisation, and it exists only as packed planes inside a forward: with `peak` set (a device float the
+// caller zeroes), every forward folds max |hi plane| of every layer's GELU2 output into it (one small launch per layer).
+// The hi plane clamps at 65504, so a peak of 65504 says the split saturated; the caller then recomputes in the fp32 mode
+// (modeling/transformer.py range_exceeded).  nullptr switches it off; the fp32 mode never looks at it.
+int ds_amax_packed_hi(const void* plane, int M, int K, float* out, ds_stream_t stream);   // misc.hip
+extern "C" int ds_denoiser_set_range_monitor(ds_denoiser* h, float* peak) {
+    DS_CHECK_ARG(h, "null handle");
+    h->range_peak = peak;
     return 0;
 }
 
@@ -390,6 +403,7 @@ static int forward_impl(const ds_denoiser* h, const int64_t* tokens, const int64
         // x += mlp(ln2(x))
         TRY(lnorm(h->P(l, DS_LP_LN2_G), h->P(l, DS_LP_LN2_B)));
         TRY(lin(l, DS_LP_W_FC1, DS_LP_B_FC1, w.hn, D, pD, nullptr, w.fc, F, D, DS_ACT_GELU2, pF));
+        if (f16 && h->range_peak) TRY(ds_amax_packed_hi(w.fc, M, F, h->range_peak, s));
         TRY(lin(l, DS_LP_W_FC2, DS_LP_B_FC2, w.fc, F, pF, w.x, w.x, D, F, DS_ACT_NONE, 0));
     }
     TRY(lnorm(d.lnf_g, d.lnf_b));

@@ -13,9 +13,18 @@
 // normal range, and the epilogue multiplies by out_scale = 2^-s.  Activations are used unscaled, so the split is
 // fp32-class only for |a| in about [2^-3, 65504].  Above 65504 both planes saturate (anything past 131008 becomes
 // 131008).  Below 2^-3 a1 is an fp16 subnormal and a keeps an absolute precision of 2^-25: the error of a dot
-// product is then at most 2^-25 * sum |w| on top of the fp32-class term.  The denoiser's operands are normalised
-// (LayerNorm, attention and GELU2 outputs).  The codec's and the vocoder's raw-stream operands are not: VQModel.decode
-// and Generator.forward check them against 65504 and recompute past it in the strict fp32 mode.
+// product is then at most 2^-25 * sum |w| on top of the fp32-class term.  Where the denoiser's operands sit (the oracle's
+// record, tests/test_denoiser_operand_record.py): the LayerNorm / AdaLN outputs (QKV, cross-Q, FC1, logits),
+// the self-attention output and the GELU2 outputs have their median above 2^-3 (0.14 .. 0.7); the whole cross-attention
+// K / V side -- the l2-normalised caption embedding (median 0.03), its K and V, the scores and the attention output that
+// feeds the second projection -- runs BELOW 2^-3, i.e. on the 2^-25-absolute bound, not the fp32-class one.  Nothing is
+// bounded above by construction: GELU2 outputs (FC2's operand) reach 1.4e4 on the trained-like weights, a factor 4.5 from
+// saturation, every other site keeps more than 2^3.  That one site is guarded at run time: where the weights alone do not
+// keep it 2^3 below 65504, the denoiser folds max |GELU2 output| of every forward into a device float, and a call during
+// which the split saturated is recomputed in the strict fp32 mode (api.hip ds_denoiser_set_range_monitor,
+// Text2ImageTransformer.range_exceeded).  tests/test_hip_denoiser_range.py holds this kernel to both bounds at operand
+// scales 2^-12 .. 6e4 and runs the guard.  The codec's and the vocoder's raw-stream operands are checked the same way:
+// VQModel.decode and Generator.forward compare them with 65504 and recompute past it in the strict fp32 mode.
 //
 // 256 threads = 4 waves (2x2), block tile BM x BN x 32, two fp16 planes per operand, unpadded 64-byte LDS
 // rows with an XOR chunk swizzle (conflict-free ds_read_b128 and ds_write_b128), double-buffered LDS (one barrier per k-tile), two register sets

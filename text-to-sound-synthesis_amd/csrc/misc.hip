@@ -259,3 +259,53 @@ extern "C" int ds_mel_to_cl(const float* mel, float* out, int B, int C, int T, i
     DS_CHECK_LAUNCH();
     return 0;
 }
+
+// ---- max |x| over the real rows of the hi plane of a packed split operand (common.h ds_packed_off), into *out ---------
+// The denoiser's range monitor (api.hip, ds_denoiser_set_range_monitor): ds_split_hi clamps at 65504, so a maximum of 65504
+// means the split saturated.  X[M][K], rows padded to 16: one 16-byte chunk = 8 halves of one row; the padding rows are never
+// read for their value (they may hold anything).  |half| orders like its low 15 bits; one atomic per workgroup (*out >= 0).
+__global__ __launch_bounds__(256) void ds_amax_packed_hi_kernel(const uint4* __restrict__ plane, int M, int ktiles,
+                                                                long long chunks, unsigned* __restrict__ out) {
+    __shared__ unsigned wm[4];
+    unsigned m = 0u;
+    for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < chunks; c += (long long)gridDim.x * 256) {
+        const long long tile = c >> 6;                                   // 512 halves = 64 chunks per 16 x 32 tile
+        const int row = (int)(tile / ktiles) * 16 + (int)((c & 63) >> 2);
+        if (row >= M) continue;
+        const uint4 v = plane[c];
+        const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const unsigned a = w[e] & 0x7fffu, b = (w[e] >> 16) & 0x7fffu;
+            m = a > m ? a : m;
+            m = b > m ? b : m;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned other = (unsigned)__shfl_xor((int)m, o);
+        m = other > m ? other : m;
+    }
+    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned b = wm[0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) b = wm[w] > b ? wm[w] : b;
+        const unsigned short hb = (unsigned short)b;
+        _Float16 h;
+        __builtin_memcpy(&h, &hb, 2);
+        const float f = (float)h;                                        // (a NaN pattern converts to NaN and is not stored)
+        if (f > 0.f) atomicMax(out, __float_as_uint(f));
+    }
+}
+
+int ds_amax_packed_hi(const void* plane, int M, int K, float* out, ds_stream_t stream) {
+    DS_CHECK_ARG(plane && out && M > 0 && K > 0 && K % 32 == 0, "bad arguments");
+    const long long chunks = (long long)((M + 15) & ~15) * K / 8;
+    const long long blocks = (chunks + 2047) / 2048;
+    hipLaunchKernelGGL(ds_amax_packed_hi_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0,
+                       (hipStream_t)stream, (const uint4*)plane, M, K / 32, chunks, (unsigned*)out);
+    DS_CHECK_LAUNCH();
+    return 0;
+}

@@ -432,8 +432,27 @@ class DiffusionTransformer(nn.Module):
         kv2 = self.transformer.condition_kv(torch.cat((cond_emb.float(), null), 0).contiguous(), sched)
         return kv2, scale, torch.empty(2 * B, self.content_seq_len, device=self.device, dtype=torch.long)
 
-    def _reverse(self, cond_emb, steps, noise_fn, return_logits, start_tokens=None, caption_ids=None, seed=None, hold=None,
-                 guide=None):
+    def _reverse(self, *args, **kwargs):
+        """_reverse_once under the denoiser's range guard (Text2ImageTransformer.range_exceeded): a chain during which FC2's
+        split operand saturated is run again from its start in the fp32 mode, with the state of Python's `random` (the repeat
+        sampler) and of the device's generator (the torch.rand noise) put back first; the Philox noise needs neither."""
+        import random
+        tr = self.transformer
+        tr.packed(self._schedule_table())
+        if tr._packed.get("range_peak") is None:
+            return self._reverse_once(*args, **kwargs)
+        state, gen = random.getstate(), torch.cuda.get_rng_state(self.device)
+        tr.range_exceeded()                                 # clear what earlier calls left
+        out = self._reverse_once(*args, **kwargs)
+        if not tr.range_exceeded():
+            return out
+        random.setstate(state)
+        torch.cuda.set_rng_state(gen, self.device)
+        with tr.strict_mode():
+            return self._reverse_once(*args, **kwargs)
+
+    def _reverse_once(self, cond_emb, steps, noise_fn, return_logits, start_tokens=None, caption_ids=None, seed=None, hold=None,
+                      guide=None):
         """guide: (null embeddings, scale) of _guide -- every call then runs one forward at batch 2B and the guided tail.
         steps: list of (t, t_post) pairs, first one from the all-[MASK] state (or from start_tokens, already
         diffused to the first t).  hold: (keep, known, mode) of _hold_start -- every call then runs the region-held

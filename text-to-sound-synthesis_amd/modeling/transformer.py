@@ -9,13 +9,28 @@ called.  `Text2ImageTransformer.forward` packs the weights once (QKV concatenati
 cross-attention K/V weights) and runs the whole stack through ds_denoiser_forward.
 """
 import ctypes as C
+import math
 import os
+import warnings
 
 import torch
 from torch import nn
 
 from .. import _lib
 from ..config import instantiate_from_config
+
+# The f16x2 kernels split an activation into two UN-SCALED fp16 planes, which saturate at 65504 (csrc/gemm_f16x2.hip).  The
+# range monitor runs where the weights alone do not keep FC2's operand this factor below it (Text2ImageTransformer.range_exceeded).
+SPLIT_LIMIT = 65504.0
+RANGE_HEADROOM = 8.0
+
+
+def gelu2_operand_bound(w, c, g, b):
+    """A bound on |FC2's operand| of one block from its weights alone: FC1 (w [F][D], c [F]) reads h = g * xhat + b with
+    |xhat|_2 <= sqrt(D) (LayerNorm), so its row n gives |w_n . h + c_n| <= sqrt(D) |w_n * g|_2 + |w_n . b + c_n|, and
+    |GELU2(y)| <= |y|."""
+    w, c, g, b = w.double(), c.double(), g.double(), b.double()
+    return float(((w * g).norm(dim=1) * math.sqrt(w.shape[1]) + (w @ b + c).abs()).max())
 
 
 class DalleMaskImageEmbedding(nn.Module):
@@ -135,6 +150,8 @@ class Text2ImageTransformer(nn.Module):
         #   "fp32"   v_mfma_f32_32x32x2_f32, the exact fp32 FMA chain (csrc/gemm_f32.hip): the strict mode
         # (DIFFSOUND_GEMM=fp32 selects the strict mode for a whole process: the one numerics switch read from the environment)
         self.precision = os.environ.get("DIFFSOUND_GEMM", "f16x2")
+        # calls recomputed in the fp32 mode because FC2's split operand reached SPLIT_LIMIT (range_exceeded)
+        self.range_fallbacks = 0
         self.row_padding = True       # padded-row mode of the sampling step (csrc/api.hip rows_per_sample); tests switch it off
         self._packed = None
         self._register_load_state_dict_pre_hook(lambda *a, **k: self.invalidate())
@@ -244,9 +261,42 @@ class Text2ImageTransformer(nn.Module):
         # padded-row mode of the sampling step (272 rows per sample at batch sizes served by the per-sample GEMM program,
         # csrc/api.hip rows_per_sample): on by default; `row_padding = False` keeps 265 rows
         _lib.check(_lib.lib().ds_denoiser_set_row_padding(h, int(self.row_padding)))
+        # range monitor (f16x2 mode): on only where the weights alone do not keep FC2's operand 2^3 below SPLIT_LIMIT
+        peak = None
+        if self.precision == "f16x2" and self.gelu2_operand_bound() * RANGE_HEADROOM > SPLIT_LIMIT:
+            peak = torch.zeros(1, device=dev)
+            _lib.check(_lib.lib().ds_denoiser_set_range_monitor(h, _lib.ptr(peak)))
         self._packed = {"handle": h, "keep": keep, "sched_src": sched, "ws": {}, "device": dev,
-                        "precision": self.precision, "row_padding": self.row_padding}
+                        "precision": self.precision, "row_padding": self.row_padding, "range_peak": peak}
         return self._packed
+
+    @torch.no_grad()
+    def gelu2_operand_bound(self):
+        """the largest gelu2_operand_bound over the blocks"""
+        return max(gelu2_operand_bound(blk.mlp[0].weight, blk.mlp[0].bias, blk.ln2.weight, blk.ln2.bias) for blk in self.blocks)
+
+    def range_exceeded(self):
+        """Range guard of the f16x2 mode (DESIGN.md 4.2).  Every split site of the denoiser but one reads a normalised operand;
+        FC2 reads the GELU2 outputs, which exist only inside a forward.  Where gelu2_operand_bound() does not keep them 2^3 below
+        SPLIT_LIMIT, the handle folds max |GELU2 output| of every forward into one device float (ds_denoiser_set_range_monitor).
+        This reads and clears it (one host read): True if the split saturated since the last call -- the caller then recomputes
+        in the fp32 mode (`forward` here, AudioDiffusion._reverse for a sampling chain), counted in range_fallbacks."""
+        peak = self._packed.get("range_peak") if self._packed else None
+        if peak is None:
+            return False
+        m = float(peak.item())
+        peak.zero_()
+        if m < SPLIT_LIMIT:
+            return False
+        if not self.range_fallbacks:
+            warnings.warn("denoiser: FC2's split operand (GELU2 output) reached %.0f, the largest value the fp16 split holds; the "
+                          "call is recomputed in the strict fp32 mode (counted in range_fallbacks)" % SPLIT_LIMIT)
+        self.range_fallbacks += 1
+        return True
+
+    def strict_mode(self):
+        """context: the fp32 mode for the calls inside (the weights are packed again on entry and on exit)"""
+        return _StrictMode(self)
 
     def workspace(self, B, sched=None, slot=0):
         """One workspace per (batch size, slot); concurrent sub-batches on different streams take different slots."""
@@ -279,4 +329,19 @@ class Text2ImageTransformer(nn.Module):
         _lib.check(_lib.lib().ds_denoiser_forward(
             p["handle"], _lib.ptr(tok), _lib.ptr(tt), _lib.ptr(kv), B,
             _lib.ptr(self.workspace(B, p["sched_src"])), _lib.ptr(out), 1, _lib.stream()))
+        if self.range_exceeded():
+            with self.strict_mode():
+                return self.forward(input, cond_emb, t)
         return out
+
+
+class _StrictMode:
+    def __init__(self, tr):
+        self.tr = tr
+
+    def __enter__(self):
+        self.was, self.tr.precision = self.tr.precision, "fp32"
+
+    def __exit__(self, *exc):
+        self.tr.precision = self.was
+        return False
