@@ -2,10 +2,16 @@
 
 The backward splits every GEMM operand to fp16 under a loss scale 2^k plus one power of two per site (train.py's module
 docstring).  `TrainStep.calibrate` measures, this class decides: where a calibration aims (`_target`, `_exp_from_amax`,
-`site_exponents`), when the calibrated scales are dropped again (`check_loss_scale`: the saturation monitor;
+`site_exponents`, `fwd_exponents`), when the calibrated scales are dropped again (`check_loss_scale`: the saturation monitor;
 `observe_grad_norm`: the gradient norm), and what a weight swap or a re-capture forgets (`reset`).  Nothing here launches a
-kernel; the only device object is the monitor's scalar `_amax_live`, which the step's packs fold into and `check_loss_scale`
-reads with one host sync.
+kernel of the library's; the only device objects are the monitors' scalars `_amax_live` (gradient side) and `_fwd_live` (forward side), which
+the step's packs fold into and `check_loss_scale` reads with one host sync.
+
+The FORWARD operands (LayerNorm outputs, attention outputs, gelu2(fc1 output)) are split unscaled as long as they stay under
+2^13; a linear whose input has grown past that -- fc2's, on trained weights, is the one that gets there -- is packed under a
+power of two 2^f <= 1 of its own (`fwd_exponents`, from the first calibration pass), taken out again by the forward epilogue
+and the dW epilogue.  The split saturates silently at 65504, so real passes fold max |X 2^f| into `_fwd_live` and a reading at
+or above the window's upper end drops the calibration like a gradient-side one.
 """
 import math
 
@@ -24,6 +30,11 @@ class LossScalePolicy:
         # scalar (ds_amax, the calibration's own probe; captured into the graph like any other launch), and
         # check_loss_scale() reads it on the host every `monitor_interval` steps -- whether or not clipping is configured.
         self._amax_live = None
+        # ... and the same for the forward operands: {linear key: f <= 0} of the last calibration (None: none yet; every
+        # missing key is 0) and the device scalar the forward packs fold max |X 2^f| into (None until a step has run: the
+        # host tests of this class leave it out)
+        self.fwd_exp = None
+        self._fwd_live = None
         self.monitor_interval = 16
         # Where a calibration puts the largest value of every fp16-split gradient operand of ITS batch: 2^calib_log2 .. 2x that.
         # What matters for precision is only that a tensor's largest element is >= 2^0 (a split value keeps 22 bits down to
@@ -56,13 +67,15 @@ class LossScalePolicy:
         if self.enabled:
             self.loss_scale_exp = None
             self._site_exp = None
+            self.fwd_exp = None
         self._calib_norm = None
-        if self._amax_live is not None:
-            self._amax_live.zero_()
+        for live in (self._amax_live, self._fwd_live):
+            if live is not None:
+                live.zero_()
 
     def begin_calibration(self):
         """A calibration starts from the bare gradients (no scale at all) and restarts the monitor's 1, 2, 4, 8 schedule."""
-        self.loss_scale_exp, self._site_exp = 0, None
+        self.loss_scale_exp, self._site_exp, self.fwd_exp = 0, None, None
         self._next_check, self._since_check = 1, 0
 
     def check_loss_scale(self, force=False):
@@ -78,9 +91,20 @@ class LossScalePolicy:
             return False
         self._since_check = 0
         self._next_check = min(self.monitor_interval, 2 * self._next_check)
-        m = float(self._amax_live.item())
+        if self._fwd_live is None:
+            m, mf = float(self._amax_live.item()), 0.0
+        else:                                   # both monitors in the one host sync
+            import torch
+            m, mf = torch.cat((self._amax_live.reshape(1), self._fwd_live.reshape(1).to(self._amax_live.device))).tolist()
+            self._fwd_live.zero_()
         self._amax_live.zero_()
         self.monitor_log = self.monitor_log[-63:] + [round(math.log2(m), 2) if m > 0.0 and math.isfinite(m) else m]
+        if not mf < 2.0 ** self.monitor_window[1]:
+            # a forward operand has outgrown the power of two it was calibrated under (or never had one): its planes are
+            # within a bit of saturating, or have.  The next calibration measures the forward again.
+            self.last_trip = "forward operand high: max |X 2^f| = " + ("2^%.2f" % math.log2(mf) if math.isfinite(mf) else repr(mf))
+            self.loss_scale_exp, self._calib_norm, self.fwd_exp = None, None, None
+            return True
         if m == 0.0:
             # ds_amax never lets a NaN win and skips non-positive values, so 0 means EITHER genuinely zero gradients (nothing
             # was scaled: no reason to re-calibrate / re-capture) OR an all-NaN scaled dY (a diverged loss).  The loss of the
@@ -128,6 +152,14 @@ class LossScalePolicy:
         """{key: e} from the second calibration pass: max |operand| per site (under the loss scale, in the order the backward
         visits the sites) -> the power of two that puts it at the target, within 2^-40 .. 2^40"""
         return {k: max(-40, min(40, self._exp_from_amax(v))) for k, v in zip(keys, per_site)}
+
+    @staticmethod
+    def fwd_exponents(keys, per_site):
+        """{key: f} from the first calibration pass: max |forward operand| per linear -> f = min(0, 12 - floor(log2 m)), the
+        power of two that brings a maximum of 2^13 or more back to [2^12, 2^13) -- three bits under the monitor's 2^15, and
+        inside the range (>= 2^-3 for everything within 2^15 of the maximum) where the split is fp32-class.  Never a shift up:
+        below 2^13 an operand is split as it is (f = 0: the step's arithmetic to the bit).  0 for 0 / inf / NaN."""
+        return {k: 0 if not (m > 0.0 and math.isfinite(m)) else min(0, 12 - math.floor(math.log2(m))) for k, m in zip(keys, per_site)}
 
     def observe_grad_norm(self, norm):
         """Second guard of the calibrated scales ("f16x2" backend, eager solver): the calibration leaves 2^9 of headroom below

@@ -31,7 +31,11 @@ Two GEMM backends (`TrainStep(precision=...)`; modeling/train_gemm.py), both beh
            come from a two-pass calibration (`calibrate`: max |operand| per site, two host syncs; the policy around them -- where a
            calibration aims, when it is dropped -- is modeling/loss_scale.py).  A split value keeps an
            absolute precision of 2^-25, so anything above 2^-3 after scaling is fp32-class; the calibration puts every site's
-           largest value at 2^6..2^7 under a saturation monitor whose window ends at 2^15.  The step has no host
+           largest value at 2^6..2^7 under a saturation monitor whose window ends at 2^15.  The FORWARD operands (LayerNorm and
+           attention outputs, gelu2(u)) are split as they are while they stay under 2^13; a linear whose input has outgrown
+           that (fc2's is the candidate: 1.4e4 on trained-like weights) is packed under 2^f = 2^(12 - floor(log2 max)) from the
+           first calibration pass, 2^-f goes into its forward and dW epilogues, and a second monitor scalar takes max |x 2^f|
+           of every pass (LossScalePolicy.fwd_exponents / check_loss_scale; tests/test_hip_train_range.py).  The step has no host
            synchronisation at all and is captured in a hipGraph (`capture`): one graph launch per iteration instead of ~2000
            kernel launches from Python.
 
@@ -279,15 +283,21 @@ class _Pass:
     scale; `small` collects what one multiply un-scales at the end (the weight gradients lose it in their GEMM's epilogue).
 
     site_amax: second calibration pass -- a zeroed f32[>= number of sites] whose slot i takes max |operand| of the i-th site
-    (a linear's dY, a fused attention backward's dO) IN THE ORDER THE BACKWARD VISITS THEM; `site_index` receives the keys."""
+    (a linear's dY, a fused attention backward's dO) IN THE ORDER THE BACKWARD VISITS THEM; `site_index` receives the keys.
+    fwd_amax: first calibration pass -- the same for the FORWARD operands: slot i takes max |x| of the i-th linear input the
+    forward packs (`fwd_index`: the keys), every one packed unscaled.  Every other pass packs a linear's input under its
+    calibrated 2^f (LossScalePolicy.fwd_exp) and folds max |x 2^f| into the forward monitor (`_fwd_live`)."""
 
-    def __init__(self, step, x0, cond_emb, t, pt, noise, calibrating, amax=None, on_grads=None, site_amax=None):
+    def __init__(self, step, x0, cond_emb, t, pt, noise, calibrating, amax=None, on_grads=None, site_amax=None, fwd_amax=None):
         self.step, self.dt, self.tr, self.gemm, self.policy = step, step.dt, step.tr, step.gemm, step.policy
         self.x0, self.cond_emb, self.t, self.pt, self.noise = x0, cond_emb, t, pt, noise
         self.calibrating, self.amax, self.site_amax = calibrating, amax, site_amax
         self.on_grads = None if calibrating else on_grads
         self.site_exp = {} if (calibrating or self.policy._site_exp is None) else self.policy._site_exp
         self.site_index = {}                    # site key -> slot of site_amax, in visiting order
+        self.fwd_amax, self.fwd_index = fwd_amax, {}
+        self.fwd_exp = {} if (fwd_amax is not None or self.policy.fwd_exp is None) else self.policy.fwd_exp
+        self.fwd_live = None
         self.dev = x0.device
         self.B, self.Lx = x0.shape
         self.Lc = cond_emb.shape[1]
@@ -315,6 +325,10 @@ class _Pass:
             if self.policy._amax_live is None or self.policy._amax_live.device != self.dev:
                 self.policy._amax_live = torch.zeros(1, device=self.dev)
             self.amax = self.policy._amax_live
+        if step.precision == "f16x2":
+            if self.policy._fwd_live is None or self.policy._fwd_live.device != self.dev:
+                self.policy._fwd_live = torch.zeros(1, device=self.dev)
+            self.fwd_live = self.policy._fwd_live
         x = self.embed()
         self.adaln_tables()
         saved = []
@@ -322,7 +336,7 @@ class _Pass:
             s, x = self.block_fwd(li, x)
             saved.append(s)
         lnf = self.tr.to_logits[0]
-        hf = G_.prep_x(self.lin_logits, _norm_fwd(x, 1, self.Lx, gamma=lnf.weight, beta=lnf.bias))
+        hf = self.prep_x(self.lin_logits, _norm_fwd(x, 1, self.Lx, gamma=lnf.weight, beta=lnf.bias))
         logits = G_.fwd(self.lin_logits, hf)                                        # [M, K]
         loss, dlog = self.loss_and_dlogits(logits)
         g = self.g
@@ -355,7 +369,7 @@ class _Pass:
         cond = self.cond_emb.reshape(-1, self.cond_emb.shape[-1]).float().contiguous()
         # operand handles (gemm.prep_x): the forward's GEMM input AND the X^T of the same layer's dW, made in one pass; the
         # caption embedding feeds every block's cross K | V projection (same K, same padded contraction: one handle)
-        self.cond_h = self.gemm.prep_x(self.blocks[0]["kv2"], cond)
+        self.cond_h = self.prep_x(self.blocks[0]["kv2"], cond)
         return x
 
     def adaln_tables(self):
@@ -376,6 +390,15 @@ class _Pass:
     def adaln_prefixes(self):
         return ["transformer.blocks.%d.%s" % (li, n) for li in range(len(self.tr.blocks)) for n in ("ln1", "ln1_1")]
 
+    def prep_x(self, lin, x, pro=PACK_PLAIN):
+        """gemm.prep_x under the linear's forward power of two, with max |x 2^f| folded into the first calibration pass's slot
+        of this linear or into the forward monitor (the "fp32" backend: no scale, no monitor)"""
+        if self.fwd_amax is not None:
+            slot = self.fwd_amax[self.fwd_index.setdefault(lin.key, len(self.fwd_index))]
+        else:
+            slot = self.fwd_live
+        return self.gemm.prep_x(lin, x, pro=pro, scale=2.0 ** self.fwd_exp.get(lin.key, 0), amax=slot)
+
     # ---- one block: forward, and its backward right below ----------------------------------------------------------------
     def block_fwd(self, li, x):
         """x -> x + proj1(attn1(qkv1(ln1 x))) -> + proj2(attn2(q2(ln1_1 .), kv2(caption))) -> + fc2(gelu2(fc1(ln2 .)))"""
@@ -384,20 +407,20 @@ class _Pass:
         attn, split = self.step.attn_cls, self.step.split_attention
         s = _BlockActs()
         s.x0 = x
-        s.h1 = G_.prep_x(ls["qkv1"], _norm_fwd(x, 0, Lx, table=self.tabs[2 * li], t=rows))
+        s.h1 = self.prep_x(ls["qkv1"], _norm_fwd(x, 0, Lx, table=self.tabs[2 * li], t=rows))
         qkv = G_.fwd(ls["qkv1"], s.h1)                                            # [M][3D]: q | k | v
         s.att1 = attn((qkv, 0, 3 * D), (qkv, D, 3 * D), (qkv, 2 * D, 3 * D), B, Lx, Lx, H, split=split)
-        s.o1 = G_.prep_x(ls["proj1"], s.att1.out)
+        s.o1 = self.prep_x(ls["proj1"], s.att1.out)
         s.x1 = x = G_.fwd(ls["proj1"], s.o1, R=x)
-        s.h2 = G_.prep_x(ls["q2"], _norm_fwd(x, 0, Lx, table=self.tabs[2 * li + 1], t=rows))
+        s.h2 = self.prep_x(ls["q2"], _norm_fwd(x, 0, Lx, table=self.tabs[2 * li + 1], t=rows))
         q = G_.fwd(ls["q2"], s.h2)
         kv = G_.fwd(ls["kv2"], self.cond_h)                                       # [B*Lc][2D]: k | v
         s.att2 = attn((q, 0, D), (kv, 0, 2 * D), (kv, D, 2 * D), B, Lx, Lc, H, split=split)
-        s.o2 = G_.prep_x(ls["proj2"], s.att2.out)
+        s.o2 = self.prep_x(ls["proj2"], s.att2.out)
         s.x2 = x = G_.fwd(ls["proj2"], s.o2, R=x)
-        s.h3 = G_.prep_x(ls["fc1"], _norm_fwd(x, 1, Lx, gamma=blk.ln2.weight, beta=blk.ln2.bias))
+        s.h3 = self.prep_x(ls["fc1"], _norm_fwd(x, 1, Lx, gamma=blk.ln2.weight, beta=blk.ln2.bias))
         s.u = G_.fwd(ls["fc1"], s.h3)
-        s.g = G_.prep_x(ls["fc2"], s.u, pro=PACK_GELU2)                           # gelu2(u): the f16x2 backend never stores it in fp32
+        s.g = self.prep_x(ls["fc2"], s.u, pro=PACK_GELU2)                           # gelu2(u): the f16x2 backend never stores it in fp32
         return s, G_.fwd(ls["fc2"], s.g, R=x)
 
     def block_bwd(self, li, s, dx):
@@ -461,7 +484,8 @@ class _Pass:
         dxo = G_.dx(lin, dyh, unscale=down) if need_dx else None
         # dW is off the critical path: a backend that pairs products (pairs_dw) gets them collected, side by side (flush_dw)
         dW = torch.empty(lin.N, lin.K, device=self.dev)
-        self.pending_dw.append((lin, xh, dyh, self.inv * down, dW))
+        # (... and 2^-f of a forward operand that was packed as x 2^f: the handle knows it; fp32 handles are plain tensors)
+        self.pending_dw.append((lin, xh, dyh, self.inv * down * getattr(xh, "unscale", 1.0), dW))
         if not G_.pairs_dw:
             self.flush_dw()
         db = G_.db(lin, dyh)
@@ -689,9 +713,15 @@ class TrainStep:
             return 0
         pol, batch = self.policy, (x0, cond_emb, t, pt, noise)
         pol.begin_calibration()
-        amax = torch.zeros(1, device=x0.device)
-        _Pass(self, *batch, calibrating=True, amax=amax).run()
-        m = float(amax.item())
+        # (the forward operands ride along in the same pass and the same host sync: max |x| of every linear's input -> the
+        #  power of two 2^f <= 1 that keeps it under 2^13, LossScalePolicy.fwd_exponents; slot 0 is the gradients' maximum)
+        n_lin = 6 * len(self.tr.blocks) + 2                                  # 6 per block + the caption rows (kv2) + the logits layer
+        probe = torch.zeros(1 + n_lin, device=x0.device)
+        first = _Pass(self, *batch, calibrating=True, amax=probe[0], fwd_amax=probe[1:])
+        first.run()
+        m, *per_lin = probe.tolist()
+        assert len(first.fwd_index) == n_lin, (len(first.fwd_index), n_lin)
+        pol.fwd_exp = pol.fwd_exponents(list(first.fwd_index), per_lin)
         self.calibrated_amax = m
         # Second pass, under that provisional scale (unscaled, the deep sites' operands flush to 0): the largest value of EVERY
         # operand the backward splits to fp16 under the loss scale -- max |dY| per linear (its dY feeds the dX and dW GEMMs)

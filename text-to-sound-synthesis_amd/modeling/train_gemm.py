@@ -2,8 +2,10 @@
 dX = dY W, dW = dY^T X -- behind one surface, `_Fp32Gemm` (exact-fp32 MFMA, the reference arithmetic) and `_SplitGemm` (3-pass
 fp16 split on packed planes), plus the `ds_pack_operand` helpers the second one lives on.
 
-The surface: prepare(lin) once per step and weight; prep_x / prep_dy turn an fp32 matrix into the backend's operand handle;
-fwd, dx, db launch at once; dw_many(items) takes weight-gradient work [(lin, x handle, dY handle, 1 / scale, dW out)] --
+The surface: prepare(lin) once per step and weight; prep_x / prep_dy turn an fp32 matrix into the backend's operand handle --
+each under a power of two of the caller's (`scale`; prep_x: the forward operand's 2^f, which `fwd` takes out again by itself and
+the dW item's 1 / scale must carry as `x handle.unscale`; prep_dy: the site's 2^e, which dx's `unscale` and the dW item take
+out) and with max |operand * scale| folded into `amax`; fwd, dx, db launch at once; dw_many(items) takes weight-gradient work [(lin, x handle, dY handle, 1 / scale, dW out)] --
 `pairs_dw` says whether the step should collect that work over two blocks first (the split backend groups equal products
 into one grid) or hand every product in as it arises.
 """
@@ -73,7 +75,8 @@ class _Fp32Gemm:
     def prepare(self, lin):
         pass
 
-    def prep_x(self, lin, x, pro=PACK_PLAIN):
+    def prep_x(self, lin, x, pro=PACK_PLAIN, scale=1.0, amax=None):
+        """scale, amax: ignored (nothing is split to fp16 here)"""
         return _gelu2(x) if pro == PACK_GELU2 else x
 
     def prep_dy(self, lin, dy, pro=PACK_PLAIN, aux=None, amax=None, need_row=True, scale=1.0):
@@ -115,8 +118,9 @@ class _Fp32Gemm:
 
 class _Packed:
     """What ds_pack_operand made of one fp32 matrix [rows][cols]: `row` = packed planes of the matrix (int16 [2][plane]),
-    `t` = packed planes of its transpose with the contraction index padded to rows_pad, `part` = per-64-row column sums."""
-    __slots__ = ("rows", "cols", "row", "row_plane", "t", "t_plane", "rows_pad", "part")
+    `t` = packed planes of its transpose with the contraction index padded to rows_pad, `part` = per-64-row column sums,
+    `unscale` = 2^-f of a forward operand whose planes hold x 2^f (prep_x; 1.0 everywhere else)."""
+    __slots__ = ("rows", "cols", "row", "row_plane", "t", "t_plane", "rows_pad", "part", "unscale")
 
 
 def _pack(src, rows, cols, *, scale=1.0, pro=PACK_PLAIN, aux=None, want_row=True, rows_pad=0, colsum=False, amax=None, ld=None):
@@ -125,6 +129,7 @@ def _pack(src, rows, cols, *, scale=1.0, pro=PACK_PLAIN, aux=None, want_row=True
     o = _Packed()
     o.rows, o.cols, o.rows_pad = rows, cols, rows_pad
     o.row = o.t = o.part = None
+    o.unscale = 1.0
     o.row_plane = _ceil(rows, 16) * cols
     o.t_plane = _ceil(cols, 16) * rows_pad
     if want_row:
@@ -146,7 +151,7 @@ def _pack_parts(parts, K, scale):
     N = sum(w.shape[0] for w in parts)
     assert all(w.shape[0] % 32 == 0 and w.shape[1] == K and w.is_contiguous() for w in parts)
     o = _Packed()
-    o.rows, o.cols, o.rows_pad, o.part = N, K, N, None
+    o.rows, o.cols, o.rows_pad, o.part, o.unscale = N, K, N, None, 1.0
     o.row_plane, o.t_plane = N * K, _ceil(K, 16) * N
     o.row = torch.empty(2, o.row_plane, dtype=torch.int16, device=dev)
     o.t = torch.empty(2, o.t_plane, dtype=torch.int16, device=dev)
@@ -205,9 +210,13 @@ class _SplitGemm:
         else:
             lin.extra["Wp"] = _pack(lin.W, lin.N, lin.K, scale=2.0 ** s, rows_pad=_ceil(lin.N, 32))
 
-    def prep_x(self, lin, x, pro=PACK_PLAIN):
+    def prep_x(self, lin, x, pro=PACK_PLAIN, scale=1.0, amax=None):
+        """scale: the forward operand's own power of two 2^f (LossScalePolicy.fwd_exp; applied after the prologue): the planes
+        hold x * scale, the handle remembers 1 / scale for `fwd` and for the dW item; `amax` takes max |x * scale|"""
         M = x.shape[0]
-        return _pack(x, M, lin.K, pro=pro, rows_pad=self.rows_pad(lin, M))
+        o = _pack(x, M, lin.K, scale=scale, pro=pro, rows_pad=self.rows_pad(lin, M), amax=amax)
+        o.unscale = 1.0 / scale
+        return o
 
     def prep_dy(self, lin, dy, pro=PACK_PLAIN, aux=None, amax=None, need_row=True, scale=1.0):
         """scale: the site's own power of two (LossScalePolicy._site_exp): the planes hold dY * scale, the column sums (bias
@@ -222,7 +231,7 @@ class _SplitGemm:
         Wp = lin.extra["Wp"]
         # (rows_per_sample: lets the dispatcher take the sampling loop's per-sample 272 x 256 program where its grid pays --
         #  the 20 x 12 tiles of the QKV projection, 91 us against 101; same bits, tests/test_hip_widening.py)
-        return L_.gemm(xp.row, Wp.row, y, M, lin.N, lin.K, bias=lin.b, R=R, split2=lin.extra["osc"], a_plane=xp.row_plane,
+        return L_.gemm(xp.row, Wp.row, y, M, lin.N, lin.K, bias=lin.b, R=R, split2=lin.extra["osc"] * xp.unscale, a_plane=xp.row_plane,
                        w_plane=Wp.row_plane, rows_per_sample=self.rows_per_sample if M % max(1, self.rows_per_sample) == 0 else 0)
 
     def dx(self, lin, dyp, unscale=1.0):
