@@ -145,10 +145,18 @@ __device__ __forceinline__ double wmaxd(double v) {
         float mx = v[0];                                                                 \
         _Pragma("unroll") for (int j = 1; j < NPL; ++j) mx = fmaxf(mx, v[j]);            \
         mx = wmaxf(mx);                                                                  \
+        /* log(n + rest) as log n + log1p(rest / n), n: the classes at the maximum (their exp is exactly 1), rest: the  \
+           others' sum.  log(1 + rest) has an ABSOLUTE error of 1e-16: in the dominant class's entry, -rest, that is     \
+           more than a float ulp once the class holds all but 2e-9 of the mass (tests/test_hip_sampler_edges.py). */    \
         double se = 0.0;                                                                 \
-        _Pragma("unroll") for (int j = 0; j < NPL; ++j) se += exp((double)v[j] - (double)mx); \
+        int nmx = 0;                                                                     \
+        _Pragma("unroll") for (int j = 0; j < NPL; ++j) {                                \
+            const bool top = v[j] == mx;                                                 \
+            nmx += __popcll(__ballot(top));                                              \
+            se += top ? 0.0 : exp((double)v[j] - (double)mx);                            \
+        }                                                                                \
         se = wsumd(se);                                                                  \
-        const double lse64 = log(se);                                                    \
+        const double lse64 = nmx == 1 ? log1p(se) : log((double)nmx) + log1p(se / (double)nmx); \
         _Pragma("unroll") for (int j = 0; j < NPL; ++j) {                                \
             float x = (float)(((double)v[j] - (double)mx) - lse64);                      \
             lp_[j] = fminf(fmaxf(x, -70.f), 0.f);                                        \
