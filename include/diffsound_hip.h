@@ -599,6 +599,15 @@ int ds_stencil7_tanh(const float* taps, int ldt, float bias, float* out, int B, 
 /* mel [B][C][T] -> [B][T][Cpad], y = a*x + b (generate_samples_batch.py:181-182 uses a = b = 0.5) */
 int ds_mel_to_cl(const float* mel, float* out, int B, int C, int T, int Cpad, float a, float b,
                  ds_stream_t stream);
+/* Join W overlapping window mels into one long mel (csrc/misc.hip).  win f32[B][W][C][F]: window w starts at output frame
+ * w S; fade f32[V], V = F - S: the weight of the LATER window over the V frames two neighbours share; out f32[B][C][F + (W-1) S].
+ * For output frame tau: w = min(tau / S, W - 1), f = tau - w S;
+ *     w >= 1 and f < V:  out = (1 - fade[f]) win[w-1][f + S] + fade[f] win[w][f],     otherwise  out = win[w][f];
+ * then out = a out + b (fp32, each operation rounded; a = 1, b = 0 leaves the value as it is).  Requires 0 <= V <= S (at most two
+ * windows cover a frame), F % 4 == 0, S % 4 == 0 and 16-byte aligned pointers (fade may be NULL when V == 0); anything else
+ * returns -1 and launches nothing. */
+int ds_mel_stitch(const float* win, const float* fade, float* out, int B, int W, int C, int F, int S, float a, float b,
+                  ds_stream_t stream);
 /* Audio front end: waveform -> log-mel spectrogram in one launch (csrc/stft_mel.hip).  Replaces the librosa chain of
  * vocoder/mel2wav/extract_mel_spectrogram.py:15-38,141-187 (= Codebook/feature_extraction/extract_mel_spectrogram.py) and
  * Audio2Mel.forward (vocoder/modules.py:54-69).  Per clip b and frame f:

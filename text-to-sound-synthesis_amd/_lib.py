@@ -173,6 +173,7 @@ _PROTOS = {
     "ds_melgan_final": (C.c_int, [_vp, _vp, _f, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "ds_stencil7_tanh": (C.c_int, [_vp, C.c_int, _f, _vp, C.c_int, C.c_int, _vp]),
     "ds_mel_to_cl": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f, _f, _vp]),
+    "ds_mel_stitch": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f, _f, _vp]),
     "ds_wave_to_mel": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_int, _f, _f, _f, _f, _f, _vp, _vp]),
     "ds_resample": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp]),

@@ -1,6 +1,7 @@
 """Host side of the audio front end: the mel filterbank, the FFT tables of `ds_wave_to_mel`, a RIFF reader, and the thin
 launcher of the kernel (csrc/stft_mel.hip) that `modeling.vocoder.Audio2Mel` and `modeling.melspec.WaveToMel` share; the
-polyphase table of `ds_resample` (csrc/resample.hip) and its launcher: audio at any integer sample rate in and out.
+polyphase table of `ds_resample` (csrc/resample.hip) and its launcher: audio at any integer sample rate in and out; the
+cross-fade table of `ds_mel_stitch` (csrc/misc.hip) and its launcher: window mels joined into one long mel.
 
 The reference extracts mels with librosa on the host (Diffsound/vocoder/mel2wav/extract_mel_spectrogram.py:15-38,141-187)
 and reads audio with `librosa.load(path, sr=None)` (:167); its data preparation resamples with `librosa.load(path, sr=22050)`
@@ -192,6 +193,48 @@ def resample(wave, src, dst, *, lengths=None, n_out=None):
     _, _, taps, W = _resample_table(src, dst, wave.device)
     _lib.check(_lib.lib().ds_resample(_lib.ptr(wave), B, T, _lib.ptr(lengths), L, M, _lib.ptr(taps), W, _lib.ptr(out),
                                       int(n_out), _lib.stream()))
+    return out
+
+
+def fade_table(V):
+    """f32[V]: the weight of the LATER window over the V frames two neighbouring windows share (ds_mel_stitch),
+        fade[f] = sin^2(pi (f + 1/2) / (2 V)):
+    strictly increasing from ~0 to ~1 and symmetric, fade[f] + fade[V-1-f] = 1; the earlier window's weight is 1 - fade[f].
+    Built in float64, rounded once (like the resampler's polyphase table)."""
+    V = int(V)
+    if V < 0:
+        raise ValueError("the overlap must be >= 0 frames, got %d" % V)
+    f = np.arange(V, dtype=np.float64)
+    return torch.from_numpy((np.sin(np.pi * (f + 0.5) / (2.0 * max(V, 1))) ** 2).astype(np.float32))
+
+
+_FADE_TABLES = {}
+
+
+def _fade_table(V, device):
+    key = (int(V), device.type, device.index)
+    if key not in _FADE_TABLES:
+        _FADE_TABLES[key] = fade_table(V).to(device)
+    return _FADE_TABLES[key]
+
+
+def stitch_mel(win, hop_frames, scale=1.0, shift=0.0):
+    """ds_mel_stitch on win f32[B, W, C, F] (device): window w starts at frame w hop_frames; the F - hop_frames frames two
+    neighbours share are cross-faded with fade_table -> f32[B, C, F + (W - 1) hop_frames], then scale x + shift.  W = 1 is a
+    scaled copy.  F and hop_frames must be multiples of 4 and F / 2 <= hop_frames <= F (at most two windows cover a frame):
+    otherwise the library's argument error is raised and nothing is launched.  A host tensor raises (there is no CPU path)."""
+    if not torch.is_tensor(win) or win.dim() != 4:
+        raise ValueError("win must be a tensor f32[B, W, C, F]")
+    if not win.is_cuda:
+        raise _lib.DiffsoundHipError("win is not on a GPU: the HIP path has no CPU fallback")
+    win = win.float().contiguous()
+    B, W, C, F = win.shape
+    S = int(hop_frames)
+    V = F - S
+    fade = _fade_table(V, win.device) if 0 < V <= S else None        # (an overlap out of range is the library's to refuse)
+    out = torch.empty(B, C, max(F + (W - 1) * S, 0), device=win.device, dtype=torch.float32)
+    _lib.check(_lib.lib().ds_mel_stitch(_lib.ptr(win), _lib.ptr(fade), _lib.ptr(out), B, W, C, F, S, float(scale), float(shift),
+                                        _lib.stream()))
     return out
 
 

@@ -123,6 +123,37 @@ __global__ __launch_bounds__(256) void ds_vq_argmin_kernel(const float* __restri
     }
 }
 
+// ---- join overlapping window mels into one long mel, cross-faded, with y = a*x + b -----------------------------------
+// win [B][W][C][F], window w starts at output frame w*S; fade [V = F - S] = the weight of the LATER window over the V frames two
+// neighbours share (at most two windows cover a frame: V <= S); out [B][C][Ttot = F + (W-1) S].  Memory-bound: every output
+// value is one or two loads and one store.  A thread takes 4 consecutive frames (F, S and so V, Ttot are multiples of 4: a
+// vector never straddles the edge of an overlap or of a row) as 16-byte loads and one 16-byte store; consecutive threads take
+// consecutive vectors of a row, so a wave reads and writes whole 1 KB runs.  The arithmetic is written unfused, in the order
+// of the defining formula: the result does not depend on what the compiler would contract.
+__global__ __launch_bounds__(256) void ds_mel_stitch_kernel(const float* __restrict__ win, const float* __restrict__ fade,
+                                                            float* __restrict__ out, int W, int C, int F, int S, int vecs_row,
+                                                            long long nvec, float a, float bb) {
+#pragma clang fp contract(off)
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nvec) return;
+    const long long row = i / vecs_row;                       // b * C + c
+    const int tau = (int)(i - row * vecs_row) * 4;
+    const long long b = row / C;
+    const int c = (int)(row - b * C);
+    int w = tau / S;
+    if (w > W - 1) w = W - 1;
+    const int f = tau - w * S;
+    const float* cur = win + (((size_t)b * W + w) * C + c) * F + f;
+    f32x4 o = *(const f32x4*)cur;
+    if (w >= 1 && f < F - S) {
+        const f32x4 prev = *(const f32x4*)(cur - (size_t)C * F + S);       // win[w-1][f + S]
+        const f32x4 fd = *(const f32x4*)(fade + f);
+        o = (1.f - fd) * prev + fd * o;
+    }
+    if (a != 1.f || bb != 0.f) o = a * o + bb;
+    *(f32x4*)(out + (size_t)i * 4) = o;
+}
+
 // ---- C ABI ----------------------------------------------------------------------------------------
 extern "C" int ds_vq_argmin(const float* z, const float* ze, const float* ee, int64_t* idx, float* dmin, int M, int C,
                             int K, ds_stream_t stream_) {
@@ -256,6 +287,22 @@ extern "C" int ds_mel_to_cl(const float* mel, float* out, int B, int C, int T, i
     DS_CHECK_ARG(mel && out && Cpad >= C, "bad arguments");
     hipLaunchKernelGGL(ds_mel_to_cl_kernel, dim3((B * T * Cpad + 255) / 256), dim3(256), 0, stream, mel, out, B, C, T,
                        Cpad, a, b);
+    DS_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int ds_mel_stitch(const float* win, const float* fade, float* out, int B, int W, int C, int F, int S, float a,
+                             float b, ds_stream_t stream_) {
+    DS_CHECK_ARG(win && out && B > 0 && W > 0 && C > 0 && F > 0 && S > 0, "bad arguments");
+    DS_CHECK_ARG(F % 4 == 0 && S % 4 == 0, "F and S must be multiples of 4");
+    DS_CHECK_ARG(F - S >= 0 && F - S <= S, "the overlap F - S must be in 0 .. S (at most two windows per frame)");
+    DS_CHECK_ARG(fade || F == S, "null fade table");
+    DS_CHECK_ARG((((uintptr_t)win | (uintptr_t)fade | (uintptr_t)out) & 15) == 0, "win / fade / out must be 16-byte aligned");
+    const long long ttot = (long long)F + (long long)(W - 1) * S;
+    const long long nvec = (long long)B * C * (ttot / 4);
+    DS_CHECK_ARG(ttot < (1ll << 31) && nvec < (1ll << 38), "too large");
+    hipLaunchKernelGGL(ds_mel_stitch_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, win, fade,
+                       out, W, C, F, S, (int)(ttot / 4), nvec, a, b);
     DS_CHECK_LAUNCH();
     return 0;
 }

@@ -167,6 +167,34 @@ class DALLE(nn.Module):
         return torch.cat([ids for _ in range(replicate)]) + \
             torch.arange(replicate).repeat_interleave(ids.numel()) * int(batch.get("caption_id_stride", 1 << 24))
 
+    @staticmethod
+    def _free_keywords(filter_ratio, temperature, return_att_weight, sample_type):
+        """the chain keywords of generate_content: everything is generated"""
+        return dict(content_token=None, filter_ratio=filter_ratio, temperature=temperature, return_att_weight=return_att_weight,
+                    return_logits=False, print_log=False, sample_type=sample_type)
+
+    @staticmethod
+    def _hold_keywords(tokens, keep, keep_mode):
+        """the chain keywords of inpaint_content: the positions of `keep` carry `tokens`"""
+        return dict(content_token=tokens, filter_ratio=0, return_logits=False, print_log=False, keep_mask=keep, keep_mode=keep_mode)
+
+    def _run_chain(self, batch, condition, kw, replicate, sample_type, guidance_scale):
+        """What generate_content, inpaint_content and generate_long_content share once the chain's own keywords `kw` are set:
+        install the sample type, add the (replicated) condition, the guidance and the noise keywords of `batch`, run sample() or
+        sample_fast() -> tokens i64[B r, 265]."""
+        parts = self._install_sample_type(sample_type)
+        tr = self.transformer
+        kw = dict(kw, condition_token=condition.get("condition_token"), condition_mask=condition.get("condition_mask"),
+                  condition_embed=condition.get("condition_embed_token"))
+        kw.update(self._guidance(batch, guidance_scale, replicate))
+        if batch.get("caption_ids") is not None:             # per-caption in-kernel noise (diffusion.py rng_mode)
+            kw["caption_ids"] = self._replicated_caption_ids(batch, replicate)
+        if batch.get("seed") is not None:
+            kw["seed"] = int(batch["seed"])
+        if len(parts) == 2 and parts[1][:4] == "fast":       # skip-step sampler (:211-222)
+            return tr.sample_fast(skip_step=int(parts[1][4:]), **kw)["content_token"]
+        return tr.sample(**kw)["content_token"]
+
     @torch.no_grad()
     def inpaint_content(self, *, batch, keep_mask, keep_mode="clamp", replicate=1, sample_type="top0.85r", guidance_scale=None):
         """Region-held generation (not in the reference, whose content_ratio slices the token vector and cannot run for any
@@ -194,21 +222,8 @@ class DALLE(nn.Module):
                     condition[k] = torch.cat([condition[k] for _ in range(replicate)], dim=0)
             tokens = torch.cat([tokens for _ in range(replicate)], dim=0)
             keep = torch.cat([keep for _ in range(replicate)], dim=0)
-        parts = self._install_sample_type(sample_type)
-        tr = self.transformer
-        kw = dict(condition_token=condition.get("condition_token"), condition_mask=condition.get("condition_mask"),
-                  condition_embed=condition.get("condition_embed_token"), content_token=tokens, filter_ratio=0,
-                  return_logits=False, print_log=False, keep_mask=keep, keep_mode=keep_mode)
-        kw.update(self._guidance(batch, guidance_scale, replicate))
-        if batch.get("caption_ids") is not None:
-            kw["caption_ids"] = self._replicated_caption_ids(batch, replicate)
-        if batch.get("seed") is not None:
-            kw["seed"] = int(batch["seed"])
-        if len(parts) == 2 and parts[1][:4] == "fast":
-            trans_out = tr.sample_fast(skip_step=int(parts[1][4:]), **kw)
-        else:
-            trans_out = tr.sample(**kw)
-        out_tokens = trans_out["content_token"]
+        out_tokens = self._run_chain(batch, condition, self._hold_keywords(tokens, keep, keep_mode), replicate, sample_type,
+                                     guidance_scale)
         content = self.decode_to_img(out_tokens, (out_tokens.shape[0], 256, 5, 53))
         self.train()
         return {"content": content, "content_token": out_tokens}
@@ -225,24 +240,62 @@ class DALLE(nn.Module):
             for k in condition:
                 if condition[k] is not None:
                     condition[k] = torch.cat([condition[k] for _ in range(replicate)], dim=0)
-        parts = self._install_sample_type(sample_type)
-        tr = self.transformer
-        kw = dict(condition_token=condition.get("condition_token"), condition_mask=condition.get("condition_mask"),
-                  condition_embed=condition.get("condition_embed_token"), content_token=None,
-                  filter_ratio=filter_ratio, temperature=temperature, return_att_weight=return_att_weight,
-                  return_logits=False, print_log=False, sample_type=sample_type)
-        kw.update(self._guidance(batch, guidance_scale, replicate))
-        if batch.get("caption_ids") is not None:             # per-caption in-kernel noise (diffusion.py rng_mode)
-            kw["caption_ids"] = self._replicated_caption_ids(batch, replicate)
-        if batch.get("seed") is not None:
-            kw["seed"] = int(batch["seed"])
-        if len(parts) == 2 and parts[1][:4] == "fast":       # skip-step sampler (:211-222)
-            trans_out = tr.sample_fast(skip_step=int(parts[1][4:]), **kw)
-        else:
-            trans_out = tr.sample(**kw)
-        tokens = trans_out["content_token"]
+        tokens = self._run_chain(batch, condition, self._free_keywords(filter_ratio, temperature, return_att_weight, sample_type),
+                                 replicate, sample_type, guidance_scale)
         zshape = (tokens.shape[0], 256, 5, 53)   # hard-coded in the reference too (:236)
         content = self.decode_to_img(tokens, zshape)
+        self.train()
+        return {"content": content, "content_token": tokens}
+
+    @torch.no_grad()
+    def generate_long_content(self, *, batch, windows, overlap_cols, keep_mode="clamp", sample_type="top0.85r",
+                              guidance_scale=None, start_token=None):
+        """A clip longer than one token grid as `windows` overlapping 5 x 53 grids (not in the reference; the plan comes from
+        pipeline.long_plan).  Window 0 is what generate_content(filter_ratio=0, content_ratio=1) generates with per-caption
+        in-kernel noise (batch['caption_ids'], default 0 .. B-1; batch['seed']) -- or start_token (i64[B, 265], e.g. a
+        recording's tokens), and then no chain runs for it.  Window w >= 1 is inpaint_content's chain on
+        pipeline.continuation_tokens(window w-1, overlap_cols): the last overlap_cols columns of its predecessor, held as its
+        first ones (keep_mode "clamp" | "renoise"), the rest generated under the same caption, seed, sample_type and guidance
+        with the caption ids + w 2^20 (pipeline.window_caption_ids: ids must be below 2^20, which keeps the windows apart from
+        each other and from the replicate stride 2^24).  All windows are decoded in ONE decode_to_img call at batch B W.
+        The model's truncation settings are this call's only: saved before and restored after.
+        Returns {'content_token': i64[B, W, 265], 'content': mel image [B W, 1, 80, 848], clip-major (index b W + w)}."""
+        from ..pipeline import GRID_COLS, MAX_WINDOWS, continuation_tokens, window_caption_ids
+        windows, n = int(windows), int(overlap_cols)
+        if not 1 <= windows <= MAX_WINDOWS:
+            raise ValueError("windows must be in 1 .. %d, got %r" % (MAX_WINDOWS, windows))
+        if not 1 <= n <= GRID_COLS // 2:
+            raise ValueError("overlap_cols must be in 1 .. %d, got %r" % (GRID_COLS // 2, overlap_cols))
+        self.eval()
+        condition = self.prepare_condition(batch=batch)
+        B = next(v.shape[0] for v in condition.values() if torch.is_tensor(v))
+        ids = batch.get("caption_ids")
+        ids = torch.arange(B) if ids is None else torch.as_tensor(ids, dtype=torch.long).reshape(-1)
+        if ids.numel() != B:
+            raise ValueError("%d caption ids for %d captions" % (ids.numel(), B))
+        window_caption_ids(ids, windows - 1)                  # the range check, before anything runs
+        tr = self.transformer
+        saved = tr.truncation_r, tr.truncation_k, tr.repeat_rate, self.truncation_forward
+        self.truncation_forward = False                       # install THIS call's sample type
+        try:
+            if start_token is not None:
+                cur = torch.as_tensor(start_token).to(self.device).long().contiguous()
+                if tuple(cur.shape) != (B, tr.content_seq_len):
+                    raise ValueError("start_token must be i64[%d, %d], got %s" % (B, tr.content_seq_len, tuple(cur.shape)))
+            else:
+                cur = self._run_chain(dict(batch, caption_ids=ids), condition, self._free_keywords(0, 1.0, False, sample_type), 1,
+                                      sample_type, guidance_scale)
+            toks = [cur]
+            for w in range(1, windows):
+                known, keep = continuation_tokens(cur, n)
+                cur = self._run_chain(dict(batch, caption_ids=window_caption_ids(ids, w)), condition,
+                                      self._hold_keywords(known, keep, keep_mode), 1, sample_type, guidance_scale)
+                toks.append(cur)
+        finally:
+            tr.truncation_r, tr.truncation_k, tr.repeat_rate, self.truncation_forward = saved
+        tokens = torch.stack(toks, 1).contiguous()
+        flat = tokens.view(B * windows, tokens.shape[2])
+        content = self.decode_to_img(flat, (flat.shape[0], 256, 5, 53))
         self.train()
         return {"content": content, "content_token": tokens}
 

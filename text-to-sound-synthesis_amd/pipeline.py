@@ -102,6 +102,50 @@ def continuation_tokens(tokens, n_cols):
     return out, keep
 
 
+WINDOW_ID_STRIDE = 1 << 20    # window w of a long clip draws its noise as caption id + w * 2^20 (replicates: + r * 2^24)
+MAX_WINDOWS = 16              # about two minutes at the default overlap
+COLUMN_FRAMES = 16            # mel frames per grid column (4096 / 256)
+
+
+def long_plan(seconds, overlap_seconds=2.4):
+    """The window plan of a clip longer than one 5 x 53 token grid (Diffsound.generate_long): -> (windows W, overlap columns
+    n, total columns, samples).  samples = round(seconds 22050) (whole samples snapped as in spans_to_keep_mask);
+    n = ceil(overlap_seconds 22050 / 4096) columns are shared by two neighbouring windows, 1 <= n <= 26 (the hop 53 - n is
+    then at least n: at most two windows cover a frame); W = 1 while ceil(samples / 4096) <= 53 columns, else
+    1 + ceil((columns - 53) / (53 - n)) -- the fewest windows that cover the clip -- and total = 53 + (W - 1)(53 - n).
+    More than 16 windows, an overlap outside 1 .. 26 columns or a length of no samples raise ValueError.
+
+    The default overlap (2.4 s = 13 columns) is a design choice: the later window is generated with those columns of the
+    earlier one held as context, and their mel frames are cross-faded.  No trained checkpoint has been available to this
+    project, so how the seams SOUND at this or any other overlap has not been measured."""
+    import math
+    samples = int(round(_seconds_to_samples(seconds)))
+    if samples < 1:
+        raise ValueError("seconds must cover at least one sample, got %r" % (seconds,))
+    n = int(math.ceil(_seconds_to_samples(overlap_seconds) / COLUMN_SAMPLES))
+    if not 1 <= n <= GRID_COLS // 2:
+        raise ValueError("overlap_seconds must cover 1 .. %d columns of %d samples, got %r (%d columns)"
+                         % (GRID_COLS // 2, COLUMN_SAMPLES, overlap_seconds, n))
+    needed = -(-samples // COLUMN_SAMPLES)
+    hop = GRID_COLS - n
+    windows = 1 if needed <= GRID_COLS else 1 + -(-(needed - GRID_COLS) // hop)
+    if windows > MAX_WINDOWS:
+        raise ValueError("%r s needs %d windows at an overlap of %d columns: at most %d (%.1f s)"
+                         % (seconds, windows, n, MAX_WINDOWS, (GRID_COLS + (MAX_WINDOWS - 1) * hop) * COLUMN_SAMPLES / VOCODER_RATE))
+    return windows, n, GRID_COLS + (windows - 1) * hop, samples
+
+
+def window_caption_ids(caption_ids, window):
+    """The caption ids window `window` of a long clip draws its noise under: ids + window 2^20 (i64 tensor).  Ids must be in
+    0 .. 2^20 - 1, which keeps the windows apart from each other and from the replicate stride 2^24; else ValueError."""
+    ids = torch.as_tensor(caption_ids, dtype=torch.long).reshape(-1)
+    if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= WINDOW_ID_STRIDE):
+        raise ValueError("caption ids of a long clip must be in 0 .. %d (window w draws as id + w 2^20)" % (WINDOW_ID_STRIDE - 1))
+    if not 0 <= int(window) < MAX_WINDOWS:
+        raise ValueError("window must be in 0 .. %d, got %r" % (MAX_WINDOWS - 1, window))
+    return ids + int(window) * WINDOW_ID_STRIDE
+
+
 class Diffsound:
     def __init__(self, config=None, path=None, ckpt_vocoder=None, device="cuda", random_vocoder=False):
         """ckpt_vocoder falsy: `self.vocoder = None` and the drivers write `.npy` only, as the reference does (:53-56).
@@ -264,13 +308,91 @@ class Diffsound:
         """Generate the clip that follows given recordings: the last ceil(keep_seconds 22050 / 4096) token columns of the
         recording become the first columns of a new 10-s clip (a shift by 5 (53 - n) tokens), held, and the remaining columns
         are generated under `text`.  Arguments and return as inpaint_audio.  The new clip's head is the codec's rendering of
-        the kept tail (exact tokens, not the input's samples); stitching the two waveforms across the seam is left to the
-        caller."""
+        the kept tail (exact tokens, not the input's samples).  This returns the NEW clip only; extend_audio returns the
+        recording and what follows it as one clip, joined in the mel domain."""
         content = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})
         known, keep = continuation_tokens(content["content_token"], continuation_columns(keep_seconds))
         tokens = self._inpaint_tokens(known, keep, text, keep_mode, truncation_rate, caption_ids, seed, guidance_scale,
                                       negative_text)
         return self._render(tokens, content["content_quant"].shape, save_root, sample_rate)
+
+    def _long_tokens(self, text, windows, overlap_cols, keep_mode, truncation_rate, caption_ids, seed,
+                     guidance_scale, negative_text, start_token=None):
+        """DALLE.generate_long_content under this call's caption / noise keywords (the truncation rate is the call's: the
+        facade saves and restores the model's own)."""
+        batch = dict(self._caption_batch(text))
+        if caption_ids is not None:
+            batch["caption_ids"] = caption_ids
+        if seed is not None:
+            batch["seed"] = seed
+        if negative_text is not None:
+            batch["negative_text"] = negative_text
+        return self.model.generate_long_content(batch=batch, windows=windows, overlap_cols=overlap_cols, keep_mode=keep_mode,
+                                                sample_type="top" + str(truncation_rate) + "r", guidance_scale=guidance_scale,
+                                                start_token=start_token)
+
+    VOCODER_CHUNK_FRAMES = 64 * 848       # mel frames per vocoder call of a long clip: the largest call the benchmarks run
+
+    def _render_long(self, out, windows, overlap_cols, samples, save_root, sample_rate):
+        """window mels -> ds_mel_stitch (codec domain) -> ONE vocoder pass per clip over its whole stitched mel -> both cut to
+        `samples` (the vocoder's reflection at the far end lies past the cut) -> sample_rate, files.  Clips go through the
+        vocoder in batch chunks of at most VOCODER_CHUNK_FRAMES mel frames; a clip is never split."""
+        import numpy as np
+        from . import audio
+        win = out["content"]                                          # [B W, 1, 80, 848], clip-major: index b W + w
+        B = win.shape[0] // windows
+        mel = audio.stitch_mel(win.reshape(B, windows, win.shape[2], win.shape[3]), (GRID_COLS - overlap_cols) * COLUMN_FRAMES)
+        wave = None
+        if self.vocoder is not None:
+            step = max(1, self.VOCODER_CHUNK_FRAMES // mel.shape[2])
+            wave = torch.cat([self.vocoder(mel[i:i + step], scale=0.5, shift=0.5) for i in range(0, B, step)], 0)
+            wave = self._at_rate(wave[:, :, :samples].contiguous(), sample_rate)
+        mel01 = ((mel + 1) / 2)[:, :, :-(-samples // 256)].contiguous()
+        if save_root is not None:
+            os.makedirs(save_root, exist_ok=True)
+            m_, w_ = mel01.cpu().numpy(), None if wave is None else wave[:, 0].cpu().numpy()
+            for i in range(B):
+                path = os.path.join(save_root, str(i).zfill(6))
+                np.save(path + ".npy", m_[i])
+                if w_ is not None:
+                    write_wav_pcm24(path + ".wav", w_[i], VOCODER_RATE if sample_rate is None else int(sample_rate))
+        return mel01, wave, out["content_token"]
+
+    @torch.no_grad()
+    def generate_long(self, text, seconds, overlap_seconds=2.4, truncation_rate=0.85, keep_mode="clamp", caption_ids=None,
+                      seed=None, sample_rate=None, guidance_scale=None, negative_text=None, save_root=None):
+        """Captions -> clips of `seconds` (up to 16 windows, about two minutes): (mel01 f32[B, 80, ceil(samples / 256)], wave
+        f32[B, 1, samples] -- None without a vocoder --, tokens i64[B, W, 265]), samples = round(seconds 22050).  The clip is
+        generated as W overlapping windows of one 5 x 53 grid each (long_plan): window 0 like generate_sample_with_condition
+        with per-caption in-kernel noise, every later window by region-held sampling with the last ceil(overlap_seconds
+        22050 / 4096) token columns of its predecessor held as its first columns (keep_mode as in inpaint_audio), under the
+        same caption, seed and guidance, drawing as caption id + w 2^20 (caption_ids default 0 .. B-1, each below 2^20).  All
+        windows are decoded in one batch; their mels are cross-faded over the shared frames on the device (audio.stitch_mel)
+        and the vocoder renders the whole long mel at once, so the waveform has no seam of its own -- it reflects only at the
+        clip's two ends, and the far end's reflection is cut away with the frames past `samples`.  sample_rate / save_root as
+        in the other drivers.  seconds up to one grid (217 088 samples): W = 1, the same path without a held chain.
+
+        The overlap is a design choice whose audible quality is unmeasured (long_plan)."""
+        windows, n, _, samples = long_plan(seconds, overlap_seconds)
+        out = self._long_tokens(text, windows, n, keep_mode, truncation_rate, caption_ids, seed, guidance_scale, negative_text)
+        return self._render_long(out, windows, n, samples, save_root, sample_rate)
+
+    @torch.no_grad()
+    def extend_audio(self, audio, text, seconds, overlap_seconds=2.4, truncation_rate=0.85, keep_mode="clamp", caption_ids=None,
+                     seed=None, sample_rate=None, guidance_scale=None, negative_text=None, save_root=None, audio_rate=None):
+        """Extend given recordings to `seconds` in total (more than one grid, 217 088 / 22 050 s): audio / audio_rate as in
+        continue_audio; the recording is encoded to its 5 x 53 tokens, which become window 0, and the windows after it are
+        generated under `text` as in generate_long.  Returns what generate_long returns; tokens[:, 0] are the recording's.
+        The head of the result is the codec's and the vocoder's rendering of the recording's tokens, not the input's samples
+        (see continue_audio)."""
+        windows, n, _, samples = long_plan(seconds, overlap_seconds)
+        if windows < 2:
+            raise ValueError("extend_audio: seconds must exceed one grid (%d samples at %d Hz), got %r"
+                             % (CLIP_SAMPLES, VOCODER_RATE, seconds))
+        start = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})["content_token"]
+        out = self._long_tokens(text, windows, n, keep_mode, truncation_rate, caption_ids, seed, guidance_scale, negative_text,
+                                start_token=start)
+        return self._render_long(out, windows, n, samples, save_root, sample_rate)
 
     @torch.no_grad()
     def inference_generate_sample_with_condition(self, text, truncation_rate, save_root, batch_size, fast=False,
