@@ -246,6 +246,35 @@ int ds_sample_tail_guided_rng(const float* logits_c, const float* logits_u, cons
                               int64_t* out_tokens, int B, int L, int K, int T, int initial, float trunc_r, int trunc_k,
                               float scale, const unsigned char* keep, const int64_t* known, int mode, ds_stream_t stream);
 
+/* Purity-prior sampling in the tail (the high-quality inference strategy of Tang et al., "Improved Vector Quantized
+ * Diffusion Models", 2022; specification: DESIGN.md section 4).  One step reveals an exact number of [MASK] positions per
+ * sample, the most confident first, and never re-samples a revealed token; it uses no posterior and no schedule table.
+ * Per grid position (one wavefront, ds_sample_purity_rows_kernel):
+ *     lp    predict_start of the row; with logits_u != NULL the guided mix of ds_sample_tail_guided (scale) comes next
+ *     tr    the truncation of lp (trunc_r / trunc_k as in ds_sample_tail_ex; dropped classes at -70)
+ *     lmax  max_c lp[c], before truncation: the log of the purity
+ *     sh    weight == 0: tr, bit for bit; weight > 0: with a = 1 + weight expf(lmax),
+ *           a tr - logsumexp(a tr) in float64, max-shifted, rounded to f32, clamped to [-70, 0]
+ *     cand  argmax over the K real classes of sh[c] + G(u_c), G(u) = -logf(-logf(u + 1e-30f) + 1e-30f), first index wins
+ *     key   lmax + G(u_K) where xt == K ([MASK]), -INFINITY elsewhere; u_K is the [MASK] slot's uniform
+ * and per sample (one workgroup, ds_sample_purity_select_kernel): with m [MASK] positions and n = max(0, m - remain), the
+ * n masked positions of largest key (equal keys: the smaller position first) get out = cand, every other position keeps xt.
+ * The uniforms are the plain tail's: u [B][K+1][L], or the Philox words of (gids, seed, call) (ds_sample_tail_rng).
+ *   lrows    rows of logits (and logits_u) per sample, >= L: [B * lrows][K] (the denoiser's padded-row mode)
+ *   scratch  ds_purity_scratch_bytes(B, L) bytes of device memory: cand i32[B][L], then key f32[B][L]
+ *   dbg_*    optional: dbg_sharp f32[B][K+1][L] (sh, [MASK] row -70), dbg_key f32[B][L], dbg_cand i32[B][L]
+ * Rejected (-1, nothing launched): null pointers, K other than 256 / 512, remain < 0, a negative or non-finite weight, a
+ * non-finite scale with logits_u, both truncations, lrows < L, L > 288. */
+int64_t ds_purity_scratch_bytes(int B, int L);
+int ds_sample_tail_purity(const float* logits, const float* logits_u, float scale, const int64_t* xt, const float* u,
+                          int remain, float weight, float trunc_r, int trunc_k, int lrows, void* scratch,
+                          int64_t* out_tokens, float* dbg_sharp, float* dbg_key, int32_t* dbg_cand, int B, int L, int K,
+                          ds_stream_t stream);
+int ds_sample_tail_purity_rng(const float* logits, const float* logits_u, float scale, const int64_t* xt,
+                              const int64_t* gids, unsigned long long seed, int call, int remain, float weight,
+                              float trunc_r, int trunc_k, int lrows, void* scratch, int64_t* out_tokens, float* dbg_sharp,
+                              float* dbg_key, int32_t* dbg_cand, int B, int L, int K, ds_stream_t stream);
+
 /* forward terms of the training loss (DiffusionTransformer._train_loss, diffusion_transformer.py:408-476), one value
  * per grid position [B][L]: kl = KL(true posterior || model posterior) (:439-440), nll = the t == 0 decoder term
  * (:446), kl_aux = KL(x_0 || p(x_0|x_t)) over the K classes (:462); logits [B*L][K] of the network at (x_t, t),
@@ -497,6 +526,28 @@ int ds_denoiser_sample_guided_rng(const ds_denoiser* h, int64_t* tokens, int64_t
                                   int n_calls, const float* kv, const int64_t* gids, unsigned long long seed, int call0,
                                   int B, int initial, float trunc_r, int trunc_k, float scale, const unsigned char* keep,
                                   const int64_t* known, int mode, int64_t* tokens2, void* workspace, ds_stream_t stream);
+
+/* Purity-prior steps and chains (see ds_sample_tail_purity): forward + purity tail.  t drives the network only (AdaLN);
+ * remain = the [MASK] positions a sample may still have after the step; weight = the sharpening weight r.  Region-held
+ * sampling needs no further argument: a held position enters as its known token, which no step changes.
+ *   tokens2   NULL: unguided -- kv, workspace and t are those of ds_denoiser_step_rng at batch B, scale is not read.
+ *             i64[2B][seq_len]: guided with `scale`, on ds_denoiser_step_guided's conventions -- kv and workspace at batch
+ *             2B, t with 2B entries (the caller's B repeated), tokens2 receives the duplicated tokens of every step
+ *   scratch   ds_purity_scratch_bytes(B, seq_len) bytes; a pointer of its own, the workspace keeps its size
+ * The chain runs n_calls steps without returning to the host: t_steps = DEVICE i64[n_calls][B] (guided: [n_calls][2B]),
+ * remain = HOST int[n_calls] (read before the call returns), tokens in: the start state / out: the result, tokens_tmp the
+ * other end of the ping-pong, call k draws Philox call index call0 + k.  Argument checks come before anything is enqueued. */
+int ds_denoiser_step_purity(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const float* kv, const float* u,
+                            int B, int remain, float weight, float trunc_r, int trunc_k, float scale, int64_t* tokens2,
+                            void* workspace, void* scratch, int64_t* tokens_out, ds_stream_t stream);
+int ds_denoiser_step_purity_rng(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const float* kv,
+                                const int64_t* gids, unsigned long long seed, int call, int B, int remain, float weight,
+                                float trunc_r, int trunc_k, float scale, int64_t* tokens2, void* workspace, void* scratch,
+                                int64_t* tokens_out, ds_stream_t stream);
+int ds_denoiser_sample_purity_rng(const ds_denoiser* h, int64_t* tokens, int64_t* tokens_tmp, const int64_t* t_steps,
+                                  const int* remain, int n_calls, const float* kv, const int64_t* gids,
+                                  unsigned long long seed, int call0, int B, float weight, float trunc_r, int trunc_k,
+                                  float scale, int64_t* tokens2, void* workspace, void* scratch, ds_stream_t stream);
 
 /* per-launch HIP-event timing of the denoiser's GEMM launches (measurement only, bench.py) */
 int ds_profile_enable(int on);

@@ -148,6 +148,17 @@ _PROTOS = {
                                               C.c_int, _f, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
     "ds_denoiser_sample_guided_rng": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_uint64, C.c_int, C.c_int, C.c_int,
                                                 _f, C.c_int, _f, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "ds_purity_scratch_bytes": (_i64, [C.c_int, C.c_int]),
+    "ds_sample_tail_purity": (C.c_int, [_vp, _vp, _f, _vp, _vp, C.c_int, _f, _f, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp,
+                                        C.c_int, C.c_int, C.c_int, _vp]),
+    "ds_sample_tail_purity_rng": (C.c_int, [_vp, _vp, _f, _vp, _vp, C.c_uint64, C.c_int, C.c_int, _f, _f, C.c_int, C.c_int, _vp,
+                                            _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "ds_denoiser_step_purity": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _f, _f, C.c_int, _f, _vp, _vp, _vp, _vp,
+                                          _vp]),
+    "ds_denoiser_step_purity_rng": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, C.c_int, C.c_int, C.c_int, _f, _f, C.c_int,
+                                              _f, _vp, _vp, _vp, _vp, _vp]),
+    "ds_denoiser_sample_purity_rng": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int), C.c_int, _vp, _vp, C.c_uint64, C.c_int,
+                                                C.c_int, _f, _f, C.c_int, _f, _vp, _vp, _vp, _vp]),
     "ds_profile_enable": (C.c_int, [C.c_int]),
     "ds_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i64)]),
     "ds_profile_collect_n": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i64), C.c_int]),

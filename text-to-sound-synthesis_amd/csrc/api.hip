@@ -646,6 +646,93 @@ extern "C" int ds_denoiser_sample_guided_rng(const ds_denoiser* h, int64_t* toke
     return 0;
 }
 
+// ---- purity-prior sampling (sampler.hip SamplePurity): forward + purity tail.  tokens2 == NULL: the forward of step_impl at
+// batch B; else guided_step_impl's forward at batch 2B on the duplicated tokens, the tail mixing the two halves of the logits.
+// The tail reads no timestep and no schedule table.  scratch: ds_purity_scratch_bytes, a pointer of its own.
+int ds_sample_tail_purity_check(const char* who, bool pointers, bool guided, float scale, int remain, float weight, float trunc_r,
+                                int trunc_k, int logits_rows, int L, int K);   // sampler.hip
+int ds_sample_tail_purity_rows(const char* who, const float* logits, const float* logits_u, float scale, int logits_rows,
+                               const int64_t* xt, const float* u, const int64_t* gids, unsigned long long seed, int call,
+                               int remain, float weight, float trunc_r, int trunc_k, void* scratch, int64_t* out_tokens,
+                               float* dbg_sharp, float* dbg_key, int32_t* dbg_cand, int B, int L, int K, ds_stream_t stream);
+
+static int purity_step_impl(const char* who, const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const float* kv,
+                            const float* u, const int64_t* gids, unsigned long long seed, int call, int B, int remain,
+                            float weight, float trunc_r, int trunc_k, float scale, int64_t* tokens2, void* workspace,
+                            void* scratch, int64_t* tokens_out, ds_stream_t stream, bool zero_kv_pad = true) {
+    const int L = h->d.seq_len, K = h->d.n_codes, Bf = tokens2 ? 2 * B : B;
+    const int64_t* fwd_tokens = tokens_in;
+    if (tokens2) {
+        for (int half = 0; half < 2; ++half) {
+            hipError_t e = hipMemcpyAsync(tokens2 + (size_t)half * B * L, tokens_in, (size_t)B * L * sizeof(int64_t),
+                                          hipMemcpyDeviceToDevice, (hipStream_t)stream);
+            if (e != hipSuccess) {
+                ds_set_error("%s: hipMemcpyAsync: %s", who, hipGetErrorString(e));
+                return -2;
+            }
+        }
+        fwd_tokens = tokens2;
+    }
+    Carve w;
+    const int Lp = rows_per_sample(h, Bf);
+    carve(h, Bf, workspace, &w, Lp);
+    TRY(forward_impl(h, fwd_tokens, t, kv, Bf, w, w.logits, 0, (hipStream_t)stream, Lp, zero_kv_pad));
+    return ds_sample_tail_purity_rows(who, w.logits, tokens2 ? w.logits + (size_t)B * Lp * K : nullptr, scale, Lp, tokens_in, u,
+                                      gids, seed, call, remain, weight, trunc_r, trunc_k, scratch, tokens_out, nullptr, nullptr,
+                                      nullptr, B, L, K, stream);
+}
+
+extern "C" int ds_denoiser_step_purity(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const float* kv,
+                                       const float* u, int B, int remain, float weight, float trunc_r, int trunc_k, float scale,
+                                       int64_t* tokens2, void* workspace, void* scratch, int64_t* tokens_out,
+                                       ds_stream_t stream) {
+    TRY(ds_sample_tail_purity_check(__func__, h && tokens_in && t && kv && u && workspace && scratch && tokens_out && B > 0,
+                                    tokens2 != nullptr, scale, remain, weight, trunc_r, trunc_k, h ? h->d.seq_len : 0,
+                                    h ? h->d.seq_len : 0, h ? h->d.n_codes : 0));
+    return purity_step_impl(__func__, h, tokens_in, t, kv, u, nullptr, 0ull, 0, B, remain, weight, trunc_r, trunc_k, scale,
+                            tokens2, workspace, scratch, tokens_out, stream);
+}
+
+extern "C" int ds_denoiser_step_purity_rng(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const float* kv,
+                                           const int64_t* gids, unsigned long long seed, int call, int B, int remain,
+                                           float weight, float trunc_r, int trunc_k, float scale, int64_t* tokens2,
+                                           void* workspace, void* scratch, int64_t* tokens_out, ds_stream_t stream) {
+    TRY(ds_sample_tail_purity_check(__func__, h && tokens_in && t && kv && gids && workspace && scratch && tokens_out && B > 0,
+                                    tokens2 != nullptr, scale, remain, weight, trunc_r, trunc_k, h ? h->d.seq_len : 0,
+                                    h ? h->d.seq_len : 0, h ? h->d.n_codes : 0));
+    return purity_step_impl(__func__, h, tokens_in, t, kv, nullptr, gids, seed, call, B, remain, weight, trunc_r, trunc_k, scale,
+                            tokens2, workspace, scratch, tokens_out, stream);
+}
+
+// the whole purity chain: ds_denoiser_sample_rng's ping-pong and call0 rules; t_steps is i64[n_calls][B] (guided: [n_calls][2B]),
+// remain a HOST array read here, before the call returns
+extern "C" int ds_denoiser_sample_purity_rng(const ds_denoiser* h, int64_t* tokens, int64_t* tokens_tmp, const int64_t* t_steps,
+                                             const int* remain, int n_calls, const float* kv, const int64_t* gids,
+                                             unsigned long long seed, int call0, int B, float weight, float trunc_r,
+                                             int trunc_k, float scale, int64_t* tokens2, void* workspace, void* scratch,
+                                             ds_stream_t stream) {
+    const bool ptrs = h && tokens && tokens_tmp && t_steps && remain && kv && gids && workspace && scratch && B > 0 && n_calls >= 0;
+    for (int k = 0; k < (ptrs ? n_calls : 1); ++k)          // every step's arguments, before anything is enqueued
+        TRY(ds_sample_tail_purity_check(__func__, ptrs, tokens2 != nullptr, scale, ptrs && n_calls > 0 ? remain[k] : 0, weight,
+                                        trunc_r, trunc_k, h ? h->d.seq_len : 0, h ? h->d.seq_len : 0, h ? h->d.n_codes : 0));
+    int64_t *cur = tokens, *nxt = tokens_tmp;
+    const size_t tb = tokens2 ? 2 * (size_t)B : (size_t)B;
+    for (int k = 0; k < n_calls; ++k) {
+        TRY(purity_step_impl(__func__, h, cur, t_steps + (size_t)k * tb, kv, nullptr, gids, seed, call0 + k, B, remain[k], weight,
+                             trunc_r, trunc_k, scale, tokens2, workspace, scratch, nxt, stream, k == 0));
+        int64_t* sw = cur; cur = nxt; nxt = sw;
+    }
+    if (cur != tokens) {
+        hipError_t e = hipMemcpyAsync(tokens, cur, (size_t)B * h->d.seq_len * sizeof(int64_t), hipMemcpyDeviceToDevice,
+                                      (hipStream_t)stream);
+        if (e != hipSuccess) {
+            ds_set_error("ds_denoiser_sample_purity_rng: hipMemcpyAsync: %s", hipGetErrorString(e));
+            return -2;
+        }
+    }
+    return 0;
+}
+
 extern "C" int ds_denoiser_step(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const float* kv,
                                 const float* u, int B, int initial, float trunc_r, void* workspace,
                                 int64_t* tokens_out, ds_stream_t stream) {

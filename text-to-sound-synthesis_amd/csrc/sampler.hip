@@ -127,6 +127,21 @@ struct SampleGuide {
     float scale;
 };
 
+// PURITY form (purity-prior sampling: the *_purity entries; specification: DESIGN.md section 4).  The column's wave runs the
+// prediction, the guidance and the truncation of the body below -- the same code, not a copy -- and then, instead of the posterior,
+// sharpens the truncated prediction (weight r > 0: a = 1 + r expf(lmax), sh = a tr - logsumexp(a tr) in float64; r == 0: sh = tr,
+// no arithmetic), draws the candidate token c* = argmax over the K real classes of sh + Gumbel with the uniforms the plain tail
+// uses for those classes, and writes (c*, key) to the caller's scratch: key = lmax + Gumbel([MASK] slot's uniform) at a [MASK]
+// position, -INFINITY elsewhere; lmax = max_c lp[c] before truncation is the log of the purity.  Which positions take their
+// candidate is decided per sample by ds_sample_purity_select_kernel.  A separate kernel argument and separate __global__
+// wrappers, as for SampleHold and SampleGuide: the other kernels keep their arguments, registers and code.
+struct SamplePurity {
+    int* cand;                   // [B][L]
+    float* key;                  // [B][L]
+    float* dbg_sharp;            // optional [B][K+1][L]
+    float weight;                // r >= 0
+};
+
 __device__ __forceinline__ double wmaxd(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
@@ -163,9 +178,10 @@ __device__ __forceinline__ double wmaxd(double v) {
         }                                                                                \
     }
 
-template <int NPL, bool RNG, bool HOLD, bool GUIDED = false>
+template <int NPL, bool RNG, bool HOLD, bool GUIDED = false, bool PURITY = false>
 __device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const SampleRng& g, const SampleHold& h,
-                                                    const SampleGuide& gd = SampleGuide{nullptr, 1.f}) {
+                                                    const SampleGuide& gd = SampleGuide{nullptr, 1.f},
+                                                    const SamplePurity& pu = SamplePurity{nullptr, nullptr, nullptr, 0.f}) {
     constexpr int K = NPL * 64;
     __shared__ float s_lp[4][K];
     __shared__ __attribute__((aligned(16))) float s_pr[4][K];
@@ -327,6 +343,41 @@ __device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const
         if (lane == 0) p.dbg_trunc[dbg_base + (size_t)K * p.L] = -70.f;
     }
 
+    float post[NPL];
+    float post_m;
+    [[maybe_unused]] float lmax = 0.f;
+    if constexpr (PURITY) {
+        // ---- purity and sharpening: `post` becomes sh, the distribution the candidate is drawn from ----
+        lmax = lp[0];
+#pragma unroll
+        for (int j = 1; j < NPL; ++j) lmax = fmaxf(lmax, lp[j]);
+        lmax = wmaxf(lmax);
+        if (pu.weight > 0.f) {
+            const double a = (double)(1.f + pu.weight * expf(lmax));
+            double av[NPL];
+#pragma unroll
+            for (int j = 0; j < NPL; ++j) av[j] = a * (double)tr[j];
+            double am = av[0];
+#pragma unroll
+            for (int j = 1; j < NPL; ++j) am = fmax(am, av[j]);
+            am = wmaxd(am);
+            double as = 0.0;
+#pragma unroll
+            for (int j = 0; j < NPL; ++j) as += exp(av[j] - am);
+            const double alse = log(wsumd(as));
+#pragma unroll
+            for (int j = 0; j < NPL; ++j) post[j] = fminf(fmaxf((float)((av[j] - am) - alse), -70.f), 0.f);
+        } else {
+#pragma unroll
+            for (int j = 0; j < NPL; ++j) post[j] = tr[j];
+        }
+        post_m = -70.f;                  // (dumped only: the [MASK] class is no candidate)
+        if (pu.dbg_sharp && live) {
+#pragma unroll
+            for (int j = 0; j < NPL; ++j) pu.dbg_sharp[dbg_base + (size_t)(j * 64 + lane) * p.L] = post[j];
+            if (lane == 0) pu.dbg_sharp[dbg_base + (size_t)K * p.L] = post_m;
+        }
+    } else {
     // ---- q_posterior ----
     const int T1 = p.T + 1;
     const int t = (int)p.t[b];
@@ -362,7 +413,6 @@ __device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const
     es = wsumf(es) + expf(q_m - qmax);
     const float lse = logf(es) + qmax;  // torch.logsumexp
 
-    float post[NPL];
 #pragma unroll
     for (int j = 0; j < NPL; ++j) {
         const int c = j * 64 + lane;
@@ -370,7 +420,6 @@ __device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const
         const float o = ev + (c == xt ? q1_hit : q1_off) + lse;
         post[j] = fminf(fmaxf(o, -70.f), 0.f);
     }
-    float post_m;
     {
         const float ev = lae((q_m - lse) + l1mcct1, lcct1);
         post_m = fminf(fmaxf(ev + q1_m + lse, -70.f), 0.f);
@@ -379,6 +428,7 @@ __device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const
 #pragma unroll
         for (int j = 0; j < NPL; ++j) p.dbg_post[dbg_base + (size_t)(j * 64 + lane) * p.L] = post[j];
         if (lane == 0) p.dbg_post[dbg_base + (size_t)K * p.L] = post_m;
+    }
     }
 
     // ---- Gumbel-argmax (first index wins ties, as torch.argmax) ----
@@ -406,7 +456,7 @@ __device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const
         const float gsc = -logf(-logf(un[j] + 1e-30f) + 1e-30f) + post[j];
         if (gsc > best) { best = gsc; bidx = c; }  // ascending c within a lane keeps the first max
     }
-    if (lane == 0) {
+    if (!PURITY && lane == 0) {
         const float gsc = -logf(-logf(un_m + 1e-30f) + 1e-30f) + post_m;
         if (gsc > best) { best = gsc; bidx = K; }
     }
@@ -416,7 +466,12 @@ __device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const
         const int oi = __shfl_xor(bidx, o);
         if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
     }
-    if (lane == 0 && live) p.out_tokens[col] = bidx;
+    if constexpr (PURITY) {
+        if (lane == 0 && live) {
+            pu.cand[col] = bidx;
+            pu.key[col] = (int)p.xt[col] == K ? lmax + -logf(-logf(un_m + 1e-30f) + 1e-30f) : -INFINITY;
+        }
+    } else if (lane == 0 && live) p.out_tokens[col] = bidx;
 }
 
 template <int NPL, bool RNG>
@@ -434,6 +489,52 @@ template <int NPL, bool RNG>
 __global__ __launch_bounds__(256) void ds_sample_tail_guided_kernel(const SampleParams p, const SampleRng g, const SampleHold h,
                                                                     const SampleGuide gd) {
     ds_sample_tail_body<NPL, RNG, true, true>(p, g, h, gd);
+}
+
+// steps 1-5 of a purity step (see SamplePurity): one wave per grid position -> (candidate, key) in the caller's scratch
+template <int NPL, bool RNG, bool GUIDED>
+__global__ __launch_bounds__(256) void ds_sample_purity_rows_kernel(const SampleParams p, const SampleRng g, const SampleGuide gd,
+                                                                    const SamplePurity pu) {
+    ds_sample_tail_body<NPL, RNG, false, GUIDED, true>(p, g, SampleHold{nullptr, nullptr, 0}, gd, pu);
+}
+
+// step 6: one workgroup per sample.  m = its [MASK] positions, n = max(0, m - remain); the n masked positions of largest key
+// take their candidate, every other position keeps its token.  Rank by counting over the keys in LDS -- position i is revealed
+// iff #{j : key_j > key_i or (key_j == key_i and j < i)} < n (a non-[MASK] j carries -INFINITY and never counts against a
+// finite key) -- so the result depends on no order of execution: no atomics, no data-dependent launch.
+#define DS_PURITY_MAX_L 288
+__global__ __launch_bounds__(256) void ds_sample_purity_select_kernel(const int64_t* __restrict__ xt, const int* __restrict__ cand,
+                                                                      const float* __restrict__ key, int64_t* __restrict__ out,
+                                                                      int L, int K, int remain) {
+    __shared__ float s_k[DS_PURITY_MAX_L];
+    __shared__ int s_cnt[4];
+    const int tid = threadIdx.x;
+    const size_t base = (size_t)blockIdx.x * L;
+    int mine = 0;
+    for (int i = tid; i < L; i += 256) {
+        s_k[i] = key[base + i];
+        mine += (int)xt[base + i] == K ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
+    if ((tid & 63) == 0) s_cnt[tid >> 6] = mine;
+    __syncthreads();
+    const int m = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    const int n = m > remain ? m - remain : 0;
+    for (int i = tid; i < L; i += 256) {
+        const int64_t x = xt[base + i];
+        bool reveal = false;
+        if ((int)x == K && n > 0) {
+            const float ki = s_k[i];
+            int rank = 0;
+            for (int j = 0; j < L; ++j) {
+                const float kj = s_k[j];
+                rank += (kj > ki || (kj == ki && j < i)) ? 1 : 0;
+            }
+            reveal = rank < n;
+        }
+        out[base + i] = reveal ? (int64_t)cand[base + i] : x;
+    }
 }
 
 // ---- training-loss terms (DiffusionTransformer._train_loss, diffusion_transformer.py:408-476), forward only ----
@@ -925,4 +1026,85 @@ extern "C" int ds_sample_tail(const float* logits, const int64_t* xt, const int6
                               ds_stream_t stream) {
     return ds_sample_tail_ex(logits, xt, t, u, sched, out_tokens, dbg_log_pred, dbg_trunc, dbg_post, B, L, K, T, initial,
                              trunc_r, 0, stream);
+}
+
+// ---- purity-prior tails (see SamplePurity): the argument rules, and the two launches.  `who`: the public entry the messages name.
+int ds_sample_tail_purity_check(const char* who, bool pointers, bool guided, float scale, int remain, float weight, float trunc_r,
+                                int trunc_k, int logits_rows, int L, int K) {
+    const char* msg = !pointers                                        ? "null pointer"
+                      : !(K == 256 || K == 512)                        ? "codebook size must be 256 or 512"
+                      : !(L > 0 && L <= DS_PURITY_MAX_L)               ? "L must be in 1 .. 288"
+                      : logits_rows < L                                ? "logits rows per sample"
+                      : remain < 0                                     ? "remain must be >= 0"
+                      : !(weight >= 0.f && weight - weight == 0.f)     ? "the purity weight must be finite and >= 0"
+                      : (guided && !(scale - scale == 0.f))            ? "the guidance scale must be finite"
+                      : !(trunc_k >= 0 && !(trunc_k > 0 && trunc_r >= 0.f)) ? "top-k and top-r truncation are exclusive"
+                                                                       : nullptr;
+    if (!msg) return 0;
+    ds_set_error("%s: %s", who, msg);
+    return -1;
+}
+
+extern "C" int64_t ds_purity_scratch_bytes(int B, int L) {
+    return B > 0 && L > 0 ? (int64_t)B * L * (int64_t)(sizeof(int) + sizeof(float)) : -1;
+}
+
+int ds_sample_tail_purity_rows(const char* who, const float* logits, const float* logits_u, float scale, int logits_rows,
+                               const int64_t* xt, const float* u, const int64_t* gids, unsigned long long seed, int call,
+                               int remain, float weight, float trunc_r, int trunc_k, void* scratch, int64_t* out_tokens,
+                               float* dbg_sharp, float* dbg_key, int32_t* dbg_cand, int B, int L, int K, ds_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (ds_sample_tail_purity_check(who, logits && xt && (u || gids) && scratch && out_tokens && B > 0, logits_u != nullptr, scale,
+                                    remain, weight, trunc_r, trunc_k, logits_rows, L, K))
+        return -1;
+    const size_t cols = (size_t)B * L;
+    int* cand = (int*)scratch;
+    float* key = (float*)(cand + cols);
+    SampleParams p{logits, xt, nullptr, u, nullptr, nullptr, nullptr, nullptr, nullptr, B, L, 0, 0, trunc_r, trunc_k, logits_rows};
+    const SampleRng g{gids, (unsigned)seed, (unsigned)(seed >> 32), call};
+    const SampleGuide gd{logits_u, scale};
+    const SamplePurity pu{cand, key, dbg_sharp, weight};
+    const dim3 grid((unsigned)((cols + 3) / 4));
+#define DS_PURITY_LAUNCH(NPL_, RNG_)                                                                                                \
+    do {                                                                                                                            \
+        if (logits_u) hipLaunchKernelGGL((ds_sample_purity_rows_kernel<NPL_, RNG_, true>), grid, dim3(256), 0, stream, p, g, gd, pu); \
+        else hipLaunchKernelGGL((ds_sample_purity_rows_kernel<NPL_, RNG_, false>), grid, dim3(256), 0, stream, p, g, gd, pu);         \
+    } while (0)
+    if (K == 256 && u) DS_PURITY_LAUNCH(4, false);
+    else if (K == 256) DS_PURITY_LAUNCH(4, true);
+    else if (u) DS_PURITY_LAUNCH(8, false);
+    else DS_PURITY_LAUNCH(8, true);
+#undef DS_PURITY_LAUNCH
+    DS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(ds_sample_purity_select_kernel, dim3(B), dim3(256), 0, stream, xt, (const int*)cand, (const float*)key,
+                       out_tokens, L, K, remain);
+    DS_CHECK_LAUNCH();
+    if (dbg_key || dbg_cand) {
+        hipError_t e = dbg_key ? hipMemcpyAsync(dbg_key, key, cols * sizeof(float), hipMemcpyDeviceToDevice, stream) : hipSuccess;
+        if (e == hipSuccess && dbg_cand) e = hipMemcpyAsync(dbg_cand, cand, cols * sizeof(int), hipMemcpyDeviceToDevice, stream);
+        if (e != hipSuccess) {
+            ds_set_error("%s: hipMemcpyAsync: %s", who, hipGetErrorString(e));
+            return -2;
+        }
+    }
+    return 0;
+}
+
+extern "C" int ds_sample_tail_purity(const float* logits, const float* logits_u, float scale, const int64_t* xt, const float* u,
+                                     int remain, float weight, float trunc_r, int trunc_k, int lrows, void* scratch,
+                                     int64_t* out_tokens, float* dbg_sharp, float* dbg_key, int32_t* dbg_cand, int B, int L,
+                                     int K, ds_stream_t stream) {
+    DS_CHECK_ARG(u, "null pointer");
+    return ds_sample_tail_purity_rows(__func__, logits, logits_u, scale, lrows, xt, u, nullptr, 0ull, 0, remain, weight, trunc_r,
+                                      trunc_k, scratch, out_tokens, dbg_sharp, dbg_key, dbg_cand, B, L, K, stream);
+}
+
+extern "C" int ds_sample_tail_purity_rng(const float* logits, const float* logits_u, float scale, const int64_t* xt,
+                                         const int64_t* gids, unsigned long long seed, int call, int remain, float weight,
+                                         float trunc_r, int trunc_k, int lrows, void* scratch, int64_t* out_tokens,
+                                         float* dbg_sharp, float* dbg_key, int32_t* dbg_cand, int B, int L, int K,
+                                         ds_stream_t stream) {
+    DS_CHECK_ARG(gids, "null pointer");
+    return ds_sample_tail_purity_rows(__func__, logits, logits_u, scale, lrows, xt, nullptr, gids, seed, call, remain, weight,
+                                      trunc_r, trunc_k, scratch, out_tokens, dbg_sharp, dbg_key, dbg_cand, B, L, K, stream);
 }

@@ -162,6 +162,29 @@ class DALLE(nn.Module):
         return parts
 
     @staticmethod
+    def _purity_part(sample_type, keep_mode="clamp"):
+        """The purity part of a sample type (not in the reference): ",purity{S}" or ",purity{S}w{r}" -- an S-step purity-prior
+        chain (DiffusionTransformer.sample_purity), r = the sharpening weight (default 0) -> (S, r), or None without one.
+        Together with ",fast{n}", ",q{rate}" or keep_mode "renoise" it raises ValueError: before anything is installed or run."""
+        parts = sample_type.split(",")
+        pur = [q for q in parts[1:] if q[:6] == "purity"]
+        if not pur:
+            return None
+        if len(pur) > 1:
+            raise ValueError("one purity part per sample type, got %r" % (sample_type,))
+        for q in parts[1:]:
+            if q[:4] == "fast" or q[:1] == "q":
+                raise ValueError("purity sampling has its own chain: %r cannot be combined with it (%r)" % (q, sample_type))
+        if keep_mode != "clamp":
+            raise ValueError("purity sampling holds positions clean: keep_mode=%r cannot be combined with it" % (keep_mode,))
+        body = pur[0][6:]
+        try:
+            steps, sep, weight = body.partition("w")
+            return int(steps), (float(weight) if sep else 0.0)
+        except ValueError:
+            raise ValueError("a purity part is 'purity{S}' or 'purity{S}w{r}', got %r" % (pur[0],)) from None
+
+    @staticmethod
     def _replicated_caption_ids(batch, replicate):
         ids = torch.as_tensor(batch["caption_ids"], dtype=torch.long)
         return torch.cat([ids for _ in range(replicate)]) + \
@@ -180,8 +203,9 @@ class DALLE(nn.Module):
 
     def _run_chain(self, batch, condition, kw, replicate, sample_type, guidance_scale):
         """What generate_content, inpaint_content and generate_long_content share once the chain's own keywords `kw` are set:
-        install the sample type, add the (replicated) condition, the guidance and the noise keywords of `batch`, run sample() or
-        sample_fast() -> tokens i64[B r, 265]."""
+        install the sample type, add the (replicated) condition, the guidance and the noise keywords of `batch`, run sample(),
+        sample_fast() or -- for a sample type with a ",purity{S}" part (_purity_part) -- sample_purity() -> tokens i64[B r, 265]."""
+        purity = self._purity_part(sample_type, kw.get("keep_mode", "clamp"))
         parts = self._install_sample_type(sample_type)
         tr = self.transformer
         kw = dict(kw, condition_token=condition.get("condition_token"), condition_mask=condition.get("condition_mask"),
@@ -191,6 +215,8 @@ class DALLE(nn.Module):
             kw["caption_ids"] = self._replicated_caption_ids(batch, replicate)
         if batch.get("seed") is not None:
             kw["seed"] = int(batch["seed"])
+        if purity is not None:                               # purity-prior chain: ",purity{S}" / ",purity{S}w{r}"
+            return tr.sample_purity(steps=purity[0], purity_weight=purity[1], **kw)["content_token"]
         if len(parts) == 2 and parts[1][:4] == "fast":       # skip-step sampler (:211-222)
             return tr.sample_fast(skip_step=int(parts[1][4:]), **kw)["content_token"]
         return tr.sample(**kw)["content_token"]
@@ -233,7 +259,9 @@ class DALLE(nn.Module):
                          replicate=1, return_att_weight=False, sample_type="top0.85r", guidance_scale=None):
         """guidance_scale (not in the reference): classifier-free guidance of every sampler step against the null condition
         -- the empty caption, or batch['negative_text'] (a caption or a list of B) -- see DiffusionTransformer.sample and
-        null_condition; None or exactly 1 is the unguided path."""
+        null_condition; None or exactly 1 is the unguided path.
+        sample_type (beyond the reference's forms): a ",purity{S}" or ",purity{S}w{r}" part, e.g. "top0.85r,purity25", runs an
+        S-step purity-prior chain instead (_purity_part, DiffusionTransformer.sample_purity; filter_ratio must resolve to 0)."""
         self.eval()
         condition = self.prepare_condition(batch=batch, condition=condition)
         if replicate != 1:
@@ -274,6 +302,7 @@ class DALLE(nn.Module):
         if ids.numel() != B:
             raise ValueError("%d caption ids for %d captions" % (ids.numel(), B))
         window_caption_ids(ids, windows - 1)                  # the range check, before anything runs
+        self._purity_part(sample_type, keep_mode)             # ... and the purity part's rules (window 0 holds nothing)
         tr = self.transformer
         saved = tr.truncation_r, tr.truncation_k, tr.repeat_rate, self.truncation_forward
         self.truncation_forward = False                       # install THIS call's sample type

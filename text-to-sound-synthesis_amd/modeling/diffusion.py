@@ -31,6 +31,34 @@ def alpha_schedule(time_step, N=100, att_1=0.99999, att_T=0.000009, ctt_1=0.0000
     return at, bt, ct, att, btt, ctt
 
 
+def purity_plan(S, L, log_cumprod_ct):
+    """The host-side plan of an S-step purity chain over a grid of L positions: [(t_k, R_k)], k = 0 .. S-1.
+    R_k = floor((S-1-k) L / S) is the number of [MASK] positions a sample may still have after step k (R_{S-1} = 0; the reveal
+    counts R_{k-1} - R_k differ by at most one).  t_k, the timestep the network is told, is the one at which the forward process
+    has masked, in expectation, the share of the grid that is still masked: argmin_t |exp(log_cumprod_ct[t]) - R_{k-1} / L|
+    with R_{-1} = L, ties to the larger t, forced non-increasing, t_0 = T - 1.  log_cumprod_ct: the model's buffer of T + 1
+    entries (tensor, array or list); entry T is the wrap-around slot of t = -1, not a timestep, and is not searched.
+    1 <= S <= L, else ValueError.  Pure host arithmetic in float64."""
+    S, L = int(S), int(L)
+    if S < 1:
+        raise ValueError("a purity chain has at least one step, got S = %d" % S)
+    if S > L:
+        raise ValueError("a purity chain reveals at least one position per step: S = %d exceeds the %d grid positions" % (S, L))
+    lc = log_cumprod_ct.detach().cpu().numpy() if torch.is_tensor(log_cumprod_ct) else log_cumprod_ct
+    gamma = np.exp(np.asarray(lc, dtype=np.float64).reshape(-1)[:-1])
+    T = gamma.shape[0]
+    if T < 1:
+        raise ValueError("log_cumprod_ct must have T + 1 entries with T >= 1")
+    plan, prev_r, prev_t = [], L, T - 1
+    for k in range(S):
+        d = np.abs(gamma - prev_r / L)
+        t = T - 1 if k == 0 else min(prev_t, int(np.nonzero(d == d.min())[0].max()))
+        r = ((S - 1 - k) * L) // S
+        plan.append((t, r))
+        prev_r, prev_t = r, t
+    return plan
+
+
 def _log_1_min_a(a):
     return torch.log(1 - a.exp() + 1e-40)
 
@@ -436,20 +464,24 @@ class DiffusionTransformer(nn.Module):
         """_reverse_once under the denoiser's range guard (Text2ImageTransformer.range_exceeded): a chain during which FC2's
         split operand saturated is run again from its start in the fp32 mode, with the state of Python's `random` (the repeat
         sampler) and of the device's generator (the torch.rand noise) put back first; the Philox noise needs neither."""
+        return self._guarded(self._reverse_once, *args, **kwargs)
+
+    def _guarded(self, chain, *args, **kwargs):
+        """chain(*args, **kwargs) under the range guard described in _reverse"""
         import random
         tr = self.transformer
         tr.packed(self._schedule_table())
         if tr._packed.get("range_peak") is None:
-            return self._reverse_once(*args, **kwargs)
+            return chain(*args, **kwargs)
         state, gen = random.getstate(), torch.cuda.get_rng_state(self.device)
         tr.range_exceeded()                                 # clear what earlier calls left
-        out = self._reverse_once(*args, **kwargs)
+        out = chain(*args, **kwargs)
         if not tr.range_exceeded():
             return out
         random.setstate(state)
         torch.cuda.set_rng_state(gen, self.device)
         with tr.strict_mode():
-            return self._reverse_once(*args, **kwargs)
+            return chain(*args, **kwargs)
 
     def _reverse_once(self, cond_emb, steps, noise_fn, return_logits, start_tokens=None, caption_ids=None, seed=None, hold=None,
                       guide=None):
@@ -626,3 +658,93 @@ class DiffusionTransformer(nn.Module):
                                  return_logits, start_tokens=x, caption_ids=caption_ids, seed=seed, hold=hold, guide=guide)
         finally:
             self.repeat_rate = keep
+
+    # ---- purity-prior sampling (csrc/sampler.hip SamplePurity) ---------------------------------------------
+    def _purity_check(self, steps, purity_weight, keep_mode, filter_ratio):
+        """The argument rules of sample_purity, before anything is enqueued -> (S, weight)."""
+        if keep_mode != "clamp":
+            raise ValueError("purity sampling holds positions clean (keep_mode='clamp'): a revealed token is never re-drawn, "
+                             "so keep_mode=%r does not exist here" % (keep_mode,))
+        if self.repeat_rate is not None:
+            raise ValueError("the repeat sampler (',q{rate}') re-applies a posterior step: not with purity sampling")
+        if int(self.num_timesteps * filter_ratio) != 0:
+            raise ValueError("purity sampling generates from [MASK]: filter_ratio must resolve to step 0")
+        S = self.num_timesteps if steps is None else int(steps)
+        w = float(purity_weight)
+        if not (w >= 0.0 and w != float("inf")):
+            raise ValueError("purity_weight must be finite and >= 0, got %r" % (purity_weight,))
+        if not 1 <= S <= self.content_seq_len:
+            raise ValueError("steps must be in 1 .. %d (a step reveals at least one position), got %r" % (self.content_seq_len, steps))
+        return S, w
+
+    def _purity_once(self, cond_emb, plan, weight, noise_fn, return_logits, start_tokens=None, caption_ids=None, seed=None,
+                     guide=None):
+        """The purity chain of `plan` (purity_plan).  In-kernel noise: one C call (ds_denoiser_sample_purity_rng), nothing
+        returns to Python between steps; caller noise: noise_fn(k, shape) per call k, or torch.rand."""
+        import ctypes
+        device = self.device
+        B, K1, L = cond_emb.shape[0], self.num_classes, self.content_seq_len
+        cond_emb = cond_emb.to(device)
+        x = torch.full((B, L), K1 - 1, device=device, dtype=torch.long) if start_tokens is None else start_tokens.to(device).clone()
+        sched = self._schedule_table()
+        tr = self.transformer
+        p = tr.packed(sched)
+        lib = _lib.lib()
+        r, k = self._truncation()
+        scratch = torch.empty(int(lib.ds_purity_scratch_bytes(B, L)), device=device, dtype=torch.uint8)
+        tmp = torch.empty_like(x)
+        if guide is not None:
+            kv, scale, tokens2 = self._guide_start(guide, cond_emb, sched)
+            Bf = 2 * B
+        else:
+            kv, scale, tokens2, Bf = tr.condition_kv(cond_emb.contiguous(), sched), 1.0, None, B
+        ws = tr.workspace(Bf, sched, 0)
+        if noise_fn is None and (caption_ids is not None or self.rng_mode == "philox"):
+            gids = self._caption_ids(caption_ids, B, device)
+            t_steps = torch.tensor([t for t, _ in plan], dtype=torch.long, device=device).view(-1, 1).expand(-1, Bf).contiguous()
+            remain = (ctypes.c_int * len(plan))(*[rk for _, rk in plan])
+            _lib.check(lib.ds_denoiser_sample_purity_rng(
+                p["handle"], _lib.ptr(x), _lib.ptr(tmp), _lib.ptr(t_steps), remain, len(plan), _lib.ptr(kv), _lib.ptr(gids),
+                int(self.sample_seed if seed is None else seed), 0, B, weight, r, k, float(scale), _lib.ptr(tokens2),
+                _lib.ptr(ws), _lib.ptr(scratch), _lib.stream()))
+        else:
+            for call, (t_k, r_k) in enumerate(plan):
+                u = (noise_fn(call, (B, K1, L)).to(device) if noise_fn is not None else torch.rand((B, K1, L), device=device))
+                u = u.contiguous()
+                t = torch.full((Bf,), t_k, device=device, dtype=torch.long)
+                _lib.check(lib.ds_denoiser_step_purity(
+                    p["handle"], _lib.ptr(x), _lib.ptr(t), _lib.ptr(kv), _lib.ptr(u), B, int(r_k), weight, r, k, float(scale),
+                    _lib.ptr(tokens2), _lib.ptr(ws), _lib.ptr(scratch), _lib.ptr(tmp), _lib.stream()))
+                x, tmp = tmp, x
+        out = {"content_token": x}
+        if return_logits:
+            out["logits"] = torch.nn.functional.one_hot(x, K1).permute(0, 2, 1).float()
+        return out
+
+    @torch.no_grad()
+    def sample_purity(self, condition_token, condition_mask, condition_embed, content_token=None, filter_ratio=0,
+                      temperature=1.0, return_att_weight=False, return_logits=False, content_logits=None, print_log=True,
+                      steps=None, purity_weight=0.0, noise_fn=None, caption_ids=None, seed=None, keep_mask=None,
+                      keep_mode="clamp", guidance_scale=None, null_condition_embed=None, **kwargs):
+        """Purity-prior sampling (not in the reference; the high-quality inference strategy of Tang et al. 2022, specified in
+        DESIGN.md section 4): a chain of `steps` = S denoiser forwards (1 <= S <= 265, default T) from the all-[MASK] state.
+        Step k reveals exactly R_{k-1} - R_k positions per sample (purity_plan) -- those where the predicted x0 distribution
+        is most certain, drawn without replacement in proportion to their purity -- with a token drawn from the truncated
+        prediction, sharpened by purity_weight r >= 0 (exponent 1 + r purity; 0: not sharpened).  A revealed token is never
+        re-sampled, and the chain ends with no [MASK] at any S.  No posterior is involved; the timestep only tells the
+        network how much of the grid is still masked.
+
+        keep_mask / content_token: region-held sampling -- the held positions enter as their known tokens, i.e. as already
+        revealed, and come out bit-exact (clamp mode only: keep_mode='renoise' raises ValueError, as do the ',q{rate}'
+        repeat sampler and a filter_ratio that does not resolve to step 0).  guidance_scale / null_condition_embed,
+        caption_ids / seed as in sample(); noise_fn(k, shape) gets the call index k = 0 .. S-1.  What this sampler does to
+        audio quality is unmeasured: no trained checkpoint has been available to this project."""
+        S, weight = self._purity_check(steps, purity_weight, keep_mode, filter_ratio)
+        cond_emb = self._cond(condition_token, condition_embed)
+        guide = self._guide(guidance_scale, null_condition_embed, cond_emb)
+        x = None
+        if keep_mask is not None:
+            _, x, _ = self._hold_start(keep_mask, "clamp", content_token, cond_emb.shape[0], noise_fn, caption_ids, seed)
+        plan = purity_plan(S, self.content_seq_len, self.log_cumprod_ct)
+        return self._guarded(self._purity_once, cond_emb, plan, weight, noise_fn, return_logits, start_tokens=x,
+                             caption_ids=caption_ids, seed=seed, guide=guide)

@@ -146,6 +146,15 @@ def window_caption_ids(caption_ids, window):
     return ids + int(window) * WINDOW_ID_STRIDE
 
 
+def purity_sample_type(sample_type, purity_steps, purity_weight=0.0):
+    """sample_type + the ",purity{S}" / ",purity{S}w{r}" part the drivers' purity_steps / purity_weight keywords stand for
+    (DALLE._purity_part); purity_steps None: sample_type as it is -- purity_weight is not looked at."""
+    if purity_steps is None:
+        return sample_type
+    w = float(purity_weight)
+    return "%s,purity%d%s" % (sample_type, int(purity_steps), "" if w == 0.0 else "w%r" % w)
+
+
 class Diffsound:
     def __init__(self, config=None, path=None, ckpt_vocoder=None, device="cuda", random_vocoder=False):
         """ckpt_vocoder falsy: `self.vocoder = None` and the drivers write `.npy` only, as the reference does (:53-56).
@@ -176,7 +185,8 @@ class Diffsound:
 
     @torch.no_grad()
     def generate_sample_with_condition(self, cond, truncation_rate=0.85, replicate=1, fast=False, caption_ids=None,
-                                       seed=None, sample_rate=None, guidance_scale=None, negative_text=None):
+                                       seed=None, sample_rate=None, guidance_scale=None, negative_text=None, purity_steps=None,
+                                       purity_weight=0.0):
         """Captions -> (mel01 f32[B,80,848], wave f32[B,1,217088] -- None without a vocoder --, tokens), everything left on the GPU.
         `cond` is a list of caption strings (needs the text stage: tokenizer + CLIP in the config),
         token ids i64[B,77], or caption embeddings f32[B,77,512].  fast=n selects the skip-step sampler with
@@ -186,7 +196,10 @@ class Diffsound:
         draws as caption id ids[i] + r * 2^24.  sample_rate: the rate of the returned waveform; another one than 22 050 Hz is the
         vocoder's output resampled on the device (audio.resample): f32[B,1,ceil(217088 sample_rate / 22050)].
         guidance_scale: classifier-free guidance (DALLE.generate_content) against the empty caption or negative_text (a
-        caption, or one per caption); None or 1: unguided."""
+        caption, or one per caption); None or 1: unguided.
+        purity_steps = S: an S-step purity-prior chain instead of the reference's 100-step loop (DiffusionTransformer.
+        sample_purity: 1 <= S <= 265 forwards, confident positions first, no [MASK] left at any S), purity_weight its
+        sharpening weight; None: today's path, untouched.  Not together with fast.  Its effect on audio quality is unmeasured."""
         if isinstance(cond, (list, tuple, str)):
             batch = {"text": [cond] if isinstance(cond, str) else list(cond)}
         elif cond.dtype == torch.long:
@@ -201,7 +214,9 @@ class Diffsound:
             batch["negative_text"] = negative_text
         out = self.model.generate_content(batch=batch, filter_ratio=0, replicate=replicate, content_ratio=1,
                                           return_att_weight=False, guidance_scale=guidance_scale,
-                                          sample_type="top" + str(truncation_rate) + ("r,fast" + str(fast - 1) if fast else "r"))
+                                          sample_type=purity_sample_type(
+                                              "top" + str(truncation_rate) + ("r,fast" + str(fast - 1) if fast else "r"),
+                                              purity_steps, purity_weight))
         mel = out["content"]                                   # [B,1,80,848] in ~[-1,1]
         wave = None if self.vocoder is None else self.vocoder(mel[:, 0], scale=0.5, shift=0.5)   # spec = (x+1)/2, :182
         return (mel[:, 0] + 1) / 2, self._at_rate(wave, sample_rate), out["content_token"]
@@ -261,7 +276,7 @@ class Diffsound:
         return {"condition_token": text} if text.dtype == torch.long else {"condition_embed_token": text}
 
     def _inpaint_tokens(self, tokens, keep, text, keep_mode, truncation_rate, caption_ids, seed, guidance_scale=None,
-                        negative_text=None):
+                        negative_text=None, purity_steps=None, purity_weight=0.0):
         """DALLE.inpaint_content at this call's truncation rate (the facade installs a rate once and keeps it: set and
         restored around the call, like generate_sample_from_audio does)."""
         batch = dict(self._caption_batch(text), content_token=tokens)
@@ -276,20 +291,23 @@ class Diffsound:
         tr.truncation_r, tr.truncation_k, model.truncation_forward = float(truncation_rate), None, True
         try:
             out = model.inpaint_content(batch=batch, keep_mask=keep, keep_mode=keep_mode, guidance_scale=guidance_scale,
-                                        sample_type="top" + str(truncation_rate) + "r")
+                                        sample_type=purity_sample_type("top" + str(truncation_rate) + "r", purity_steps,
+                                                                       purity_weight))
         finally:
             tr.truncation_r, tr.truncation_k, tr.repeat_rate, model.truncation_forward = saved
         return out["content_token"]
 
     @torch.no_grad()
     def inpaint_audio(self, audio, text, spans, keep_mode="clamp", truncation_rate=0.85, save_root=None, audio_rate=None,
-                      caption_ids=None, seed=None, sample_rate=None, guidance_scale=None, negative_text=None):
+                      caption_ids=None, seed=None, sample_rate=None, guidance_scale=None, negative_text=None, purity_steps=None,
+                      purity_weight=0.0):
         """Regenerate time spans of given recordings under a caption and keep the rest: audio / audio_rate / text as in
         generate_sample_from_audio; spans = the (t0, t1) seconds to regenerate, shared or one list per clip
         (spans_to_keep_mask: whole grid columns of 4096 samples at 22 050 Hz).  The recording is encoded to its 5 x 53 tokens,
         the tokens outside the spans are held through the whole reverse chain (keep_mode "clamp": clean; "renoise": following
         the forward process, per-caption in-kernel noise) and the spans are generated from [MASK] with them as context.
-        caption_ids / seed / sample_rate / guidance_scale / negative_text as in generate_sample_with_condition.  Returns
+        caption_ids / seed / sample_rate / guidance_scale / negative_text / purity_steps / purity_weight as in
+        generate_sample_with_condition (a purity chain holds positions clean: keep_mode "clamp" only).  Returns
         (mel01, wave or None, tokens) and writes the files generate_sample_from_audio writes.
 
         What is kept is the TOKENS: exact.  The returned audio is the codec's and the vocoder's rendering everywhere -- the
@@ -299,12 +317,13 @@ class Diffsound:
         known = content["content_token"]
         keep = spans_to_keep_mask(spans, known.shape[0], known.device)
         tokens = self._inpaint_tokens(known, keep, text, keep_mode, truncation_rate, caption_ids, seed, guidance_scale,
-                                      negative_text)
+                                      negative_text, purity_steps, purity_weight)
         return self._render(tokens, content["content_quant"].shape, save_root, sample_rate)
 
     @torch.no_grad()
     def continue_audio(self, audio, text, keep_seconds, keep_mode="clamp", truncation_rate=0.85, save_root=None,
-                       audio_rate=None, caption_ids=None, seed=None, sample_rate=None, guidance_scale=None, negative_text=None):
+                       audio_rate=None, caption_ids=None, seed=None, sample_rate=None, guidance_scale=None, negative_text=None,
+                       purity_steps=None, purity_weight=0.0):
         """Generate the clip that follows given recordings: the last ceil(keep_seconds 22050 / 4096) token columns of the
         recording become the first columns of a new 10-s clip (a shift by 5 (53 - n) tokens), held, and the remaining columns
         are generated under `text`.  Arguments and return as inpaint_audio.  The new clip's head is the codec's rendering of
@@ -313,11 +332,11 @@ class Diffsound:
         content = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})
         known, keep = continuation_tokens(content["content_token"], continuation_columns(keep_seconds))
         tokens = self._inpaint_tokens(known, keep, text, keep_mode, truncation_rate, caption_ids, seed, guidance_scale,
-                                      negative_text)
+                                      negative_text, purity_steps, purity_weight)
         return self._render(tokens, content["content_quant"].shape, save_root, sample_rate)
 
     def _long_tokens(self, text, windows, overlap_cols, keep_mode, truncation_rate, caption_ids, seed,
-                     guidance_scale, negative_text, start_token=None):
+                     guidance_scale, negative_text, start_token=None, purity_steps=None, purity_weight=0.0):
         """DALLE.generate_long_content under this call's caption / noise keywords (the truncation rate is the call's: the
         facade saves and restores the model's own)."""
         batch = dict(self._caption_batch(text))
@@ -328,8 +347,9 @@ class Diffsound:
         if negative_text is not None:
             batch["negative_text"] = negative_text
         return self.model.generate_long_content(batch=batch, windows=windows, overlap_cols=overlap_cols, keep_mode=keep_mode,
-                                                sample_type="top" + str(truncation_rate) + "r", guidance_scale=guidance_scale,
-                                                start_token=start_token)
+                                                sample_type=purity_sample_type("top" + str(truncation_rate) + "r", purity_steps,
+                                                                               purity_weight),
+                                                guidance_scale=guidance_scale, start_token=start_token)
 
     VOCODER_CHUNK_FRAMES = 64 * 848       # mel frames per vocoder call of a long clip: the largest call the benchmarks run
 
@@ -360,7 +380,8 @@ class Diffsound:
 
     @torch.no_grad()
     def generate_long(self, text, seconds, overlap_seconds=2.4, truncation_rate=0.85, keep_mode="clamp", caption_ids=None,
-                      seed=None, sample_rate=None, guidance_scale=None, negative_text=None, save_root=None):
+                      seed=None, sample_rate=None, guidance_scale=None, negative_text=None, save_root=None, purity_steps=None,
+                      purity_weight=0.0):
         """Captions -> clips of `seconds` (up to 16 windows, about two minutes): (mel01 f32[B, 80, ceil(samples / 256)], wave
         f32[B, 1, samples] -- None without a vocoder --, tokens i64[B, W, 265]), samples = round(seconds 22050).  The clip is
         generated as W overlapping windows of one 5 x 53 grid each (long_plan): window 0 like generate_sample_with_condition
@@ -370,16 +391,19 @@ class Diffsound:
         windows are decoded in one batch; their mels are cross-faded over the shared frames on the device (audio.stitch_mel)
         and the vocoder renders the whole long mel at once, so the waveform has no seam of its own -- it reflects only at the
         clip's two ends, and the far end's reflection is cut away with the frames past `samples`.  sample_rate / save_root as
-        in the other drivers.  seconds up to one grid (217 088 samples): W = 1, the same path without a held chain.
+        in the other drivers; purity_steps / purity_weight: every window's chain is a purity-prior chain
+        (generate_sample_with_condition; keep_mode "clamp" only).  seconds up to one grid (217 088 samples): W = 1, the same path without a held chain.
 
         The overlap is a design choice whose audible quality is unmeasured (long_plan)."""
         windows, n, _, samples = long_plan(seconds, overlap_seconds)
-        out = self._long_tokens(text, windows, n, keep_mode, truncation_rate, caption_ids, seed, guidance_scale, negative_text)
+        out = self._long_tokens(text, windows, n, keep_mode, truncation_rate, caption_ids, seed, guidance_scale, negative_text,
+                                purity_steps=purity_steps, purity_weight=purity_weight)
         return self._render_long(out, windows, n, samples, save_root, sample_rate)
 
     @torch.no_grad()
     def extend_audio(self, audio, text, seconds, overlap_seconds=2.4, truncation_rate=0.85, keep_mode="clamp", caption_ids=None,
-                     seed=None, sample_rate=None, guidance_scale=None, negative_text=None, save_root=None, audio_rate=None):
+                     seed=None, sample_rate=None, guidance_scale=None, negative_text=None, save_root=None, audio_rate=None,
+                     purity_steps=None, purity_weight=0.0):
         """Extend given recordings to `seconds` in total (more than one grid, 217 088 / 22 050 s): audio / audio_rate as in
         continue_audio; the recording is encoded to its 5 x 53 tokens, which become window 0, and the windows after it are
         generated under `text` as in generate_long.  Returns what generate_long returns; tokens[:, 0] are the recording's.
@@ -391,12 +415,12 @@ class Diffsound:
                              % (CLIP_SAMPLES, VOCODER_RATE, seconds))
         start = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})["content_token"]
         out = self._long_tokens(text, windows, n, keep_mode, truncation_rate, caption_ids, seed, guidance_scale, negative_text,
-                                start_token=start)
+                                start_token=start, purity_steps=purity_steps, purity_weight=purity_weight)
         return self._render_long(out, windows, n, samples, save_root, sample_rate)
 
     @torch.no_grad()
     def inference_generate_sample_with_condition(self, text, truncation_rate, save_root, batch_size, fast=False,
-                                                 guidance_scale=None, negative_text=None):
+                                                 guidance_scale=None, negative_text=None, purity_steps=None, purity_weight=0.0):
         """The reference's single-caption driver, same signature and behaviour (generate_samples_batch.py:89-123):
         ONE caption `text`, sampled `replicate = 10` times (hard-coded there, :111; `batch_size` is accepted and
         unused, as in the reference), results written under `save_root/str(text)/` as `000000`, `000001`, ...
@@ -408,7 +432,8 @@ class Diffsound:
         save_root_ = os.path.join(save_root, str(text))
         os.makedirs(save_root_, exist_ok=True)
         mel01, wave, _ = self.generate_sample_with_condition([text], truncation_rate, replicate=10, fast=fast,
-                                                             guidance_scale=guidance_scale, negative_text=negative_text)
+                                                             guidance_scale=guidance_scale, negative_text=negative_text,
+                                                             purity_steps=purity_steps, purity_weight=purity_weight)
         mel01, wave = mel01.cpu().numpy(), None if wave is None else wave[:, 0].cpu().numpy()
         written = []
         for b in range(mel01.shape[0]):
@@ -431,7 +456,7 @@ class Diffsound:
 
     @torch.no_grad()
     def generate_sample(self, val_path, truncation_rate, save_root, fast=False, replicate=2, sample_rate=None,
-                        guidance_scale=None):
+                        guidance_scale=None, purity_steps=None, purity_weight=0.0):
         """The reference's file-writing driver (generate_samples_batch.py:143-187): per audio file, all of
         its captions x `replicate` are sampled in one batch; every sample is written as
         `{base}_mel_sample_{i}.npy` (mel in [0,1], f32[80,848]) and -- if there is a vocoder (:183) --
@@ -448,7 +473,8 @@ class Diffsound:
             n_seen += len(captions)
             mel01, wave, _ = self.generate_sample_with_condition(list(captions), truncation_rate, replicate, fast=fast,
                                                                  caption_ids=ids, sample_rate=sample_rate,
-                                                                 guidance_scale=guidance_scale)
+                                                                 guidance_scale=guidance_scale, purity_steps=purity_steps,
+                                                                 purity_weight=purity_weight)
             mel01, wave = mel01.cpu().numpy(), None if wave is None else wave[:, 0].cpu().numpy()
             for i in range(mel01.shape[0]):
                 path = os.path.join(save_root, base + str(i))
