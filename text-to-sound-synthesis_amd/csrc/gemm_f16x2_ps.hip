@@ -35,9 +35,14 @@
 // * Measured (round 2, a standalone probe of this loop that has since been removed; M = 16960): 343 / 374 / 385 / 412 TF-eq at
 //   (N, K) = (1024, 1024) / (3072, 1024) / (4096, 1024) / (1024, 4096) against 253 / 286 / 290 / 283 for the
 //   128 x 128 two-workgroups-per-CU program on the same shapes (profiles/r02_probe_per_sample.txt).
-// Epilogue: the three store families of gemm_f16x2.hip (row-major fp32 + residual; packed split planes; attention-ready
-// Q / K / V^T), staged through the operand stages in three row slabs (tile rows 0..127: wave row 0, 128..255: wave row
-// 1, 256..287: every wave's ninth block) and written with 16-byte stores.  One kernel instantiation per family.
+// Epilogue (gemm_f16x2_ps_epilogue.inc): the three store families of gemm_f16x2.hip (row-major fp32 + residual; packed
+// split planes; attention-ready Q / K / V^T), one kernel instantiation per family.  The MFMAs take the WEIGHT fragment as
+// their first operand and the activation fragment as the second (the two fragment layouts are the same, so nothing else
+// of the loop knows): the accumulators hold the tile transposed -- a lane owns a tile ROW and each register quad four
+// consecutive columns of it, a 16-byte piece of the output row as it stands.  Packed planes leave straight from the
+// registers (one v_permlane32_swap between the wave halves completes the 8-column chunks); the other families stage
+// their quads through the operand stages with one ds_write_b128 each, in five steps of 64 rows, and finish the values
+// (scale, bias, activation, split) after the read-back.
 #include <stdlib.h>
 
 #include "common.h"
@@ -48,6 +53,7 @@
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) const void* ds_gptr;
 typedef __attribute__((address_space(3))) void* ds_lptr;
 
@@ -57,8 +63,17 @@ typedef __attribute__((address_space(3))) void* ds_lptr;
 #define PS_LEAD 6
 #define PS_GM 4            // raster: groups of 4 sample tiles x all column tiles (measured: 4 beats 2 and 8 by ~10 %)
 #define PS_STAGE_BYTES (2 * 2 * (PS_BM + PS_BN) * PS_HLD * 2)   // the main loop's two operand stages of 68 KB
-#define PS_VT_BYTES (2 * 2 * PS_BN * 36 * 4)                    // the epilogue's transposed V^T staging: two buffers of 72 KB
-#define PS_LDS_BYTES (PS_VT_BYTES > PS_STAGE_BYTES ? PS_VT_BYTES : PS_STAGE_BYTES)
+#define PS_EPI_BYTES (2 * 64 * (PS_BN + 4) * 4)                  // the epilogue's staging: two buffers of 64 rows x (256 + 4) words = 65 KB
+// Which fp16 families store straight from the registers (1) and which stage through LDS (0); both forms give the same bits
+// (tests/test_hip_ps_epilogue.py passes with either).  Measured inside the benchmark, per launch: FC1 -4.5 .. -6.7 us direct
+// (the staged form of this file ties it), Q / K tiles +5 us direct -- profiles/r11_ps_epilogue_*, NOTEBOOK.md "Round 11".
+#ifndef PS_DIRECT_SPLIT
+#define PS_DIRECT_SPLIT 1
+#endif
+#ifndef PS_DIRECT_QK
+#define PS_DIRECT_QK 0
+#endif
+#define PS_LDS_BYTES (PS_EPI_BYTES > PS_STAGE_BYTES ? PS_EPI_BYTES : PS_STAGE_BYTES)
 // NB16 operands: lane quad q of the 16-row MFMA operand reads tile-row quad PS_SIG(q) = {0, 2, 3, 1}[q].  With the natural
 // order the 16-lane service groups of ds_read_b128 ({0-3, 12-15, 20-27}, ...) hit each 16-byte slot of the packed image
 // twice (rows 0-3 and 4-7 of k-chunks 0 and 1 share a slot: SQ_LDS_BANK_CONFLICT = 17 % of the loop's LDS cycles, round-3
@@ -221,19 +236,19 @@ __global__ __launch_bounds__(512, 1) void ds_gemm_f16x2_ps_kernel(const GemmPara
     do {                                                                                             \
         _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                           \
             _Pragma("unroll") for (int ib = 0; ib < 2; ++ib)                                         \
-                acc[2 * (sa_) + ib][sb_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1[ks][ib], b0[sb_][ks], acc[2 * (sa_) + ib][sb_], 0, 0, 0); \
+                acc[2 * (sa_) + ib][sb_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b0[sb_][ks], a1[ks][ib], acc[2 * (sa_) + ib][sb_], 0, 0, 0); \
             _Pragma("unroll") for (int ib = 0; ib < 2; ++ib)                                         \
-                acc[2 * (sa_) + ib][sb_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[ks][ib], b1[sb_][ks], acc[2 * (sa_) + ib][sb_], 0, 0, 0); \
+                acc[2 * (sa_) + ib][sb_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b1[sb_][ks], a0[ks][ib], acc[2 * (sa_) + ib][sb_], 0, 0, 0); \
             _Pragma("unroll") for (int ib = 0; ib < 2; ++ib)                                         \
-                acc[2 * (sa_) + ib][sb_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[ks][ib], b0[sb_][ks], acc[2 * (sa_) + ib][sb_], 0, 0, 0); \
+                acc[2 * (sa_) + ib][sb_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b0[sb_][ks], a0[ks][ib], acc[2 * (sa_) + ib][sb_], 0, 0, 0); \
         }                                                                                            \
     } while (0)
 #define PS_EXTRA(sb_)                                                                                \
     do {                                                                                             \
         _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                           \
-            acc8 = __builtin_amdgcn_mfma_f32_32x32x16_f16(e1[ks], b0[sb_][ks], acc8, 0, 0, 0);       \
-            acc8 = __builtin_amdgcn_mfma_f32_32x32x16_f16(e0[ks], b1[sb_][ks], acc8, 0, 0, 0);       \
-            acc8 = __builtin_amdgcn_mfma_f32_32x32x16_f16(e0[ks], b0[sb_][ks], acc8, 0, 0, 0);       \
+            acc8 = __builtin_amdgcn_mfma_f32_32x32x16_f16(b0[sb_][ks], e1[ks], acc8, 0, 0, 0);       \
+            acc8 = __builtin_amdgcn_mfma_f32_32x32x16_f16(b1[sb_][ks], e0[ks], acc8, 0, 0, 0);       \
+            acc8 = __builtin_amdgcn_mfma_f32_32x32x16_f16(b0[sb_][ks], e0[ks], acc8, 0, 0, 0);       \
         }                                                                                            \
     } while (0)
 #define PS_READ_EB16(buf_)                                                                           \
@@ -253,9 +268,9 @@ __global__ __launch_bounds__(512, 1) void ds_gemm_f16x2_ps_kernel(const GemmPara
 #define PS_EXTRA16()                                                                                 \
     do {                                                                                             \
         _Pragma("unroll") for (int tt = 0; tt < 2; ++tt) {                                           \
-            acc9[tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ea1, eb0[tt], acc9[tt], 0, 0, 0);      \
-            acc9[tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ea0, eb1[tt], acc9[tt], 0, 0, 0);      \
-            acc9[tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ea0, eb0[tt], acc9[tt], 0, 0, 0);      \
+            acc9[tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(eb0[tt], ea1, acc9[tt], 0, 0, 0);      \
+            acc9[tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(eb1[tt], ea0, acc9[tt], 0, 0, 0);      \
+            acc9[tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(eb0[tt], ea0, acc9[tt], 0, 0, 0);      \
         }                                                                                            \
     } while (0)
     // one phase: P = phase within the k-tile (compile time), BUF = parity of the k-tile t (compile time)
@@ -342,7 +357,7 @@ __global__ __launch_bounds__(512, 1) void ds_gemm_f16x2_ps_kernel(const GemmPara
 //     fragment reads) -- which is why full tiles keep every grid they can fill.
 #define PH_AROWS 144
 #define PH_STAGE_BYTES (2 * (PH_AROWS + PS_BN) * PS_HLD * 2)    // 50 KB
-#define PH_LDS_BYTES (3 * PH_STAGE_BYTES > PS_VT_BYTES ? 3 * PH_STAGE_BYTES : PS_VT_BYTES)
+#define PH_LDS_BYTES (3 * PH_STAGE_BYTES > PS_EPI_BYTES ? 3 * PH_STAGE_BYTES : PS_EPI_BYTES)
 
 template <int EPI>
 __global__ __launch_bounds__(512, 1) void ds_gemm_f16x2_ph_kernel(const GemmParams p) {
@@ -477,19 +492,19 @@ __global__ __launch_bounds__(512, 1) void ds_gemm_f16x2_ph_kernel(const GemmPara
     do {                                                                                             \
         _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                           \
             _Pragma("unroll") for (int ib = 0; ib < 2; ++ib)                                         \
-                acc[ib][sb_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1[ks][ib], b0[sb_][ks], acc[ib][sb_], 0, 0, 0); \
+                acc[ib][sb_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b0[sb_][ks], a1[ks][ib], acc[ib][sb_], 0, 0, 0); \
             _Pragma("unroll") for (int ib = 0; ib < 2; ++ib)                                         \
-                acc[ib][sb_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[ks][ib], b1[sb_][ks], acc[ib][sb_], 0, 0, 0); \
+                acc[ib][sb_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b1[sb_][ks], a0[ks][ib], acc[ib][sb_], 0, 0, 0); \
             _Pragma("unroll") for (int ib = 0; ib < 2; ++ib)                                         \
-                acc[ib][sb_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[ks][ib], b0[sb_][ks], acc[ib][sb_], 0, 0, 0); \
+                acc[ib][sb_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b0[sb_][ks], a0[ks][ib], acc[ib][sb_], 0, 0, 0); \
         }                                                                                            \
     } while (0)
 #define PH_EXTRA16()                                                                                 \
     do {                                                                                             \
         _Pragma("unroll") for (int tt = 0; tt < 2; ++tt) {                                           \
-            acc9[tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ea1, eb0[tt], acc9[tt], 0, 0, 0);      \
-            acc9[tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ea0, eb1[tt], acc9[tt], 0, 0, 0);      \
-            acc9[tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ea0, eb0[tt], acc9[tt], 0, 0, 0);      \
+            acc9[tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(eb0[tt], ea1, acc9[tt], 0, 0, 0);      \
+            acc9[tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(eb1[tt], ea0, acc9[tt], 0, 0, 0);      \
+            acc9[tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(eb0[tt], ea0, acc9[tt], 0, 0, 0);      \
         }                                                                                            \
     } while (0)
     // one phase of k-tile `tt` (run time) in stage ST = tt % 3 (compile time): P = 0: (A, B-sub0), P = 1: (A, B-sub1) + block
@@ -555,6 +570,7 @@ static bool ps_serves(const GemmParams& p, bool half) {
     if (!p.a_split || L <= 0 || L > PS_BM - 15 || L <= 240 || p.M % L != 0) return false;
     if (half && L != PS_BM - 16) return false;
     if (p.N % PS_BN != 0 || p.K % 64 != 0 || p.lda != p.K || p.ldw != p.K) return false;
+    if (((uintptr_t)p.bias & 15) != 0) return false;               // the epilogue loads the bias four columns at a time
     if (p.store == DS_STORE_ROW && !p.c_split) {
         if (((p.N | p.ldc | p.ldr) & 3) != 0 || (((uintptr_t)p.C | (uintptr_t)p.R) & 15) != 0) return false;
     } else if (p.store == DS_STORE_ROW) {
