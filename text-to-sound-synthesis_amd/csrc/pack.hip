@@ -452,7 +452,9 @@ __global__ __launch_bounds__(1024) void ds_norm_finish_kernel(const double* __re
         *total = t;
         if (coef) {
             const float c = max_norm / (t + 1e-6f);                       // torch: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1
-            *coef = max_norm > 0.f ? (c < 1.f ? c : 1.f) : 1.f;
+            // (c > 1 ? 1 : c, not c < 1 ? c : 1: a NaN norm gives a NaN coefficient, as torch's clamp does -- every parameter turns NaN
+            // on that step, which the next loss shows, instead of one tensor silently taking its NaN gradient at full size)
+            *coef = max_norm > 0.f ? (c > 1.f ? 1.f : c) : 1.f;
         }
     }
 }

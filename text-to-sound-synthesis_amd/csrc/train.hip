@@ -568,7 +568,9 @@ __global__ __launch_bounds__(256) void ds_adamw_kernel(float* __restrict__ p, co
 extern "C" int ds_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
                         float eps, float weight_decay, int step, ds_stream_t stream) {
     DS_CHECK_ARG(p && g && m && v && n > 0 && step >= 1, "bad arguments");
-    const float bc1 = 1.f - powf(beta1, (float)step), bc2s = sqrtf(1.f - powf(beta2, (float)step));
+    // in double, rounded once: 1.f - powf(beta, step) carries powf's float32 rounding of beta^step into a small difference
+    // (beta2 = 0.999, step 2: 1.5e-5 relative on 1 - beta2^2, 20 x the float32 error of the whole update)
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step)), bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
     hipLaunchKernelGGL(ds_adamw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr,
                        beta1, beta2, eps, weight_decay, bc1, bc2s);
     DS_CHECK_LAUNCH();
