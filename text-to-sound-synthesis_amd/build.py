@@ -74,7 +74,7 @@ def _check_scratch(src, remarks):
 
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_f16x2_ps_epilogue.inc"),
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "sampler.h"), os.path.join(CSRC, "gemm_f16x2_ps_epilogue.inc"),
                os.path.join(CSRC, "stft_mel_fft.h"),
                os.path.join(ROOT, "include", "diffsound_hip.h")]
     hipcc = _hipcc()

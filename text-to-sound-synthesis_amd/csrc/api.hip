@@ -7,7 +7,7 @@
 
 #include <vector>
 
-#include "common.h"
+#include "sampler.h"
 
 static thread_local char g_err[512] = "";
 
@@ -164,7 +164,7 @@ static size_t attn_img_floats(int B, int heads, int Lk) { return (size_t)B * hea
 // 16x16x32 MFMA instead of 32 rows (gemm_f16x2_ps.hip NB16: -5 % MFMA work).  The 7 extra rows per sample start as zeros
 // (ds_embed_rows), stay finite through every layer (LayerNorm of a constant row = its shift), are extra QUERIES of the
 // attention (the ninth query tile exists anyway) but never keys (Lk = L masks them), and the sampler reads the L real
-// rows of each sample (ds_sample_tail_rows).  Rows 256..264 of a sample are then summed in another order than by the
+// rows of each sample (TailCall::logits_rows).  Rows 256..264 of a sample are then summed in another order than by the
 // 4-wave programs (same products): equal to ~1e-7 relative, not bit-identical across batch sizes.
 static const int PS_ROWS = 272;
 bool ds_gemm_f16x2_ps_taken(int B, int N);   // gemm_f16x2.hip: the dispatch rule of the per-sample program, forced tile included
@@ -424,38 +424,140 @@ extern "C" int ds_denoiser_forward(const ds_denoiser* h, const int64_t* tokens, 
     return forward_impl(h, tokens, t, kv, B, w, logits, logits_layout, (hipStream_t)stream, h->d.seq_len);
 }
 
-int ds_sample_tail_rows_hold(const float* logits, int logits_rows, const int64_t* xt, const int64_t* t, const float* u,
-                             const float* sched, int64_t* out_tokens, float* dbg_log_pred, float* dbg_trunc, float* dbg_post,
-                             int B, int L, int K, int T, int initial, float trunc_r, int trunc_k, ds_stream_t stream,
-                             const int64_t* gids, unsigned long long seed, int call, const unsigned char* keep,
-                             const int64_t* known, int mode);   // sampler.hip: ds_sample_tail_rows + the region-held form
+// ---- sampling steps and chains: forward + sampling tail (sampler.h TailCall) -------------------------------------------------
+// One step, as every ds_denoiser_step* / ds_denoiser_sample* entry describes it.  The entry fills the tail's who, stream, B,
+// noise source, truncation, `initial` and its hold / guidance / purity fields; aim_tail adds what the handle and the workspace
+// give.  kv and workspace are at the forward's batch: B, or 2B with tokens2.
+struct StepCall {
+    TailCall tail;
+    const int64_t* tokens_in = nullptr;
+    int64_t* tokens_out = nullptr;
+    const int64_t* t = nullptr;        // drives the network (AdaLN)
+    const int64_t* t_post = nullptr;   // drives the posterior, nullptr: t.  They differ only for the skip-step sampler
+                                       //   (sample_fast, diffusion_transformer.py:796-803: q_posterior with t - skip_step)
+    const float* kv = nullptr;
+    void* workspace = nullptr;
+    // non-null: classifier-free guidance (sampler.hip SampleGuide) -- ONE forward at batch 2B on the tokens duplicated into this
+    // i64[2B][seq_len] scratch (two async copies on the call's stream), rows 0 .. B-1 under the captions, rows B .. 2B-1 under
+    // the null condition (kv: ds_denoiser_cond_kv of the caption embeddings followed by the null embeddings; t, t_post: the
+    // caller's B entries repeated, the posterior reads the first B), and the tail mixes the two halves of the logits
+    int64_t* tokens2 = nullptr;
+    bool zero_kv_pad = true;           // forward_impl: false in the later steps of a chain
+};
 
-// t drives the network (AdaLN), t_post the posterior: they differ only for the skip-step sampler
-// (sample_fast, diffusion_transformer.py:796-803 calls q_posterior with t - skip_step)
-static int step_impl(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const int64_t* t_post,
-                     const float* kv, const float* u, const int64_t* gids, unsigned long long seed, int call, int B,
-                     int initial, float trunc_r, int trunc_k, void* workspace, int64_t* tokens_out, ds_stream_t stream,
-                     bool zero_kv_pad = true, const unsigned char* keep = nullptr, const int64_t* known = nullptr,
-                     int mode = 0) {
-    DS_CHECK_ARG(mode == 0 || mode == 1, "mode is 0 (clamp) or 1 (renoise)");      // before the forward is enqueued
-    DS_CHECK_ARG(!(mode == 1 && !gids), "renoise draws from the caption's Philox stream: not with caller uniforms");
-    DS_CHECK_ARG(!keep || known, "keep without known");
-    Carve w;
-    const int Lp = rows_per_sample(h, B);
-    carve(h, B, workspace, &w, Lp);
-    TRY(forward_impl(h, tokens_in, t, kv, B, w, w.logits, 0, (hipStream_t)stream, Lp, zero_kv_pad));
-    return ds_sample_tail_rows_hold(w.logits, Lp, tokens_in, t_post ? t_post : t, u, h->d.sched, tokens_out, nullptr, nullptr,
-                                    nullptr, B, h->d.seq_len, h->d.n_codes, h->d.n_steps, initial, trunc_r, trunc_k, stream,
-                                    gids, seed, call, keep, known, mode);
+static int step_error(const StepCall& s, int rc, const char* what, const char* detail) {
+    ds_set_error("%s: %s%s", s.tail.who, what, detail);
+    return rc;
 }
 
+// Completes s.tail: the logits where the forward will leave them, the tokens, and the handle's constants.  Host arithmetic
+// only.  The purity tail reads no timestep and no schedule table: t, sched and T stay zero.  Returns the rows per sample.
+static int aim_tail(const ds_denoiser* h, StepCall& s, Carve* w) {
+    TailCall& c = s.tail;
+    const int Bf = s.tokens2 ? 2 * c.B : c.B, Lp = rows_per_sample(h, Bf);
+    carve(h, Bf, s.workspace, w, Lp);
+    c.L = h->d.seq_len; c.K = h->d.n_codes;
+    c.logits = w->logits; c.logits_rows = Lp;
+    c.logits_u = s.tokens2 ? w->logits + (size_t)c.B * Lp * c.K : nullptr;
+    c.xt = s.tokens_in; c.out_tokens = s.tokens_out;
+    if (c.kind == DS_TAIL_POSTERIOR) {
+        c.t = s.t_post ? s.t_post : s.t; c.sched = h->d.sched; c.T = h->d.n_steps;
+    }
+    return Lp;
+}
+
+// the driver's pointer rules, then every rule of the tail on the call as run_step will launch it: before anything is enqueued
+static int step_check(const ds_denoiser* h, StepCall s) {
+    if (!(h && s.tokens_in && s.t && s.kv && s.workspace && s.tokens_out && s.tail.B > 0))
+        return step_error(s, -1, "bad arguments", "");
+    Carve w;
+    aim_tail(h, s, &w);
+    return ds_sample_tail_check(s.tail);
+}
+
+static int run_step(const ds_denoiser* h, StepCall& s) {
+    hipStream_t stream = (hipStream_t)s.tail.stream;
+    const size_t n_tok = (size_t)s.tail.B * h->d.seq_len;
+    for (int half = 0; s.tokens2 && half < 2; ++half) {
+        hipError_t e = hipMemcpyAsync(s.tokens2 + half * n_tok, s.tokens_in, n_tok * sizeof(int64_t), hipMemcpyDeviceToDevice,
+                                      stream);
+        if (e != hipSuccess) return step_error(s, -2, "hipMemcpyAsync: ", hipGetErrorString(e));
+    }
+    Carve w;
+    const int Lp = aim_tail(h, s, &w);
+    TRY(forward_impl(h, s.tokens2 ? s.tokens2 : s.tokens_in, s.t, s.kv, s.tokens2 ? 2 * s.tail.B : s.tail.B, w, w.logits, 0,
+                     stream, Lp, s.zero_kv_pad));
+    return ds_sample_tail_launch(s.tail);
+}
+
+static int step(const ds_denoiser* h, StepCall& s) {
+    TRY(step_check(h, s));
+    return run_step(h, s);
+}
+
+// A whole chain enqueued from C++ (DiffusionTransformer.sample's loop, diffusion_transformer.py:639-641, and sample_fast's,
+// :790-804): nothing returns to the host between steps.  What differs between the chain entries is data: t_steps, a DEVICE
+// array, holds t_stride entries per call -- the network's timestep vector first, the posterior's at post_off (0: none).
+struct ChainCall {
+    int64_t* tokens;          // in: the start state, out: the result; [B][seq_len] like tokens_tmp, the other end of the ping-pong
+    int64_t* tokens_tmp;
+    const int64_t* t_steps;
+    int n_calls;
+    size_t t_stride, post_off;
+    const int* remain;        // purity: HOST int[n_calls], read before the entry returns; nullptr otherwise
+};
+
+// `first` describes call 0 (tail.call = call0; tail.initial: the start state is all-[MASK]).  Call k draws Philox call index
+// call0 + k, only call 0 can be `initial`, and only call 0 zeroes the self-attention images' padding (nothing between two steps
+// of a chain touches the workspace).  The result lands in `tokens` after an even number of calls and is copied there after an
+// odd one.  Every call's arguments are checked before the first is enqueued.
+static int run_chain(const ds_denoiser* h, const StepCall& first, const ChainCall& ch) {
+    StepCall s = first;
+    if (!(ch.tokens && ch.tokens_tmp && ch.t_steps && ch.n_calls >= 0)) return step_error(s, -1, "bad arguments", "");
+    s.tokens_in = ch.tokens; s.tokens_out = ch.tokens_tmp; s.t = ch.t_steps;
+    TRY(step_check(h, s));
+    for (int k = 0; ch.remain && k < ch.n_calls; ++k) {
+        s.tail.remain = ch.remain[k];
+        TRY(step_check(h, s));
+    }
+    int64_t *cur = ch.tokens, *nxt = ch.tokens_tmp;
+    for (int k = 0; k < ch.n_calls; ++k) {
+        s.tokens_in = cur; s.tokens_out = nxt;
+        s.t = ch.t_steps + k * ch.t_stride;
+        s.t_post = ch.post_off ? s.t + ch.post_off : nullptr;
+        s.zero_kv_pad = k == 0;
+        s.tail.initial = first.tail.initial && k == 0;
+        s.tail.call = first.tail.call + k;
+        if (ch.remain) s.tail.remain = ch.remain[k];
+        TRY(run_step(h, s));
+        int64_t* sw = cur; cur = nxt; nxt = sw;
+    }
+    if (cur != ch.tokens) {
+        hipError_t e = hipMemcpyAsync(ch.tokens, cur, (size_t)s.tail.B * h->d.seq_len * sizeof(int64_t), hipMemcpyDeviceToDevice,
+                                      (hipStream_t)s.tail.stream);
+        if (e != hipSuccess) return step_error(s, -2, "hipMemcpyAsync: ", hipGetErrorString(e));
+    }
+    return 0;
+}
+
+// ---- the public entries: fill a StepCall (and a ChainCall), the entry's own null test -- u for the uniform forms, gids for
+// the _rng forms, and what only this family requires -- then step() or run_chain()
 extern "C" int ds_denoiser_step_ex(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t,
                                    const int64_t* t_post, const float* kv, const float* u, int B, int initial,
                                    float trunc_r, int trunc_k, void* workspace, int64_t* tokens_out,
                                    ds_stream_t stream) {
-    DS_CHECK_ARG(h && tokens_in && t && kv && u && workspace && tokens_out && B > 0, "bad arguments");
-    return step_impl(h, tokens_in, t, t_post, kv, u, nullptr, 0ull, 0, B, initial, trunc_r, trunc_k, workspace, tokens_out,
-                     stream);
+    DS_CHECK_ARG(u, "bad arguments");
+    StepCall s{{__func__, DS_TAIL_POSTERIOR, stream}};
+    TailCall& c = s.tail;
+    c.B = B; c.u = u; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    s.tokens_in = tokens_in; s.tokens_out = tokens_out; s.t = t; s.t_post = t_post; s.kv = kv; s.workspace = workspace;
+    return step(h, s);
+}
+
+extern "C" int ds_denoiser_step(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const float* kv,
+                                const float* u, int B, int initial, float trunc_r, void* workspace,
+                                int64_t* tokens_out, ds_stream_t stream) {
+    return ds_denoiser_step_ex(h, tokens_in, t, nullptr, kv, u, B, initial, trunc_r, 0, workspace, tokens_out, stream);
 }
 
 // the same step with the noise drawn inside the sampler kernel (sampler.hip: Philox keyed by seed, counter = global
@@ -465,37 +567,26 @@ extern "C" int ds_denoiser_step_rng(const ds_denoiser* h, const int64_t* tokens_
                                     const int64_t* t_post, const float* kv, const int64_t* gids,
                                     unsigned long long seed, int call, int B, int initial, float trunc_r, int trunc_k,
                                     void* workspace, int64_t* tokens_out, ds_stream_t stream) {
-    DS_CHECK_ARG(h && tokens_in && t && kv && gids && workspace && tokens_out && B > 0, "bad arguments");
-    return step_impl(h, tokens_in, t, t_post, kv, nullptr, gids, seed, call, B, initial, trunc_r, trunc_k, workspace,
-                     tokens_out, stream);
+    DS_CHECK_ARG(gids, "bad arguments");
+    StepCall s{{__func__, DS_TAIL_POSTERIOR, stream}};
+    TailCall& c = s.tail;
+    c.B = B; c.gids = gids; c.seed = seed; c.call = call; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    s.tokens_in = tokens_in; s.tokens_out = tokens_out; s.t = t; s.t_post = t_post; s.kv = kv; s.workspace = workspace;
+    return step(h, s);
 }
 
-// A whole reverse chain enqueued from C++ (DiffusionTransformer.sample's loop, diffusion_transformer.py:639-641, and
-// sample_fast's, :790-804): n_calls steps; t_steps is a DEVICE array i64[n_calls][2][B] -- per call the network's
-// timestep vector and the posterior's (equal except for the skip-step sampler).  tokens (in: the start state, out: the
-// result) and tokens_tmp ([B][seq_len] each) are the two ends of the ping-pong; call k uses Philox call index
-// call0 + k; `initial` marks the first call's state as the all-[MASK] start.  Nothing returns to the host between steps.
+// the chain of ds_denoiser_step_rng: t_steps is i64[n_calls][2][B] -- per call the network's timestep vector and the
+// posterior's (equal except for the skip-step sampler)
 extern "C" int ds_denoiser_sample_rng(const ds_denoiser* h, int64_t* tokens, int64_t* tokens_tmp, const int64_t* t_steps,
                                       int n_calls, const float* kv, const int64_t* gids, unsigned long long seed,
                                       int call0, int B, int initial, float trunc_r, int trunc_k, void* workspace,
                                       ds_stream_t stream) {
-    DS_CHECK_ARG(h && tokens && tokens_tmp && t_steps && kv && gids && workspace && B > 0 && n_calls >= 0, "bad arguments");
-    int64_t *cur = tokens, *nxt = tokens_tmp;
-    for (int k = 0; k < n_calls; ++k) {
-        const int64_t* tk = t_steps + (size_t)k * 2 * B;
-        TRY(step_impl(h, cur, tk, tk + B, kv, nullptr, gids, seed, call0 + k, B, initial && k == 0, trunc_r, trunc_k,
-                      workspace, nxt, stream, k == 0));
-        int64_t* sw = cur; cur = nxt; nxt = sw;
-    }
-    if (cur != tokens) {
-        hipError_t e = hipMemcpyAsync(tokens, cur, (size_t)B * h->d.seq_len * sizeof(int64_t), hipMemcpyDeviceToDevice,
-                                      (hipStream_t)stream);
-        if (e != hipSuccess) {
-            ds_set_error("ds_denoiser_sample_rng: hipMemcpyAsync: %s", hipGetErrorString(e));
-            return -2;
-        }
-    }
-    return 0;
+    DS_CHECK_ARG(gids, "bad arguments");
+    StepCall s{{__func__, DS_TAIL_POSTERIOR, stream}};
+    TailCall& c = s.tail;
+    c.B = B; c.gids = gids; c.seed = seed; c.call = call0; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    s.kv = kv; s.workspace = workspace;
+    return run_chain(h, s, ChainCall{tokens, tokens_tmp, t_steps, n_calls, 2 * (size_t)B, (size_t)B, nullptr});
 }
 
 // ---- region-held sampling (inpainting / continuation; sampler.hip SampleHold): the three entries above with keep u8[B][seq_len]
@@ -505,9 +596,13 @@ extern "C" int ds_denoiser_step_hold(const ds_denoiser* h, const int64_t* tokens
                                      const int64_t* t_post, const float* kv, const float* u, int B, int initial,
                                      float trunc_r, int trunc_k, const unsigned char* keep, const int64_t* known, int mode,
                                      void* workspace, int64_t* tokens_out, ds_stream_t stream) {
-    DS_CHECK_ARG(h && tokens_in && t && kv && u && workspace && tokens_out && B > 0, "bad arguments");
-    return step_impl(h, tokens_in, t, t_post, kv, u, nullptr, 0ull, 0, B, initial, trunc_r, trunc_k, workspace, tokens_out,
-                     stream, true, keep, known, mode);
+    DS_CHECK_ARG(u, "bad arguments");
+    StepCall s{{__func__, DS_TAIL_POSTERIOR, stream}};
+    TailCall& c = s.tail;
+    c.B = B; c.u = u; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    c.keep = keep; c.known = known; c.mode = mode;
+    s.tokens_in = tokens_in; s.tokens_out = tokens_out; s.t = t; s.t_post = t_post; s.kv = kv; s.workspace = workspace;
+    return step(h, s);
 }
 
 extern "C" int ds_denoiser_step_hold_rng(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t,
@@ -515,9 +610,13 @@ extern "C" int ds_denoiser_step_hold_rng(const ds_denoiser* h, const int64_t* to
                                          unsigned long long seed, int call, int B, int initial, float trunc_r, int trunc_k,
                                          const unsigned char* keep, const int64_t* known, int mode, void* workspace,
                                          int64_t* tokens_out, ds_stream_t stream) {
-    DS_CHECK_ARG(h && tokens_in && t && kv && gids && workspace && tokens_out && B > 0, "bad arguments");
-    return step_impl(h, tokens_in, t, t_post, kv, nullptr, gids, seed, call, B, initial, trunc_r, trunc_k, workspace,
-                     tokens_out, stream, true, keep, known, mode);
+    DS_CHECK_ARG(gids, "bad arguments");
+    StepCall s{{__func__, DS_TAIL_POSTERIOR, stream}};
+    TailCall& c = s.tail;
+    c.B = B; c.gids = gids; c.seed = seed; c.call = call; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    c.keep = keep; c.known = known; c.mode = mode;
+    s.tokens_in = tokens_in; s.tokens_out = tokens_out; s.t = t; s.t_post = t_post; s.kv = kv; s.workspace = workspace;
+    return step(h, s);
 }
 
 // the whole chain: `tokens` holds the caller's start state (held positions included), known stays constant over the calls;
@@ -528,85 +627,30 @@ extern "C" int ds_denoiser_sample_hold_rng(const ds_denoiser* h, int64_t* tokens
                                            unsigned long long seed, int call0, int B, int initial, float trunc_r,
                                            int trunc_k, const unsigned char* keep, const int64_t* known, int mode,
                                            void* workspace, ds_stream_t stream) {
-    DS_CHECK_ARG(h && tokens && tokens_tmp && t_steps && kv && gids && workspace && B > 0 && n_calls >= 0, "bad arguments");
-    DS_CHECK_ARG(mode == 0 || mode == 1, "mode is 0 (clamp) or 1 (renoise)");
-    DS_CHECK_ARG(!keep || known, "keep without known");
-    int64_t *cur = tokens, *nxt = tokens_tmp;
-    for (int k = 0; k < n_calls; ++k) {
-        const int64_t* tk = t_steps + (size_t)k * 2 * B;
-        TRY(step_impl(h, cur, tk, tk + B, kv, nullptr, gids, seed, call0 + k, B, initial && k == 0, trunc_r, trunc_k,
-                      workspace, nxt, stream, k == 0, keep, known, mode));
-        int64_t* sw = cur; cur = nxt; nxt = sw;
-    }
-    if (cur != tokens) {
-        hipError_t e = hipMemcpyAsync(tokens, cur, (size_t)B * h->d.seq_len * sizeof(int64_t), hipMemcpyDeviceToDevice,
-                                      (hipStream_t)stream);
-        if (e != hipSuccess) {
-            ds_set_error("ds_denoiser_sample_hold_rng: hipMemcpyAsync: %s", hipGetErrorString(e));
-            return -2;
-        }
-    }
-    return 0;
+    DS_CHECK_ARG(gids, "bad arguments");
+    StepCall s{{__func__, DS_TAIL_POSTERIOR, stream}};
+    TailCall& c = s.tail;
+    c.B = B; c.gids = gids; c.seed = seed; c.call = call0; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    c.keep = keep; c.known = known; c.mode = mode;
+    s.kv = kv; s.workspace = workspace;
+    return run_chain(h, s, ChainCall{tokens, tokens_tmp, t_steps, n_calls, 2 * (size_t)B, (size_t)B, nullptr});
 }
 
-// ---- classifier-free guidance (sampler.hip SampleGuide): ONE forward at batch 2B -- rows 0 .. B-1 under the captions, rows
-// B .. 2B-1 under the null condition, on the same tokens and timesteps -- and the guided tail on the two halves of the logits.
-// kv: ds_denoiser_cond_kv at batch 2B of the caption embeddings followed by the null embeddings; workspace:
-// ds_denoiser_workspace_bytes(h, 2B); tokens2 i64[2B][seq_len]: caller's scratch, receives the duplicated tokens of each
-// step (two async copies on the call's stream); t / t_post: 2B entries, the caller's B repeated (the posterior reads the
-// first B).  keep == NULL: unheld.
-int ds_sample_tail_rows_guided(const char* who, const float* logits, const float* logits_u, int logits_rows, const int64_t* xt,
-                               const int64_t* t, const float* u, const float* sched, int64_t* out_tokens, float* dbg_log_pred,
-                               float* dbg_trunc, float* dbg_post, int B, int L, int K, int T, int initial, float trunc_r,
-                               int trunc_k, float scale, ds_stream_t stream, const int64_t* gids, unsigned long long seed,
-                               int call, const unsigned char* keep, const int64_t* known, int mode);   // sampler.hip
-
-static int guided_check(const char* who, bool pointers, float scale, const void* gids, const unsigned char* keep,
-                        const int64_t* known, int mode) {
-    const char* msg = !pointers                ? "bad arguments"
-                      : !(scale - scale == 0.f) ? "the guidance scale must be finite"
-                      : !(mode == 0 || mode == 1) ? "mode is 0 (clamp) or 1 (renoise)"
-                      : (mode == 1 && !gids)    ? "renoise draws from the caption's Philox stream: not with caller uniforms"
-                      : (keep && !known)        ? "keep without known"
-                                                : nullptr;
-    if (!msg) return 0;
-    ds_set_error("%s: %s", who, msg);
-    return -1;
-}
-
-static int guided_step_impl(const char* who, const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t,
-                            const int64_t* t_post, const float* kv, const float* u, const int64_t* gids,
-                            unsigned long long seed, int call, int B, int initial, float trunc_r, int trunc_k, float scale,
-                            const unsigned char* keep, const int64_t* known, int mode, int64_t* tokens2, void* workspace,
-                            int64_t* tokens_out, ds_stream_t stream, bool zero_kv_pad = true) {
-    const size_t tok_bytes = (size_t)B * h->d.seq_len * sizeof(int64_t);
-    for (int half = 0; half < 2; ++half) {
-        hipError_t e = hipMemcpyAsync(tokens2 + (size_t)half * B * h->d.seq_len, tokens_in, tok_bytes, hipMemcpyDeviceToDevice,
-                                      (hipStream_t)stream);
-        if (e != hipSuccess) {
-            ds_set_error("%s: hipMemcpyAsync: %s", who, hipGetErrorString(e));
-            return -2;
-        }
-    }
-    Carve w;
-    const int Lp = rows_per_sample(h, 2 * B);
-    carve(h, 2 * B, workspace, &w, Lp);
-    TRY(forward_impl(h, tokens2, t, kv, 2 * B, w, w.logits, 0, (hipStream_t)stream, Lp, zero_kv_pad));
-    return ds_sample_tail_rows_guided(who, w.logits, w.logits + (size_t)B * Lp * h->d.n_codes, Lp, tokens_in,
-                                      t_post ? t_post : t, u, h->d.sched, tokens_out, nullptr, nullptr, nullptr, B,
-                                      h->d.seq_len, h->d.n_codes, h->d.n_steps, initial, trunc_r, trunc_k, scale, stream, gids,
-                                      seed, call, keep, known, mode);
-}
-
+// ---- classifier-free guidance (StepCall::tokens2, which these entries require); workspace: ds_denoiser_workspace_bytes(h, 2B);
+// keep == NULL: unheld
 extern "C" int ds_denoiser_step_guided(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t,
                                        const int64_t* t_post, const float* kv, const float* u, int B, int initial,
                                        float trunc_r, int trunc_k, float scale, const unsigned char* keep,
                                        const int64_t* known, int mode, int64_t* tokens2, void* workspace,
                                        int64_t* tokens_out, ds_stream_t stream) {
-    TRY(guided_check(__func__, h && tokens_in && t && kv && u && tokens2 && workspace && tokens_out && B > 0, scale, nullptr,
-                     keep, known, mode));
-    return guided_step_impl(__func__, h, tokens_in, t, t_post, kv, u, nullptr, 0ull, 0, B, initial, trunc_r, trunc_k, scale,
-                            keep, known, mode, tokens2, workspace, tokens_out, stream);
+    DS_CHECK_ARG(u && tokens2, "bad arguments");
+    StepCall s{{__func__, DS_TAIL_POSTERIOR, stream}};
+    TailCall& c = s.tail;
+    c.B = B; c.u = u; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    c.keep = keep; c.known = known; c.mode = mode; c.scale = scale;
+    s.tokens_in = tokens_in; s.tokens_out = tokens_out; s.t = t; s.t_post = t_post; s.kv = kv; s.workspace = workspace;
+    s.tokens2 = tokens2;
+    return step(h, s);
 }
 
 extern "C" int ds_denoiser_step_guided_rng(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t,
@@ -614,127 +658,72 @@ extern "C" int ds_denoiser_step_guided_rng(const ds_denoiser* h, const int64_t* 
                                            unsigned long long seed, int call, int B, int initial, float trunc_r, int trunc_k,
                                            float scale, const unsigned char* keep, const int64_t* known, int mode,
                                            int64_t* tokens2, void* workspace, int64_t* tokens_out, ds_stream_t stream) {
-    TRY(guided_check(__func__, h && tokens_in && t && kv && gids && tokens2 && workspace && tokens_out && B > 0, scale, gids,
-                     keep, known, mode));
-    return guided_step_impl(__func__, h, tokens_in, t, t_post, kv, nullptr, gids, seed, call, B, initial, trunc_r, trunc_k,
-                            scale, keep, known, mode, tokens2, workspace, tokens_out, stream);
+    DS_CHECK_ARG(gids && tokens2, "bad arguments");
+    StepCall s{{__func__, DS_TAIL_POSTERIOR, stream}};
+    TailCall& c = s.tail;
+    c.B = B; c.gids = gids; c.seed = seed; c.call = call; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    c.keep = keep; c.known = known; c.mode = mode; c.scale = scale;
+    s.tokens_in = tokens_in; s.tokens_out = tokens_out; s.t = t; s.t_post = t_post; s.kv = kv; s.workspace = workspace;
+    s.tokens2 = tokens2;
+    return step(h, s);
 }
 
-// the whole guided chain: ds_denoiser_sample_hold_rng's ping-pong and call0 rules; t_steps is i64[n_calls][2][2B]
+// the whole guided chain: t_steps is i64[n_calls][2][2B]
 extern "C" int ds_denoiser_sample_guided_rng(const ds_denoiser* h, int64_t* tokens, int64_t* tokens_tmp,
                                              const int64_t* t_steps, int n_calls, const float* kv, const int64_t* gids,
                                              unsigned long long seed, int call0, int B, int initial, float trunc_r,
                                              int trunc_k, float scale, const unsigned char* keep, const int64_t* known,
                                              int mode, int64_t* tokens2, void* workspace, ds_stream_t stream) {
-    TRY(guided_check(__func__, h && tokens && tokens_tmp && t_steps && kv && gids && tokens2 && workspace && B > 0 &&
-                                   n_calls >= 0, scale, gids, keep, known, mode));
-    int64_t *cur = tokens, *nxt = tokens_tmp;
-    for (int k = 0; k < n_calls; ++k) {
-        const int64_t* tk = t_steps + (size_t)k * 4 * B;
-        TRY(guided_step_impl(__func__, h, cur, tk, tk + 2 * B, kv, nullptr, gids, seed, call0 + k, B, initial && k == 0,
-                             trunc_r, trunc_k, scale, keep, known, mode, tokens2, workspace, nxt, stream, k == 0));
-        int64_t* sw = cur; cur = nxt; nxt = sw;
-    }
-    if (cur != tokens) {
-        hipError_t e = hipMemcpyAsync(tokens, cur, (size_t)B * h->d.seq_len * sizeof(int64_t), hipMemcpyDeviceToDevice,
-                                      (hipStream_t)stream);
-        if (e != hipSuccess) {
-            ds_set_error("ds_denoiser_sample_guided_rng: hipMemcpyAsync: %s", hipGetErrorString(e));
-            return -2;
-        }
-    }
-    return 0;
+    DS_CHECK_ARG(gids && tokens2, "bad arguments");
+    StepCall s{{__func__, DS_TAIL_POSTERIOR, stream}};
+    TailCall& c = s.tail;
+    c.B = B; c.gids = gids; c.seed = seed; c.call = call0; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    c.keep = keep; c.known = known; c.mode = mode; c.scale = scale;
+    s.kv = kv; s.workspace = workspace; s.tokens2 = tokens2;
+    return run_chain(h, s, ChainCall{tokens, tokens_tmp, t_steps, n_calls, 4 * (size_t)B, 2 * (size_t)B, nullptr});
 }
 
-// ---- purity-prior sampling (sampler.hip SamplePurity): forward + purity tail.  tokens2 == NULL: the forward of step_impl at
-// batch B; else guided_step_impl's forward at batch 2B on the duplicated tokens, the tail mixing the two halves of the logits.
-// The tail reads no timestep and no schedule table.  scratch: ds_purity_scratch_bytes, a pointer of its own.
-int ds_sample_tail_purity_check(const char* who, bool pointers, bool guided, float scale, int remain, float weight, float trunc_r,
-                                int trunc_k, int logits_rows, int L, int K);   // sampler.hip
-int ds_sample_tail_purity_rows(const char* who, const float* logits, const float* logits_u, float scale, int logits_rows,
-                               const int64_t* xt, const float* u, const int64_t* gids, unsigned long long seed, int call,
-                               int remain, float weight, float trunc_r, int trunc_k, void* scratch, int64_t* out_tokens,
-                               float* dbg_sharp, float* dbg_key, int32_t* dbg_cand, int B, int L, int K, ds_stream_t stream);
-
-static int purity_step_impl(const char* who, const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const float* kv,
-                            const float* u, const int64_t* gids, unsigned long long seed, int call, int B, int remain,
-                            float weight, float trunc_r, int trunc_k, float scale, int64_t* tokens2, void* workspace,
-                            void* scratch, int64_t* tokens_out, ds_stream_t stream, bool zero_kv_pad = true) {
-    const int L = h->d.seq_len, K = h->d.n_codes, Bf = tokens2 ? 2 * B : B;
-    const int64_t* fwd_tokens = tokens_in;
-    if (tokens2) {
-        for (int half = 0; half < 2; ++half) {
-            hipError_t e = hipMemcpyAsync(tokens2 + (size_t)half * B * L, tokens_in, (size_t)B * L * sizeof(int64_t),
-                                          hipMemcpyDeviceToDevice, (hipStream_t)stream);
-            if (e != hipSuccess) {
-                ds_set_error("%s: hipMemcpyAsync: %s", who, hipGetErrorString(e));
-                return -2;
-            }
-        }
-        fwd_tokens = tokens2;
-    }
-    Carve w;
-    const int Lp = rows_per_sample(h, Bf);
-    carve(h, Bf, workspace, &w, Lp);
-    TRY(forward_impl(h, fwd_tokens, t, kv, Bf, w, w.logits, 0, (hipStream_t)stream, Lp, zero_kv_pad));
-    return ds_sample_tail_purity_rows(who, w.logits, tokens2 ? w.logits + (size_t)B * Lp * K : nullptr, scale, Lp, tokens_in, u,
-                                      gids, seed, call, remain, weight, trunc_r, trunc_k, scratch, tokens_out, nullptr, nullptr,
-                                      nullptr, B, L, K, stream);
-}
-
+// ---- purity-prior sampling (sampler.hip SamplePurity): forward + purity tail.  tokens2 == NULL: the forward at batch B; else
+// the guided forward at batch 2B, the tail mixing the two halves of the logits.  scratch: ds_purity_scratch_bytes, a pointer
+// of its own.
 extern "C" int ds_denoiser_step_purity(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const float* kv,
                                        const float* u, int B, int remain, float weight, float trunc_r, int trunc_k, float scale,
                                        int64_t* tokens2, void* workspace, void* scratch, int64_t* tokens_out,
                                        ds_stream_t stream) {
-    TRY(ds_sample_tail_purity_check(__func__, h && tokens_in && t && kv && u && workspace && scratch && tokens_out && B > 0,
-                                    tokens2 != nullptr, scale, remain, weight, trunc_r, trunc_k, h ? h->d.seq_len : 0,
-                                    h ? h->d.seq_len : 0, h ? h->d.n_codes : 0));
-    return purity_step_impl(__func__, h, tokens_in, t, kv, u, nullptr, 0ull, 0, B, remain, weight, trunc_r, trunc_k, scale,
-                            tokens2, workspace, scratch, tokens_out, stream);
+    DS_CHECK_ARG(u, "bad arguments");
+    StepCall s{{__func__, DS_TAIL_PURITY, stream}};
+    TailCall& c = s.tail;
+    c.B = B; c.u = u; c.scale = scale;
+    c.trunc_r = trunc_r; c.trunc_k = trunc_k; c.remain = remain; c.weight = weight; c.scratch = scratch;
+    s.tokens_in = tokens_in; s.tokens_out = tokens_out; s.t = t; s.kv = kv; s.workspace = workspace; s.tokens2 = tokens2;
+    return step(h, s);
 }
 
 extern "C" int ds_denoiser_step_purity_rng(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const float* kv,
                                            const int64_t* gids, unsigned long long seed, int call, int B, int remain,
                                            float weight, float trunc_r, int trunc_k, float scale, int64_t* tokens2,
                                            void* workspace, void* scratch, int64_t* tokens_out, ds_stream_t stream) {
-    TRY(ds_sample_tail_purity_check(__func__, h && tokens_in && t && kv && gids && workspace && scratch && tokens_out && B > 0,
-                                    tokens2 != nullptr, scale, remain, weight, trunc_r, trunc_k, h ? h->d.seq_len : 0,
-                                    h ? h->d.seq_len : 0, h ? h->d.n_codes : 0));
-    return purity_step_impl(__func__, h, tokens_in, t, kv, nullptr, gids, seed, call, B, remain, weight, trunc_r, trunc_k, scale,
-                            tokens2, workspace, scratch, tokens_out, stream);
+    DS_CHECK_ARG(gids, "bad arguments");
+    StepCall s{{__func__, DS_TAIL_PURITY, stream}};
+    TailCall& c = s.tail;
+    c.B = B; c.gids = gids; c.seed = seed; c.call = call;
+    c.scale = scale; c.trunc_r = trunc_r; c.trunc_k = trunc_k; c.remain = remain; c.weight = weight; c.scratch = scratch;
+    s.tokens_in = tokens_in; s.tokens_out = tokens_out; s.t = t; s.kv = kv; s.workspace = workspace; s.tokens2 = tokens2;
+    return step(h, s);
 }
 
-// the whole purity chain: ds_denoiser_sample_rng's ping-pong and call0 rules; t_steps is i64[n_calls][B] (guided: [n_calls][2B]),
-// remain a HOST array read here, before the call returns
+// the whole purity chain: t_steps is i64[n_calls][B] (guided: [n_calls][2B]), remain a HOST array read here
 extern "C" int ds_denoiser_sample_purity_rng(const ds_denoiser* h, int64_t* tokens, int64_t* tokens_tmp, const int64_t* t_steps,
                                              const int* remain, int n_calls, const float* kv, const int64_t* gids,
                                              unsigned long long seed, int call0, int B, float weight, float trunc_r,
                                              int trunc_k, float scale, int64_t* tokens2, void* workspace, void* scratch,
                                              ds_stream_t stream) {
-    const bool ptrs = h && tokens && tokens_tmp && t_steps && remain && kv && gids && workspace && scratch && B > 0 && n_calls >= 0;
-    for (int k = 0; k < (ptrs ? n_calls : 1); ++k)          // every step's arguments, before anything is enqueued
-        TRY(ds_sample_tail_purity_check(__func__, ptrs, tokens2 != nullptr, scale, ptrs && n_calls > 0 ? remain[k] : 0, weight,
-                                        trunc_r, trunc_k, h ? h->d.seq_len : 0, h ? h->d.seq_len : 0, h ? h->d.n_codes : 0));
-    int64_t *cur = tokens, *nxt = tokens_tmp;
-    const size_t tb = tokens2 ? 2 * (size_t)B : (size_t)B;
-    for (int k = 0; k < n_calls; ++k) {
-        TRY(purity_step_impl(__func__, h, cur, t_steps + (size_t)k * tb, kv, nullptr, gids, seed, call0 + k, B, remain[k], weight,
-                             trunc_r, trunc_k, scale, tokens2, workspace, scratch, nxt, stream, k == 0));
-        int64_t* sw = cur; cur = nxt; nxt = sw;
-    }
-    if (cur != tokens) {
-        hipError_t e = hipMemcpyAsync(tokens, cur, (size_t)B * h->d.seq_len * sizeof(int64_t), hipMemcpyDeviceToDevice,
-                                      (hipStream_t)stream);
-        if (e != hipSuccess) {
-            ds_set_error("ds_denoiser_sample_purity_rng: hipMemcpyAsync: %s", hipGetErrorString(e));
-            return -2;
-        }
-    }
-    return 0;
+    DS_CHECK_ARG(gids && remain, "bad arguments");
+    StepCall s{{__func__, DS_TAIL_PURITY, stream}};
+    TailCall& c = s.tail;
+    c.B = B; c.gids = gids; c.seed = seed; c.call = call0;
+    c.scale = scale; c.trunc_r = trunc_r; c.trunc_k = trunc_k; c.weight = weight; c.scratch = scratch;
+    s.kv = kv; s.workspace = workspace; s.tokens2 = tokens2;
+    return run_chain(h, s, ChainCall{tokens, tokens_tmp, t_steps, n_calls, (tokens2 ? 2 : 1) * (size_t)B, 0, remain});
 }
 
-extern "C" int ds_denoiser_step(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const float* kv,
-                                const float* u, int B, int initial, float trunc_r, void* workspace,
-                                int64_t* tokens_out, ds_stream_t stream) {
-    return ds_denoiser_step_ex(h, tokens_in, t, nullptr, kv, u, B, initial, trunc_r, 0, workspace, tokens_out, stream);
-}

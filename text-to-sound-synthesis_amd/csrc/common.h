@@ -153,7 +153,9 @@ struct GemmParams {
 // padded-row forms used by the native denoiser driver (api.hip): Lp / logits_rows >= L rows per sample
 int ds_embed_rows(const int64_t* tokens, const float* emb, const float* pos, float* out, int B, int L, int Lp, int D,
                   ds_stream_t stream);                                                                  // norm.hip
-// u == nullptr: the uniforms are drawn in the kernel from the Philox stream of (seed; gids[b], call) (sampler.hip)
+// RETIRED, nothing defines or calls it: sampler.h's TailCall took its place.  Only the declaration stays, because this
+// file's code (not its comments) is part of build.source_fingerprint, which ties the committed PMC measurement of the
+// dominant GEMM kernel to the sources it was taken on: delete it with the next PMC round (tools/profile_round.sh).
 int ds_sample_tail_rows(const float* logits, int logits_rows, const int64_t* xt, const int64_t* t, const float* u,
                         const float* sched, int64_t* out_tokens, float* dbg_log_pred, float* dbg_trunc, float* dbg_post,
                         int B, int L, int K, int T, int initial, float trunc_r, int trunc_k, ds_stream_t stream,

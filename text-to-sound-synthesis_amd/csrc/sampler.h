@@ -1,0 +1,44 @@
+// One sampling-tail launch (sampler.hip), host side: what every ds_sample_tail* entry and the denoiser's step driver
+// (api.hip run_step) hand to the one checker and the one launcher.  The caller names the fields it has, the rest stay zero;
+// the launcher sorts them into the kernels' argument structs.  (Not in common.h: that file's code is fingerprinted with the
+// dominant GEMM kernel, build.source_fingerprint.)
+#pragma once
+#include "common.h"
+
+enum TailKind { DS_TAIL_POSTERIOR, DS_TAIL_PURITY };
+
+struct TailCall {
+    const char* who = nullptr;               // the public entry: every message names it
+    TailKind kind = DS_TAIL_POSTERIOR;
+    ds_stream_t stream = nullptr;
+    const float* logits = nullptr;           // [B * logits_rows][K]
+    const float* logits_u = nullptr;         // non-null: guided; the null-condition logits, same layout
+    int logits_rows = 0;                     // rows of the logits per sample, >= L (the denoiser's padded-row mode)
+    const int64_t* xt = nullptr;
+    const int64_t* t = nullptr;              // posterior only, like sched and T
+    const float* u = nullptr;                // caller uniforms [B][K+1][L]; nullptr: drawn in the kernel from the Philox
+    const int64_t* gids = nullptr;           //   stream of (seed; gids[b], call)
+    unsigned long long seed = 0;
+    int call = 0;
+    const float* sched = nullptr;
+    int64_t* out_tokens = nullptr;
+    float* dbg_log_pred = nullptr;           // the posterior tail's optional dumps
+    float* dbg_trunc = nullptr;
+    float* dbg_post = nullptr;
+    int B = 0, L = 0, K = 0, T = 0, initial = 0;
+    float trunc_r = 0.f;
+    int trunc_k = 0;
+    const unsigned char* keep = nullptr;     // non-null: region-held, with known and mode (0 clamp, 1 renoise)
+    const int64_t* known = nullptr;
+    int mode = 0;
+    float scale = 0.f;                       // the guidance scale, read with logits_u
+    int remain = 0;                          // purity only, from here on
+    float weight = 0.f;
+    void* scratch = nullptr;                 // ds_purity_scratch_bytes
+    float* dbg_sharp = nullptr;
+    float* dbg_key = nullptr;
+    int32_t* dbg_cand = nullptr;
+};
+
+int ds_sample_tail_check(const TailCall& c);    // every argument rule, once: -1 and a message naming c.who, no HIP call
+int ds_sample_tail_launch(const TailCall& c);   // a checked call: fills the kernel arguments, selects the kernel

@@ -21,7 +21,7 @@
 // then depends neither on the batch it is in, nor on its position in it, nor on the rank that runs it (SURVEY.md
 // section 8e: "generate the noise per sample, seeded by global caption index"), no [B][K+1][L] tensor of uniforms
 // exists, and a whole reverse chain can be enqueued without returning to the host (api.hip ds_denoiser_sample_rng).
-#include "common.h"
+#include "sampler.h"
 
 // ---- Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; the Random123 constants) ----
 // counter (c0, c1, c2, c3), key (k0, k1) -> four 32-bit words.  Host mirror: text_to_sound_synthesis_amd/shard.py
@@ -881,143 +881,109 @@ extern "C" int ds_philox_uniforms(const int64_t* gids, unsigned long long seed, 
     return 0;
 }
 
-// logits_rows >= L: rows of `logits` per sample ([B * logits_rows][K]; the denoiser's padded-row mode, api.hip).
-// keep != nullptr: the region-held kernels (known [B][L], mode 0 clamp / 1 renoise); nullptr: the unheld ones.
-int ds_sample_tail_rows_hold(const float* logits, int logits_rows, const int64_t* xt, const int64_t* t, const float* u,
-                        const float* sched, int64_t* out_tokens, float* dbg_log_pred, float* dbg_trunc, float* dbg_post,
-                        int B, int L, int K, int T, int initial, float trunc_r, int trunc_k, ds_stream_t stream_,
-                             const int64_t* gids, unsigned long long seed, int call, const unsigned char* keep,
-                             const int64_t* known, int mode) {
-    hipStream_t stream = (hipStream_t)stream_;
-    DS_CHECK_ARG(logits && xt && t && (u || gids) && sched && out_tokens, "null pointer");
-    DS_CHECK_ARG(K == 256 || K == 512, "codebook size must be 256 or 512");
-    DS_CHECK_ARG(trunc_k >= 0 && !(trunc_k > 0 && trunc_r >= 0.f), "top-k and top-r truncation are exclusive");
-    DS_CHECK_ARG(logits_rows >= L && L < 65536, "logits rows per sample");
-    DS_CHECK_ARG(mode == 0 || mode == 1, "mode is 0 (clamp) or 1 (renoise)");
-    DS_CHECK_ARG(!(mode == 1 && u), "renoise draws from the caption's Philox stream: not with caller uniforms");
-    DS_CHECK_ARG(!keep || known, "keep without known");
-    SampleParams p{logits, xt, t, u, sched, out_tokens, dbg_log_pred, dbg_trunc, dbg_post, B, L, T, initial, trunc_r,
-                   trunc_k, logits_rows};
-    const SampleRng g{gids, (unsigned)seed, (unsigned)(seed >> 32), call};
-    const int cols = B * L;
-    const dim3 grid((cols + 3) / 4);
-    if (keep) {
-        const SampleHold h{keep, known, mode};
-        if (K == 256 && u) hipLaunchKernelGGL((ds_sample_tail_hold_kernel<4, false>), grid, dim3(256), 0, stream, p, g, h);
-        else if (K == 256) hipLaunchKernelGGL((ds_sample_tail_hold_kernel<4, true>), grid, dim3(256), 0, stream, p, g, h);
-        else if (u) hipLaunchKernelGGL((ds_sample_tail_hold_kernel<8, false>), grid, dim3(256), 0, stream, p, g, h);
-        else hipLaunchKernelGGL((ds_sample_tail_hold_kernel<8, true>), grid, dim3(256), 0, stream, p, g, h);
-    } else if (K == 256 && u) hipLaunchKernelGGL((ds_sample_tail_kernel<4, false>), grid, dim3(256), 0, stream, p, g);
-    else if (K == 256) hipLaunchKernelGGL((ds_sample_tail_kernel<4, true>), grid, dim3(256), 0, stream, p, g);
-    else if (u) hipLaunchKernelGGL((ds_sample_tail_kernel<8, false>), grid, dim3(256), 0, stream, p, g);
-    else hipLaunchKernelGGL((ds_sample_tail_kernel<8, true>), grid, dim3(256), 0, stream, p, g);
-    DS_CHECK_LAUNCH();
-    return 0;
+// ---- the tails' host side: one description of a call (sampler.h TailCall), one checker, one launcher ----------------------
+// Every rule of every tail, stated once.  A field a form does not have stays zero in the TailCall and passes its rule.
+int ds_sample_tail_check(const TailCall& c) {
+    const bool purity = c.kind == DS_TAIL_PURITY, guided = c.logits_u != nullptr;
+    const char* msg =
+        !(c.logits && c.xt && (c.u || c.gids) && c.out_tokens && (purity ? c.scratch && c.B > 0 : c.t && c.sched))
+                                                                         ? "null pointer"
+        // (the unguided posterior tails never tested these three, and which calls are accepted is part of the ABI)
+        : (!purity && guided && !(c.B > 0 && c.L > 0 && c.T > 0))         ? "B, L and T must be positive"
+        : !(c.K == 256 || c.K == 512)                                     ? "codebook size must be 256 or 512"
+        : (purity && !(c.L > 0 && c.L <= DS_PURITY_MAX_L))                ? "L must be in 1 .. 288"
+        : !(c.logits_rows >= c.L && c.L < 65536)                          ? "logits rows per sample"
+        : (purity && c.remain < 0)                                        ? "remain must be >= 0"
+        : (purity && !(c.weight >= 0.f && c.weight - c.weight == 0.f))    ? "the purity weight must be finite and >= 0"
+        : (guided && !(c.scale - c.scale == 0.f))                         ? "the guidance scale must be finite"
+        : !(c.trunc_k >= 0 && !(c.trunc_k > 0 && c.trunc_r >= 0.f))       ? "top-k and top-r truncation are exclusive"
+        : !(c.mode == 0 || c.mode == 1)                                   ? "mode is 0 (clamp) or 1 (renoise)"
+        : (c.mode == 1 && c.u) ? "renoise draws from the caption's Philox stream: not with caller uniforms"
+        : (c.keep && !c.known)                                            ? "keep without known"
+                                                                          : nullptr;
+    if (!msg) return 0;
+    ds_set_error("%s: %s", c.who, msg);
+    return -1;
 }
 
-// the guided tails (see SampleGuide): logits_u has the rows of `logits` (same logits_rows); keep == nullptr: unheld.  `who`:
-// the public entry the messages name.
-int ds_sample_tail_rows_guided(const char* who, const float* logits, const float* logits_u, int logits_rows, const int64_t* xt,
-                               const int64_t* t, const float* u, const float* sched, int64_t* out_tokens, float* dbg_log_pred,
-                               float* dbg_trunc, float* dbg_post, int B, int L, int K, int T, int initial, float trunc_r,
-                               int trunc_k, float scale, ds_stream_t stream_, const int64_t* gids, unsigned long long seed,
-                               int call, const unsigned char* keep, const int64_t* known, int mode) {
-    hipStream_t stream = (hipStream_t)stream_;
-#define DS_GUIDED_ARG(cond, msg)                   \
-    do {                                           \
-        if (!(cond)) {                             \
-            ds_set_error("%s: %s", who, msg);      \
-            return -1;                             \
-        }                                          \
+// The (K, noise source) ladder, once: LAUNCH_(NPL, RNG) launches that instantiation of the call's kernel family.  The families
+// stand in the order held, plain, guided, purity because hipcc emits the kernels in the order of their first mention: it
+// is the order the code object has always had, which keeps its device code comparable byte for byte across host-side edits.
+#define DS_TAIL_LADDER(LAUNCH_)                   \
+    do {                                          \
+        if (c.K == 256 && c.u) LAUNCH_(4, false); \
+        else if (c.K == 256) LAUNCH_(4, true);    \
+        else if (c.u) LAUNCH_(8, false);          \
+        else LAUNCH_(8, true);                    \
     } while (0)
-    DS_GUIDED_ARG(logits && xt && t && (u || gids) && sched && out_tokens && B > 0 && L > 0 && T > 0, "null pointer");
-    DS_GUIDED_ARG(logits_u, "null logits_u (the null-condition logits)");
-    DS_GUIDED_ARG(scale - scale == 0.f, "the guidance scale must be finite");
-    DS_GUIDED_ARG(K == 256 || K == 512, "codebook size must be 256 or 512");
-    DS_GUIDED_ARG(trunc_k >= 0 && !(trunc_k > 0 && trunc_r >= 0.f), "top-k and top-r truncation are exclusive");
-    DS_GUIDED_ARG(logits_rows >= L && L < 65536, "logits rows per sample");
-    DS_GUIDED_ARG(mode == 0 || mode == 1, "mode is 0 (clamp) or 1 (renoise)");
-    DS_GUIDED_ARG(!(mode == 1 && u), "renoise draws from the caption's Philox stream: not with caller uniforms");
-    DS_GUIDED_ARG(!keep || known, "keep without known");
-#undef DS_GUIDED_ARG
-    SampleParams p{logits, xt, t, u, sched, out_tokens, dbg_log_pred, dbg_trunc, dbg_post, B, L, T, initial, trunc_r,
-                   trunc_k, logits_rows};
-    const SampleRng g{gids, (unsigned)seed, (unsigned)(seed >> 32), call};
-    const SampleHold h{keep, known, mode};
-    const SampleGuide gd{logits_u, scale};
-    const dim3 grid((B * L + 3) / 4);
-    if (K == 256 && u) hipLaunchKernelGGL((ds_sample_tail_guided_kernel<4, false>), grid, dim3(256), 0, stream, p, g, h, gd);
-    else if (K == 256) hipLaunchKernelGGL((ds_sample_tail_guided_kernel<4, true>), grid, dim3(256), 0, stream, p, g, h, gd);
-    else if (u) hipLaunchKernelGGL((ds_sample_tail_guided_kernel<8, false>), grid, dim3(256), 0, stream, p, g, h, gd);
-    else hipLaunchKernelGGL((ds_sample_tail_guided_kernel<8, true>), grid, dim3(256), 0, stream, p, g, h, gd);
-    DS_CHECK_LAUNCH();
+#define DS_TAIL_HOLD(NPL_, RNG_) hipLaunchKernelGGL((ds_sample_tail_hold_kernel<NPL_, RNG_>), grid, block, 0, stream, p, g, h)
+#define DS_TAIL_PLAIN(NPL_, RNG_) hipLaunchKernelGGL((ds_sample_tail_kernel<NPL_, RNG_>), grid, block, 0, stream, p, g)
+#define DS_TAIL_GUIDED(NPL_, RNG_) \
+    hipLaunchKernelGGL((ds_sample_tail_guided_kernel<NPL_, RNG_>), grid, block, 0, stream, p, g, h, gd)
+#define DS_TAIL_PURITY(NPL_, RNG_)                                                                                           \
+    do {                                                                                                                     \
+        if (guided) hipLaunchKernelGGL((ds_sample_purity_rows_kernel<NPL_, RNG_, true>), grid, block, 0, stream, p, g, gd, pu); \
+        else hipLaunchKernelGGL((ds_sample_purity_rows_kernel<NPL_, RNG_, false>), grid, block, 0, stream, p, g, gd, pu);   \
+    } while (0)
+
+int ds_sample_tail_launch(const TailCall& c) {
+    hipStream_t stream = (hipStream_t)c.stream;
+    const bool purity = c.kind == DS_TAIL_PURITY, guided = c.logits_u != nullptr;
+    const long long cols = (long long)c.B * c.L;
+    int* cand = (int*)c.scratch;                             // purity: the rows kernel leaves (candidate, key) per grid position
+    float* key = purity ? (float*)(cand + cols) : nullptr;   //   here, and the select kernel writes the tokens
+    const SampleParams p{c.logits, c.xt, c.t, c.u, c.sched, purity ? nullptr : c.out_tokens, c.dbg_log_pred, c.dbg_trunc,
+                         c.dbg_post, c.B, c.L, c.T, c.initial, c.trunc_r, c.trunc_k, c.logits_rows};
+    const SampleRng g{c.gids, (unsigned)c.seed, (unsigned)(c.seed >> 32), c.call};
+    const SampleHold h{c.keep, c.known, c.mode};             // the guided kernels take it with keep == nullptr: unheld
+    const SampleGuide gd{c.logits_u, c.scale};
+    const SamplePurity pu{cand, key, c.dbg_sharp, c.weight};
+    const dim3 grid((unsigned)((cols + 3) / 4)), block(256);
+    if (!purity && !guided && c.keep) DS_TAIL_LADDER(DS_TAIL_HOLD);
+    else if (!purity && !guided) DS_TAIL_LADDER(DS_TAIL_PLAIN);
+    else if (!purity) DS_TAIL_LADDER(DS_TAIL_GUIDED);
+    else DS_TAIL_LADDER(DS_TAIL_PURITY);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && purity) {
+        hipLaunchKernelGGL(ds_sample_purity_select_kernel, dim3(c.B), dim3(256), 0, stream, c.xt, (const int*)cand,
+                           (const float*)key, c.out_tokens, c.L, c.K, c.remain);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        ds_set_error("%s: launch failed: %s", c.who, hipGetErrorString(e));
+        return -2;
+    }
+    if (c.dbg_key) e = hipMemcpyAsync(c.dbg_key, key, cols * sizeof(float), hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess && c.dbg_cand) e = hipMemcpyAsync(c.dbg_cand, cand, cols * sizeof(int), hipMemcpyDeviceToDevice, stream);
+    if (e != hipSuccess) {
+        ds_set_error("%s: hipMemcpyAsync: %s", c.who, hipGetErrorString(e));
+        return -2;
+    }
     return 0;
 }
+#undef DS_TAIL_LADDER
+#undef DS_TAIL_HOLD
+#undef DS_TAIL_PLAIN
+#undef DS_TAIL_GUIDED
+#undef DS_TAIL_PURITY
 
-extern "C" int ds_sample_tail_guided(const float* logits_c, const float* logits_u, const int64_t* xt, const int64_t* t,
-                                     const float* u, const float* sched, int64_t* out_tokens, float* dbg_log_pred,
-                                     float* dbg_trunc, float* dbg_post, int B, int L, int K, int T, int initial,
-                                     float trunc_r, int trunc_k, float scale, const unsigned char* keep,
-                                     const int64_t* known, int mode, ds_stream_t stream) {
-    DS_CHECK_ARG(u, "null pointer");
-    return ds_sample_tail_rows_guided(__func__, logits_c, logits_u, L, xt, t, u, sched, out_tokens, dbg_log_pred, dbg_trunc,
-                                      dbg_post, B, L, K, T, initial, trunc_r, trunc_k, scale, stream, nullptr, 0ull, 0, keep,
-                                      known, mode);
+static int tail_run(const TailCall& c) {
+    const int rc = ds_sample_tail_check(c);
+    return rc ? rc : ds_sample_tail_launch(c);
 }
 
-extern "C" int ds_sample_tail_guided_rng(const float* logits_c, const float* logits_u, const int64_t* xt, const int64_t* t,
-                                         const int64_t* gids, unsigned long long seed, int call, const float* sched,
-                                         int64_t* out_tokens, int B, int L, int K, int T, int initial, float trunc_r,
-                                         int trunc_k, float scale, const unsigned char* keep, const int64_t* known, int mode,
-                                         ds_stream_t stream) {
-    DS_CHECK_ARG(gids, "null pointer");
-    return ds_sample_tail_rows_guided(__func__, logits_c, logits_u, L, xt, t, nullptr, sched, out_tokens, nullptr, nullptr,
-                                      nullptr, B, L, K, T, initial, trunc_r, trunc_k, scale, stream, gids, seed, call, keep,
-                                      known, mode);
-}
-
-int ds_sample_tail_rows(const float* logits, int logits_rows, const int64_t* xt, const int64_t* t, const float* u,
-                        const float* sched, int64_t* out_tokens, float* dbg_log_pred, float* dbg_trunc, float* dbg_post,
-                        int B, int L, int K, int T, int initial, float trunc_r, int trunc_k, ds_stream_t stream,
-                        const int64_t* gids, unsigned long long seed, int call) {
-    return ds_sample_tail_rows_hold(logits, logits_rows, xt, t, u, sched, out_tokens, dbg_log_pred, dbg_trunc, dbg_post, B, L, K,
-                                    T, initial, trunc_r, trunc_k, stream, gids, seed, call, nullptr, nullptr, 0);
-}
-
-// region-held tails (see SampleHold): ds_sample_tail_ex / ds_sample_tail_rng + keep, known, mode
-extern "C" int ds_sample_tail_hold(const float* logits, const int64_t* xt, const int64_t* t, const float* u,
-                                   const float* sched, int64_t* out_tokens, float* dbg_log_pred, float* dbg_trunc,
-                                   float* dbg_post, int B, int L, int K, int T, int initial, float trunc_r, int trunc_k,
-                                   const unsigned char* keep, const int64_t* known, int mode, ds_stream_t stream) {
-    DS_CHECK_ARG(u, "null pointer");
-    return ds_sample_tail_rows_hold(logits, L, xt, t, u, sched, out_tokens, dbg_log_pred, dbg_trunc, dbg_post, B, L, K, T,
-                                    initial, trunc_r, trunc_k, stream, nullptr, 0ull, 0, keep, known, mode);
-}
-
-extern "C" int ds_sample_tail_hold_rng(const float* logits, const int64_t* xt, const int64_t* t, const int64_t* gids,
-                                       unsigned long long seed, int call, const float* sched, int64_t* out_tokens, int B,
-                                       int L, int K, int T, int initial, float trunc_r, int trunc_k,
-                                       const unsigned char* keep, const int64_t* known, int mode, ds_stream_t stream) {
-    DS_CHECK_ARG(gids, "null pointer");
-    return ds_sample_tail_rows_hold(logits, L, xt, t, nullptr, sched, out_tokens, nullptr, nullptr, nullptr, B, L, K, T,
-                                    initial, trunc_r, trunc_k, stream, gids, seed, call, keep, known, mode);
-}
-
+// ---- the public tail entries: fill a TailCall, the entry's own null test (u for the uniform forms, gids for the _rng
+// forms, logits_u for the guided ones: in a TailCall a null logits_u means unguided), check and launch
 extern "C" int ds_sample_tail_ex(const float* logits, const int64_t* xt, const int64_t* t, const float* u,
                                  const float* sched, int64_t* out_tokens, float* dbg_log_pred, float* dbg_trunc,
                                  float* dbg_post, int B, int L, int K, int T, int initial, float trunc_r,
                                  int trunc_k, ds_stream_t stream) {
     DS_CHECK_ARG(u, "null pointer");
-    return ds_sample_tail_rows(logits, L, xt, t, u, sched, out_tokens, dbg_log_pred, dbg_trunc, dbg_post, B, L, K, T, initial,
-                               trunc_r, trunc_k, stream, nullptr, 0ull, 0);
-}
-
-extern "C" int ds_sample_tail_rng(const float* logits, const int64_t* xt, const int64_t* t, const int64_t* gids,
-                                  unsigned long long seed, int call, const float* sched, int64_t* out_tokens, int B,
-                                  int L, int K, int T, int initial, float trunc_r, int trunc_k, ds_stream_t stream) {
-    DS_CHECK_ARG(gids, "null pointer");
-    return ds_sample_tail_rows(logits, L, xt, t, nullptr, sched, out_tokens, nullptr, nullptr, nullptr, B, L, K, T, initial,
-                               trunc_r, trunc_k, stream, gids, seed, call);
+    TailCall c{__func__, DS_TAIL_POSTERIOR, stream};
+    c.logits = logits; c.logits_rows = L; c.xt = xt; c.t = t; c.u = u; c.sched = sched; c.out_tokens = out_tokens;
+    c.dbg_log_pred = dbg_log_pred; c.dbg_trunc = dbg_trunc; c.dbg_post = dbg_post;
+    c.B = B; c.L = L; c.K = K; c.T = T; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    return tail_run(c);
 }
 
 extern "C" int ds_sample_tail(const float* logits, const int64_t* xt, const int64_t* t, const float* u,
@@ -1028,66 +994,78 @@ extern "C" int ds_sample_tail(const float* logits, const int64_t* xt, const int6
                              trunc_r, 0, stream);
 }
 
-// ---- purity-prior tails (see SamplePurity): the argument rules, and the two launches.  `who`: the public entry the messages name.
-int ds_sample_tail_purity_check(const char* who, bool pointers, bool guided, float scale, int remain, float weight, float trunc_r,
-                                int trunc_k, int logits_rows, int L, int K) {
-    const char* msg = !pointers                                        ? "null pointer"
-                      : !(K == 256 || K == 512)                        ? "codebook size must be 256 or 512"
-                      : !(L > 0 && L <= DS_PURITY_MAX_L)               ? "L must be in 1 .. 288"
-                      : logits_rows < L                                ? "logits rows per sample"
-                      : remain < 0                                     ? "remain must be >= 0"
-                      : !(weight >= 0.f && weight - weight == 0.f)     ? "the purity weight must be finite and >= 0"
-                      : (guided && !(scale - scale == 0.f))            ? "the guidance scale must be finite"
-                      : !(trunc_k >= 0 && !(trunc_k > 0 && trunc_r >= 0.f)) ? "top-k and top-r truncation are exclusive"
-                                                                       : nullptr;
-    if (!msg) return 0;
-    ds_set_error("%s: %s", who, msg);
-    return -1;
+extern "C" int ds_sample_tail_rng(const float* logits, const int64_t* xt, const int64_t* t, const int64_t* gids,
+                                  unsigned long long seed, int call, const float* sched, int64_t* out_tokens, int B,
+                                  int L, int K, int T, int initial, float trunc_r, int trunc_k, ds_stream_t stream) {
+    DS_CHECK_ARG(gids, "null pointer");
+    TailCall c{__func__, DS_TAIL_POSTERIOR, stream};
+    c.logits = logits; c.logits_rows = L; c.xt = xt; c.t = t; c.sched = sched; c.out_tokens = out_tokens;
+    c.gids = gids; c.seed = seed; c.call = call;
+    c.B = B; c.L = L; c.K = K; c.T = T; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    return tail_run(c);
 }
 
+// region-held tails (see SampleHold): ds_sample_tail_ex / ds_sample_tail_rng + keep, known, mode
+extern "C" int ds_sample_tail_hold(const float* logits, const int64_t* xt, const int64_t* t, const float* u,
+                                   const float* sched, int64_t* out_tokens, float* dbg_log_pred, float* dbg_trunc,
+                                   float* dbg_post, int B, int L, int K, int T, int initial, float trunc_r, int trunc_k,
+                                   const unsigned char* keep, const int64_t* known, int mode, ds_stream_t stream) {
+    DS_CHECK_ARG(u, "null pointer");
+    TailCall c{__func__, DS_TAIL_POSTERIOR, stream};
+    c.logits = logits; c.logits_rows = L; c.xt = xt; c.t = t; c.u = u; c.sched = sched; c.out_tokens = out_tokens;
+    c.dbg_log_pred = dbg_log_pred; c.dbg_trunc = dbg_trunc; c.dbg_post = dbg_post;
+    c.B = B; c.L = L; c.K = K; c.T = T; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    c.keep = keep; c.known = known; c.mode = mode;
+    return tail_run(c);
+}
+
+extern "C" int ds_sample_tail_hold_rng(const float* logits, const int64_t* xt, const int64_t* t, const int64_t* gids,
+                                       unsigned long long seed, int call, const float* sched, int64_t* out_tokens, int B,
+                                       int L, int K, int T, int initial, float trunc_r, int trunc_k,
+                                       const unsigned char* keep, const int64_t* known, int mode, ds_stream_t stream) {
+    DS_CHECK_ARG(gids, "null pointer");
+    TailCall c{__func__, DS_TAIL_POSTERIOR, stream};
+    c.logits = logits; c.logits_rows = L; c.xt = xt; c.t = t; c.sched = sched; c.out_tokens = out_tokens;
+    c.gids = gids; c.seed = seed; c.call = call;
+    c.B = B; c.L = L; c.K = K; c.T = T; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    c.keep = keep; c.known = known; c.mode = mode;
+    return tail_run(c);
+}
+
+// the guided tails (see SampleGuide): logits_u has the rows of logits_c; keep == nullptr: unheld
+extern "C" int ds_sample_tail_guided(const float* logits_c, const float* logits_u, const int64_t* xt, const int64_t* t,
+                                     const float* u, const float* sched, int64_t* out_tokens, float* dbg_log_pred,
+                                     float* dbg_trunc, float* dbg_post, int B, int L, int K, int T, int initial,
+                                     float trunc_r, int trunc_k, float scale, const unsigned char* keep,
+                                     const int64_t* known, int mode, ds_stream_t stream) {
+    DS_CHECK_ARG(u && logits_u, "null pointer (logits_u: the null-condition logits)");
+    TailCall c{__func__, DS_TAIL_POSTERIOR, stream};
+    c.logits = logits_c; c.logits_u = logits_u; c.scale = scale; c.logits_rows = L;
+    c.xt = xt; c.t = t; c.u = u; c.sched = sched; c.out_tokens = out_tokens;
+    c.dbg_log_pred = dbg_log_pred; c.dbg_trunc = dbg_trunc; c.dbg_post = dbg_post;
+    c.B = B; c.L = L; c.K = K; c.T = T; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    c.keep = keep; c.known = known; c.mode = mode;
+    return tail_run(c);
+}
+
+extern "C" int ds_sample_tail_guided_rng(const float* logits_c, const float* logits_u, const int64_t* xt, const int64_t* t,
+                                         const int64_t* gids, unsigned long long seed, int call, const float* sched,
+                                         int64_t* out_tokens, int B, int L, int K, int T, int initial, float trunc_r,
+                                         int trunc_k, float scale, const unsigned char* keep, const int64_t* known, int mode,
+                                         ds_stream_t stream) {
+    DS_CHECK_ARG(gids && logits_u, "null pointer (logits_u: the null-condition logits)");
+    TailCall c{__func__, DS_TAIL_POSTERIOR, stream};
+    c.logits = logits_c; c.logits_u = logits_u; c.scale = scale; c.logits_rows = L;
+    c.xt = xt; c.t = t; c.sched = sched; c.out_tokens = out_tokens;
+    c.gids = gids; c.seed = seed; c.call = call;
+    c.B = B; c.L = L; c.K = K; c.T = T; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    c.keep = keep; c.known = known; c.mode = mode;
+    return tail_run(c);
+}
+
+// ---- purity-prior tails (see SamplePurity)
 extern "C" int64_t ds_purity_scratch_bytes(int B, int L) {
     return B > 0 && L > 0 ? (int64_t)B * L * (int64_t)(sizeof(int) + sizeof(float)) : -1;
-}
-
-int ds_sample_tail_purity_rows(const char* who, const float* logits, const float* logits_u, float scale, int logits_rows,
-                               const int64_t* xt, const float* u, const int64_t* gids, unsigned long long seed, int call,
-                               int remain, float weight, float trunc_r, int trunc_k, void* scratch, int64_t* out_tokens,
-                               float* dbg_sharp, float* dbg_key, int32_t* dbg_cand, int B, int L, int K, ds_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (ds_sample_tail_purity_check(who, logits && xt && (u || gids) && scratch && out_tokens && B > 0, logits_u != nullptr, scale,
-                                    remain, weight, trunc_r, trunc_k, logits_rows, L, K))
-        return -1;
-    const size_t cols = (size_t)B * L;
-    int* cand = (int*)scratch;
-    float* key = (float*)(cand + cols);
-    SampleParams p{logits, xt, nullptr, u, nullptr, nullptr, nullptr, nullptr, nullptr, B, L, 0, 0, trunc_r, trunc_k, logits_rows};
-    const SampleRng g{gids, (unsigned)seed, (unsigned)(seed >> 32), call};
-    const SampleGuide gd{logits_u, scale};
-    const SamplePurity pu{cand, key, dbg_sharp, weight};
-    const dim3 grid((unsigned)((cols + 3) / 4));
-#define DS_PURITY_LAUNCH(NPL_, RNG_)                                                                                                \
-    do {                                                                                                                            \
-        if (logits_u) hipLaunchKernelGGL((ds_sample_purity_rows_kernel<NPL_, RNG_, true>), grid, dim3(256), 0, stream, p, g, gd, pu); \
-        else hipLaunchKernelGGL((ds_sample_purity_rows_kernel<NPL_, RNG_, false>), grid, dim3(256), 0, stream, p, g, gd, pu);         \
-    } while (0)
-    if (K == 256 && u) DS_PURITY_LAUNCH(4, false);
-    else if (K == 256) DS_PURITY_LAUNCH(4, true);
-    else if (u) DS_PURITY_LAUNCH(8, false);
-    else DS_PURITY_LAUNCH(8, true);
-#undef DS_PURITY_LAUNCH
-    DS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ds_sample_purity_select_kernel, dim3(B), dim3(256), 0, stream, xt, (const int*)cand, (const float*)key,
-                       out_tokens, L, K, remain);
-    DS_CHECK_LAUNCH();
-    if (dbg_key || dbg_cand) {
-        hipError_t e = dbg_key ? hipMemcpyAsync(dbg_key, key, cols * sizeof(float), hipMemcpyDeviceToDevice, stream) : hipSuccess;
-        if (e == hipSuccess && dbg_cand) e = hipMemcpyAsync(dbg_cand, cand, cols * sizeof(int), hipMemcpyDeviceToDevice, stream);
-        if (e != hipSuccess) {
-            ds_set_error("%s: hipMemcpyAsync: %s", who, hipGetErrorString(e));
-            return -2;
-        }
-    }
-    return 0;
 }
 
 extern "C" int ds_sample_tail_purity(const float* logits, const float* logits_u, float scale, const int64_t* xt, const float* u,
@@ -1095,8 +1073,13 @@ extern "C" int ds_sample_tail_purity(const float* logits, const float* logits_u,
                                      int64_t* out_tokens, float* dbg_sharp, float* dbg_key, int32_t* dbg_cand, int B, int L,
                                      int K, ds_stream_t stream) {
     DS_CHECK_ARG(u, "null pointer");
-    return ds_sample_tail_purity_rows(__func__, logits, logits_u, scale, lrows, xt, u, nullptr, 0ull, 0, remain, weight, trunc_r,
-                                      trunc_k, scratch, out_tokens, dbg_sharp, dbg_key, dbg_cand, B, L, K, stream);
+    TailCall c{__func__, DS_TAIL_PURITY, stream};
+    c.logits = logits; c.logits_u = logits_u; c.scale = scale; c.logits_rows = lrows;
+    c.xt = xt; c.u = u; c.out_tokens = out_tokens;
+    c.B = B; c.L = L; c.K = K; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    c.remain = remain; c.weight = weight; c.scratch = scratch;
+    c.dbg_sharp = dbg_sharp; c.dbg_key = dbg_key; c.dbg_cand = dbg_cand;
+    return tail_run(c);
 }
 
 extern "C" int ds_sample_tail_purity_rng(const float* logits, const float* logits_u, float scale, const int64_t* xt,
@@ -1105,6 +1088,13 @@ extern "C" int ds_sample_tail_purity_rng(const float* logits, const float* logit
                                          float* dbg_sharp, float* dbg_key, int32_t* dbg_cand, int B, int L, int K,
                                          ds_stream_t stream) {
     DS_CHECK_ARG(gids, "null pointer");
-    return ds_sample_tail_purity_rows(__func__, logits, logits_u, scale, lrows, xt, nullptr, gids, seed, call, remain, weight,
-                                      trunc_r, trunc_k, scratch, out_tokens, dbg_sharp, dbg_key, dbg_cand, B, L, K, stream);
+    TailCall c{__func__, DS_TAIL_PURITY, stream};
+    c.logits = logits; c.logits_u = logits_u; c.scale = scale; c.logits_rows = lrows;
+    c.xt = xt; c.out_tokens = out_tokens;
+    c.gids = gids; c.seed = seed; c.call = call;
+    c.B = B; c.L = L; c.K = K; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    c.remain = remain; c.weight = weight; c.scratch = scratch;
+    c.dbg_sharp = dbg_sharp; c.dbg_key = dbg_key; c.dbg_cand = dbg_cand;
+    return tail_run(c);
 }
+

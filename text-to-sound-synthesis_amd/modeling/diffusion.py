@@ -186,6 +186,48 @@ class DiffusionTransformer(nn.Module):
         oh = torch.nn.functional.one_hot(tok, self.num_classes).permute(0, 2, 1).float()
         return torch.log(oh.clamp(min=1e-30))
 
+    def _seed(self, seed):
+        return int(self.sample_seed if seed is None else seed)
+
+    def _result(self, x, return_logits):
+        out = {"content_token": x}
+        if return_logits:
+            out["logits"] = torch.nn.functional.one_hot(x, self.num_classes).permute(0, 2, 1).float()
+        return out
+
+    def _step_entry(self, chain, noise, B, initial, hold, guide, slot=0):
+        """The C entry of one reverse step (chain False: ds_denoiser_step_*) or of a whole chain (True: ds_denoiser_sample_*)
+        and the arguments its forms share.  noise: the uniforms u, or (caption_ids, call, seed) for the in-kernel Philox draw;
+        hold: None or (keep, known, mode) -- plain and held are different entries; guide: None or (kv2, scale, tokens2).
+        Returns (entry, the noise arguments, the arguments from B to the workspace); the caller's part is what comes
+        before (handle, tokens, timesteps, kv) and after (the step's output tokens, the stream)."""
+        rng = isinstance(noise, tuple)
+        family = "_guided" if guide is not None else "_hold" if hold is not None else ""
+        name = "ds_denoiser_%s%s%s" % ("sample" if chain else "step", family, "_rng" if rng else "" if family else "_ex")
+        r, k = self._truncation()
+        args = [B, 0 if hold is not None else int(initial), r, k]
+        if guide is not None:
+            args.append(float(guide[1]))
+        if family:
+            keep, known, mode = hold if hold is not None else (None, None, 0)
+            args += [_lib.ptr(keep), _lib.ptr(known), int(mode)]
+        if guide is not None:
+            args.append(_lib.ptr(guide[2]))
+        args.append(_lib.ptr(self.transformer.workspace(2 * B if guide is not None else B, self._schedule_table(), slot)))
+        noise = [_lib.ptr(noise[0]), self._seed(noise[2]), int(noise[1])] if rng else [_lib.ptr(noise)]
+        return getattr(_lib.lib(), name), noise, args
+
+    def _p_sample(self, x_t, kv, t, noise, initial, out, t_post, slot, hold, guide):
+        p = self.transformer.packed(self._schedule_table())
+        if out is None:
+            out = torch.empty_like(x_t)
+        if guide is not None:                        # (named: alive until the launch is enqueued)
+            kv, t, t_post = guide[0], t.repeat(2), None if t_post is None else t_post.repeat(2)
+        entry, noise, args = self._step_entry(False, noise, x_t.shape[0], initial, hold, guide, slot)
+        _lib.check(entry(p["handle"], _lib.ptr(x_t), _lib.ptr(t), _lib.ptr(t_post), _lib.ptr(kv), *noise, *args, _lib.ptr(out),
+                         _lib.stream()))
+        return out
+
     @torch.no_grad()
     def p_sample_tokens(self, x_t, kv, t, u, initial, out=None, t_post=None, slot=0, hold=None, guide=None):
         """x_t i64[B,L] -> x_{t-1} i64[B,L]; kv from transformer.condition_kv().  t_post: the posterior's timestep
@@ -193,66 +235,14 @@ class DiffusionTransformer(nn.Module):
         region-held step (_hold_start); on caller uniforms only mode 0 (clamp) exists.  guide: (kv2, scale, tokens2) of
         the guided step (_guide_start: the K/V of captions + null conditions at batch 2B, the guidance scale, an
         i64[2B,L] scratch); kv is not read then."""
-        tr = self.transformer
-        sched = self._schedule_table()
-        p = tr.packed(sched)
-        B = x_t.shape[0]
-        if out is None:
-            out = torch.empty_like(x_t)
-        r, k = self._truncation()
-        if guide is not None:
-            kv2, scale, tokens2 = guide
-            t2, tp2 = t.repeat(2), None if t_post is None else t_post.repeat(2)     # named: alive until the launch is enqueued
-            keep, known, mode = hold if hold is not None else (None, None, 0)
-            _lib.check(_lib.lib().ds_denoiser_step_guided(
-                p["handle"], _lib.ptr(x_t), _lib.ptr(t2), _lib.ptr(tp2), _lib.ptr(kv2), _lib.ptr(u), B,
-                0 if hold is not None else int(initial), r, k, float(scale), _lib.ptr(keep), _lib.ptr(known), int(mode),
-                _lib.ptr(tokens2), _lib.ptr(tr.workspace(2 * B, sched, slot)), _lib.ptr(out), _lib.stream()))
-            return out
-        if hold is not None:
-            _lib.check(_lib.lib().ds_denoiser_step_hold(
-                p["handle"], _lib.ptr(x_t), _lib.ptr(t), _lib.ptr(t_post), _lib.ptr(kv), _lib.ptr(u), B, 0, r, k,
-                _lib.ptr(hold[0]), _lib.ptr(hold[1]), int(hold[2]), _lib.ptr(tr.workspace(B, sched, slot)), _lib.ptr(out),
-                _lib.stream()))
-            return out
-        _lib.check(_lib.lib().ds_denoiser_step_ex(p["handle"], _lib.ptr(x_t), _lib.ptr(t), _lib.ptr(t_post), _lib.ptr(kv),
-                                                  _lib.ptr(u), B, int(initial), r, k,
-                                                  _lib.ptr(tr.workspace(B, sched, slot)), _lib.ptr(out), _lib.stream()))
-        return out
+        return self._p_sample(x_t, kv, t, u, initial, out, t_post, slot, hold, guide)
 
     @torch.no_grad()
     def p_sample_tokens_rng(self, x_t, kv, t, caption_ids, call, initial, out=None, t_post=None, slot=0, seed=None,
                             hold=None, guide=None):
         """p_sample_tokens with the noise drawn in the kernel: Philox stream of (seed, caption_ids[b], call).  hold and
         guide as in p_sample_tokens, mode 1 (renoise) included."""
-        tr = self.transformer
-        sched = self._schedule_table()
-        p = tr.packed(sched)
-        B = x_t.shape[0]
-        if out is None:
-            out = torch.empty_like(x_t)
-        r, k = self._truncation()
-        if guide is not None:
-            kv2, scale, tokens2 = guide
-            t2, tp2 = t.repeat(2), None if t_post is None else t_post.repeat(2)
-            keep, known, mode = hold if hold is not None else (None, None, 0)
-            _lib.check(_lib.lib().ds_denoiser_step_guided_rng(
-                p["handle"], _lib.ptr(x_t), _lib.ptr(t2), _lib.ptr(tp2), _lib.ptr(kv2), _lib.ptr(caption_ids),
-                int(self.sample_seed if seed is None else seed), int(call), B, 0 if hold is not None else int(initial), r, k,
-                float(scale), _lib.ptr(keep), _lib.ptr(known), int(mode), _lib.ptr(tokens2),
-                _lib.ptr(tr.workspace(2 * B, sched, slot)), _lib.ptr(out), _lib.stream()))
-            return out
-        if hold is not None:
-            _lib.check(_lib.lib().ds_denoiser_step_hold_rng(
-                p["handle"], _lib.ptr(x_t), _lib.ptr(t), _lib.ptr(t_post), _lib.ptr(kv), _lib.ptr(caption_ids),
-                int(self.sample_seed if seed is None else seed), int(call), B, 0, r, k, _lib.ptr(hold[0]),
-                _lib.ptr(hold[1]), int(hold[2]), _lib.ptr(tr.workspace(B, sched, slot)), _lib.ptr(out), _lib.stream()))
-            return out
-        _lib.check(_lib.lib().ds_denoiser_step_rng(
-            p["handle"], _lib.ptr(x_t), _lib.ptr(t), _lib.ptr(t_post), _lib.ptr(kv), _lib.ptr(caption_ids),
-            int(self.sample_seed if seed is None else seed), int(call), B, int(initial), r, k,
-            _lib.ptr(tr.workspace(B, sched, slot)), _lib.ptr(out), _lib.stream()))
-        return out
+        return self._p_sample(x_t, kv, t, (caption_ids, call, seed), initial, out, t_post, slot, hold, guide)
 
     def _caption_ids(self, caption_ids, B, device):
         """i64[B] global caption ids on the device (default: 0 .. B-1)."""
@@ -425,7 +415,7 @@ class DiffusionTransformer(nn.Module):
             t = torch.full((B,), self.num_timesteps - 1, device=device, dtype=torch.long)
             xs = torch.empty_like(known)
             _lib.check(_lib.lib().ds_q_sample_rng(_lib.ptr(known), _lib.ptr(t), _lib.ptr(caption_ids),
-                                                  int(self.sample_seed if seed is None else seed), 0,
+                                                  self._seed(seed), 0,
                                                   _lib.ptr(self._schedule_table()), _lib.ptr(xs), B, L, K,
                                                   self.num_timesteps, _lib.stream()))
             x = torch.where(keep, xs, torch.full_like(known, K))
@@ -500,55 +490,27 @@ class DiffusionTransformer(nn.Module):
             x = torch.full((B, L), K1 - 1, device=device, dtype=torch.long)  # all [MASK]
         else:
             x = start_tokens.to(device).clone()
-        if noise_fn is None and (caption_ids is not None or self.rng_mode == "philox"):
-            # in-kernel noise: the whole chain is one C call, nothing returns to Python between steps
-            calls = []
-            for step, step_post in steps:
-                reps = 2 if (self.repeat_rate is not None and random.random() < self.repeat_rate) else 1
-                calls += [(step, step_post)] * reps
-            sched = self._schedule_table()
-            tr = self.transformer
-            p = tr.packed(sched)
-            gids = self._caption_ids(caption_ids, B, device)
-            tmp = torch.empty_like(x)
-            r, k = self._truncation()
-            sd = int(self.sample_seed if seed is None else seed)
-            t_steps = torch.tensor(calls, dtype=torch.long, device=device).view(-1, 2, 1)
-            if guide is not None:
-                kv2, scale, tokens2 = self._guide_start(guide, cond_emb, sched)
-                t_steps = t_steps.expand(-1, 2, 2 * B).contiguous()
-                keep_, known_, mode_ = hold if hold is not None else (None, None, 0)
-                _lib.check(_lib.lib().ds_denoiser_sample_guided_rng(
-                    p["handle"], _lib.ptr(x), _lib.ptr(tmp), _lib.ptr(t_steps), len(calls), _lib.ptr(kv2), _lib.ptr(gids), sd,
-                    1 if mode_ == 1 else 0, B, 0 if hold is not None else int(start_tokens is None), r, k, scale,
-                    _lib.ptr(keep_), _lib.ptr(known_), int(mode_), _lib.ptr(tokens2), _lib.ptr(tr.workspace(2 * B, sched, 0)),
-                    _lib.stream()))
-                out = {"content_token": x}
-                if return_logits:
-                    out["logits"] = torch.nn.functional.one_hot(x, K1).permute(0, 2, 1).float()
-                return out
-            kv = tr.condition_kv(cond_emb.contiguous(), sched)
-            t_steps = t_steps.expand(-1, 2, B).contiguous()
-            if hold is not None:        # (renoise: stream-1 call 0 was the start state's q_sample, so the calls start at 1)
-                _lib.check(_lib.lib().ds_denoiser_sample_hold_rng(
-                    p["handle"], _lib.ptr(x), _lib.ptr(tmp), _lib.ptr(t_steps), len(calls), _lib.ptr(kv), _lib.ptr(gids),
-                    int(self.sample_seed if seed is None else seed), 1 if hold[2] == 1 else 0, B, 0, r, k,
-                    _lib.ptr(hold[0]), _lib.ptr(hold[1]), int(hold[2]), _lib.ptr(tr.workspace(B, sched, 0)), _lib.stream()))
-            else:
-                _lib.check(_lib.lib().ds_denoiser_sample_rng(
-                    p["handle"], _lib.ptr(x), _lib.ptr(tmp), _lib.ptr(t_steps), len(calls), _lib.ptr(kv), _lib.ptr(gids),
-                    int(self.sample_seed if seed is None else seed), 0, B, int(start_tokens is None), r, k,
-                    _lib.ptr(tr.workspace(B, sched, 0)), _lib.stream()))
-            out = {"content_token": x}
-            if return_logits:
-                out["logits"] = torch.nn.functional.one_hot(x, K1).permute(0, 2, 1).float()
-            return out
         sched = self._schedule_table()
         if guide is not None:
             kv, guide = None, self._guide_start(guide, cond_emb, sched)
         else:
             kv = self.transformer.condition_kv(cond_emb.contiguous(), sched)
         nxt = torch.empty_like(x)
+        if noise_fn is None and (caption_ids is not None or self.rng_mode == "philox"):
+            # in-kernel noise: the whole chain is one C call, nothing returns to Python between steps
+            calls = []
+            for step, step_post in steps:
+                reps = 2 if (self.repeat_rate is not None and random.random() < self.repeat_rate) else 1
+                calls += [(step, step_post)] * reps
+            p = self.transformer.packed(sched)
+            gids = self._caption_ids(caption_ids, B, device)
+            t_steps = torch.tensor(calls, dtype=torch.long, device=device).view(-1, 2, 1)
+            t_steps = t_steps.expand(-1, 2, 2 * B if guide is not None else B).contiguous()
+            call0 = 1 if hold is not None and hold[2] == 1 else 0   # renoise: stream-1 call 0 was the start state's q_sample
+            entry, noise, args = self._step_entry(True, (gids, call0, seed), B, start_tokens is None, hold, guide)
+            _lib.check(entry(p["handle"], _lib.ptr(x), _lib.ptr(nxt), _lib.ptr(t_steps), len(calls),
+                             _lib.ptr(kv if guide is None else guide[0]), *noise, *args, _lib.stream()))
+            return self._result(x, return_logits)
         calls = 0
         for i, (step, step_post) in enumerate(steps):
             repeats = 2 if (self.repeat_rate is not None and random.random() < self.repeat_rate) else 1
@@ -565,10 +527,7 @@ class DiffusionTransformer(nn.Module):
                 self.p_sample_tokens(x, kv, t, u, initial=(start_tokens is None and i == 0 and rep == 0), out=nxt, t_post=tp,
                                      hold=hold, **kw)
                 x, nxt = nxt, x
-        out = {"content_token": x}
-        if return_logits:
-            out["logits"] = torch.nn.functional.one_hot(x, K1).permute(0, 2, 1).float()
-        return out
+        return self._result(x, return_logits)
 
     @torch.no_grad()
     def sample(self, condition_token, condition_mask, condition_embed, content_token=None, filter_ratio=0.5,
@@ -619,7 +578,7 @@ class DiffusionTransformer(nn.Module):
             gids = self._caption_ids(caption_ids, B, device)
             x = torch.empty_like(x0)
             _lib.check(_lib.lib().ds_q_sample_rng(_lib.ptr(x0), _lib.ptr(t), _lib.ptr(gids),
-                                                  int(self.sample_seed if seed is None else seed), 0,
+                                                  self._seed(seed), 0,
                                                   _lib.ptr(self._schedule_table()), _lib.ptr(x), B, self.content_seq_len,
                                                   self.num_classes - 1, self.num_timesteps, _lib.stream()))
             return self._reverse(cond_emb, [(s_, s_) for s_ in steps], None, return_logits, start_tokens=x,
@@ -705,7 +664,7 @@ class DiffusionTransformer(nn.Module):
             remain = (ctypes.c_int * len(plan))(*[rk for _, rk in plan])
             _lib.check(lib.ds_denoiser_sample_purity_rng(
                 p["handle"], _lib.ptr(x), _lib.ptr(tmp), _lib.ptr(t_steps), remain, len(plan), _lib.ptr(kv), _lib.ptr(gids),
-                int(self.sample_seed if seed is None else seed), 0, B, weight, r, k, float(scale), _lib.ptr(tokens2),
+                self._seed(seed), 0, B, weight, r, k, float(scale), _lib.ptr(tokens2),
                 _lib.ptr(ws), _lib.ptr(scratch), _lib.stream()))
         else:
             for call, (t_k, r_k) in enumerate(plan):
@@ -716,10 +675,7 @@ class DiffusionTransformer(nn.Module):
                     p["handle"], _lib.ptr(x), _lib.ptr(t), _lib.ptr(kv), _lib.ptr(u), B, int(r_k), weight, r, k, float(scale),
                     _lib.ptr(tokens2), _lib.ptr(ws), _lib.ptr(scratch), _lib.ptr(tmp), _lib.stream()))
                 x, tmp = tmp, x
-        out = {"content_token": x}
-        if return_logits:
-            out["logits"] = torch.nn.functional.one_hot(x, K1).permute(0, 2, 1).float()
-        return out
+        return self._result(x, return_logits)
 
     @torch.no_grad()
     def sample_purity(self, condition_token, condition_mask, condition_embed, content_token=None, filter_ratio=0,
