@@ -283,6 +283,18 @@ int ds_loss_tail(const float* logits, const int64_t* x0, const int64_t* xt, cons
                  float* kl, float* nll, float* kl_aux, float* dbg_model_log_prob, int B, int L, int K, int T,
                  ds_stream_t stream);
 
+/* Likelihood scoring: one term of a clip's variational bound per row (definition: DESIGN.md section 4).  Row b is a
+ * (clip, timestep) pair -- x0 i64[B][L] the clip's tokens (each < K), xt i64[B][L] its diffused state, t i64[B] (each in
+ * [0, T): rows at different timesteps share a launch; a row outside that range gets NaN), logits [B * lrows][K] the
+ * network's output on (xt, t) with lrows >= L rows per sample (the denoiser's padded-row mode; rows >= L are never read).
+ * Per grid position, exactly what ds_loss_tail writes there, bit for bit -- nll where t[b] == 0, kl where t[b] > 0 -- and
+ * only that term is computed (no true posterior at t == 0, never the auxiliary KL).  term f64[B]: the row's positions
+ * widened to double and summed in a fixed order, no atomics, so a row's result depends neither on B nor on its row index.
+ * dbg_pos optional f32[B][L]: the per-position values.  Mask weights are (1, 1): this is the bound, not the training loss.
+ * Rejected (-1, nothing launched): null pointers (except dbg_pos), K other than 256 / 512, lrows < L, L > 288, B < 1. */
+int ds_score_tail(const float* logits, const int64_t* x0, const int64_t* xt, const int64_t* t, const float* sched,
+                  double* term, float* dbg_pos, int lrows, int B, int L, int K, int T, ds_stream_t stream);
+
 /* d(sum over samples of vb_loss) / d logits for the loss above (pt [B] = the sampling probabilities of t; mask
  * weights for masked / unmasked x_t positions; auxiliary loss weight and its adaptive flag): dlogits [B*L][K].  The
  * first kernel of the training step's backward (modeling/train.py composes the rest from the entries below, the GEMMs
@@ -566,6 +578,15 @@ int ds_denoiser_sample_purity_rng(const ds_denoiser* h, int64_t* tokens, int64_t
                                   const int* remain, int n_calls, const float* kv, const int64_t* gids,
                                   unsigned long long seed, int call0, int B, float weight, float trunc_r, int trunc_k,
                                   float scale, int64_t* tokens2, void* workspace, void* scratch, ds_stream_t stream);
+
+/* Likelihood scoring of B independent (clip, timestep) rows in one call (see ds_score_tail): x_t = ds_q_sample_rng(x0, t) on
+ * rng_stream 1 of (gids[b], seed, call) into xt_scratch i64[B][seq_len], the forward at batch B on the step driver's own
+ * activation layout (ds_denoiser_rows_per_sample), the score tail on the logits where the forward left them.  kv and
+ * workspace as for ds_denoiser_step_rng at batch B; term f64[B]; dbg_pos optional f32[B][seq_len].  t[b] in [0, n_steps) is
+ * the caller's to guarantee.  Argument checks come before anything is enqueued. */
+int ds_denoiser_score_rng(const ds_denoiser* h, const int64_t* x0, const int64_t* t, const float* kv, const int64_t* gids,
+                          unsigned long long seed, int call, int B, void* workspace, int64_t* xt_scratch, double* term,
+                          float* dbg_pos, ds_stream_t stream);
 
 /* per-launch HIP-event timing of the denoiser's GEMM launches (measurement only, bench.py) */
 int ds_profile_enable(int on);

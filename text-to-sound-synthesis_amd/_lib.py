@@ -159,6 +159,8 @@ _PROTOS = {
                                               _f, _vp, _vp, _vp, _vp, _vp]),
     "ds_denoiser_sample_purity_rng": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int), C.c_int, _vp, _vp, C.c_uint64, C.c_int,
                                                 C.c_int, _f, _f, C.c_int, _f, _vp, _vp, _vp, _vp]),
+    "ds_score_tail": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "ds_denoiser_score_rng": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "ds_profile_enable": (C.c_int, [C.c_int]),
     "ds_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i64)]),
     "ds_profile_collect_n": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i64), C.c_int]),

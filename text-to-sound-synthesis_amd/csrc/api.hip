@@ -727,3 +727,21 @@ extern "C" int ds_denoiser_sample_purity_rng(const ds_denoiser* h, int64_t* toke
     return run_chain(h, s, ChainCall{tokens, tokens_tmp, t_steps, n_calls, (tokens2 ? 2 : 1) * (size_t)B, 0, remain});
 }
 
+// ---- likelihood scoring (sampler.hip ds_score_tail_kernel): B independent (clip, timestep) rows -- x_t = ds_q_sample_rng(x0, t;
+// stream 1 of gids[b], call), the forward on the step driver's activation layout (padded rows where rows_per_sample says so),
+// the score tail on the logits where the forward left them.  Every rule is checked before anything is enqueued.
+extern "C" int ds_denoiser_score_rng(const ds_denoiser* h, const int64_t* x0, const int64_t* t, const float* kv,
+                                     const int64_t* gids, unsigned long long seed, int call, int B, void* workspace,
+                                     int64_t* xt_scratch, double* term, float* dbg_pos, ds_stream_t stream) {
+    DS_CHECK_ARG(h && x0 && t && kv && gids && workspace && xt_scratch && term, "null pointer");
+    DS_CHECK_ARG(B >= 1, "B must be at least 1");
+    const int Lp = rows_per_sample(h, B);
+    Carve w;
+    carve(h, B, workspace, &w, Lp);
+    const ScoreCall c{__func__, stream, w.logits, x0, xt_scratch, t, h->d.sched, term, dbg_pos, Lp, B, h->d.seq_len,
+                      h->d.n_codes, h->d.n_steps};
+    TRY(ds_score_tail_check(c));
+    TRY(ds_q_sample_rng(x0, t, gids, seed, call, h->d.sched, xt_scratch, B, c.L, c.K, c.T, stream));
+    TRY(forward_impl(h, xt_scratch, t, kv, B, w, w.logits, 0, (hipStream_t)stream, Lp));
+    return ds_score_tail_launch(c);
+}

@@ -42,3 +42,21 @@ struct TailCall {
 
 int ds_sample_tail_check(const TailCall& c);    // every argument rule, once: -1 and a message naming c.who, no HIP call
 int ds_sample_tail_launch(const TailCall& c);   // a checked call: fills the kernel arguments, selects the kernel
+
+// One score-tail launch (sampler.hip ds_score_tail_kernel): ds_score_tail and the denoiser's score driver (api.hip) share the
+// checker and the launcher, like the sampling tails above.
+struct ScoreCall {
+    const char* who;
+    ds_stream_t stream;
+    const float* logits;                     // [B * lrows][K]
+    const int64_t* x0;                       // [B][L]
+    const int64_t* xt;                       // [B][L]
+    const int64_t* t;                        // [B], each row its own timestep
+    const float* sched;
+    double* term;                            // [B]
+    float* dbg_pos;                          // optional [B][L]
+    int lrows, B, L, K, T;
+};
+
+int ds_score_tail_check(const ScoreCall& c);    // -1 and a message naming c.who, no HIP call
+int ds_score_tail_launch(const ScoreCall& c);

@@ -1098,3 +1098,121 @@ extern "C" int ds_sample_tail_purity_rng(const float* logits, const float* logit
     return tail_run(c);
 }
 
+// ---- likelihood scoring: one term of a clip's variational bound per row -------------------------------
+// Row b is a (clip, timestep) pair: x0[b] the clip's tokens, xt[b] its forward-diffused state at t[b], logits the denoiser's
+// output on (xt[b], t[b]) in the [B * lrows][K] layout of the step driver (lrows >= L: rows >= L of a sample are never read).
+// Per grid position -- one wavefront, the thread mapping and the expressions of ds_loss_tail_kernel, so the value is that
+// kernel's bit for bit -- only the term t[b] selects is computed:
+//   t == 0: nll = -log p_theta(x_0 | x_1)                                    (no true posterior is formed)
+//   t >  0: kl  = KL(q(x_{t-1} | x_t, x_0) || p_theta(x_{t-1} | x_t))
+// and never the auxiliary KL.  One workgroup per row: its 16 waves walk the positions (wave w takes w, w + 16, ...), leave the
+// f32 values in LDS, and wave 0 widens them to double and adds them in a fixed order -- lane l sums positions l, l + 64, ...
+// ascending, then the xor butterfly -- so term[b] depends on nothing but row b's own inputs: not on B, not on b, and no
+// floating-point atomics.  A timestep outside [0, T) reads no table: the row's term (and map) is NaN.
+// The two accumulations are spelled fmaf: ds_loss_tail_kernel's `acc += e * d` chains are contracted to fma by the compiler,
+// while here, with fewer accumulators alive, it pairs the products into packed multiplies followed by separate adds -- one
+// rounding more per product, values a last place apart (tests/test_hip_score.py holds the two kernels together).
+#define DS_SCORE_WAVES 16
+template <int NPL>
+__global__ __launch_bounds__(64 * DS_SCORE_WAVES) void ds_score_tail_kernel(
+    const float* __restrict__ logits, const int64_t* __restrict__ x0, const int64_t* __restrict__ xt,
+    const int64_t* __restrict__ t, const float* __restrict__ sched, double* __restrict__ term, float* __restrict__ dbg_pos,
+    int lrows, int L, int T) {
+    constexpr int K = NPL * 64;
+    __shared__ float s_pos[DS_PURITY_MAX_L];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int b = blockIdx.x;
+    const int tt = (int)t[b];
+    const bool t_ok = tt >= 0 && tt < T;
+    for (int pos = w; pos < L; pos += DS_SCORE_WAVES) {
+        const size_t col = (size_t)b * L + pos;
+        float val = __builtin_nanf("");
+        if (t_ok) {
+            float v[NPL];
+            const float* lg = logits + ((size_t)b * lrows + pos) * K;
+#pragma unroll
+            for (int j = 0; j < NPL; ++j) v[j] = lg[j * 64 + lane];
+            float mx = v[0];
+#pragma unroll
+            for (int j = 1; j < NPL; ++j) mx = fmaxf(mx, v[j]);
+            mx = wmaxf(mx);
+            double se = 0.0;
+#pragma unroll
+            for (int j = 0; j < NPL; ++j) se += exp((double)v[j] - (double)mx);
+            const double lse64 = log(wsumd(se));
+            float lp[NPL], ls[NPL];
+            const int x0c = (int)x0[col], xtc = (int)xt[col];
+#pragma unroll
+            for (int j = 0; j < NPL; ++j) {
+                lp[j] = fminf(fmaxf((float)(((double)v[j] - (double)mx) - lse64), -70.f), 0.f);   // log p_theta(x_0 | x_t)
+                ls[j] = (j * 64 + lane) == x0c ? 0.f : LOG_ZERO_F;                                 // log one-hot of x_0
+            }
+            const float ls_m = x0c == K ? 0.f : LOG_ZERO_F;
+            float pm[NPL], pm_m;
+            ds_posterior<NPL>(lp, -70.f, xtc, K, lane, sched, T + 1, tt, pm, pm_m);    // model posterior
+            if (tt == 0) {
+                float n = 0.f;
+#pragma unroll
+                for (int j = 0; j < NPL; ++j) n = fmaf(expf(ls[j]), pm[j], n);
+                n = fmaf(expf(ls_m), pm_m, wsumf(n));
+                val = -n;
+            } else {
+                float pr[NPL], pr_m;
+                ds_posterior<NPL>(ls, ls_m, xtc, K, lane, sched, T + 1, tt, pr, pr_m);     // true posterior
+                float a = 0.f;
+#pragma unroll
+                for (int j = 0; j < NPL; ++j) a = fmaf(expf(pr[j]), pr[j] - pm[j], a);
+                a = fmaf(expf(pr_m), pr_m - pm_m, wsumf(a));
+                val = a;
+            }
+        }
+        if (lane == 0) {
+            s_pos[pos] = val;
+            if (dbg_pos) dbg_pos[col] = val;
+        }
+    }
+    __syncthreads();
+    if (w == 0) {
+        double acc = 0.0;
+        for (int pos = lane; pos < L; pos += 64) acc += (double)s_pos[pos];
+        acc = wsumd(acc);
+        if (lane == 0) term[b] = acc;
+    }
+}
+
+int ds_score_tail_check(const ScoreCall& c) {
+    const char* msg = !(c.logits && c.x0 && c.xt && c.t && c.sched && c.term) ? "null pointer"
+                      : !(c.K == 256 || c.K == 512)                          ? "codebook size must be 256 or 512"
+                      : !(c.L > 0 && c.L <= DS_PURITY_MAX_L)                  ? "L must be in 1 .. 288"
+                      : !(c.lrows >= c.L)                                     ? "logits rows per sample"
+                      : !(c.B >= 1)                                           ? "B must be at least 1"
+                      : !(c.T > 0)                                            ? "T must be positive"
+                                                                              : nullptr;
+    if (!msg) return 0;
+    ds_set_error("%s: %s", c.who, msg);
+    return -1;
+}
+
+int ds_score_tail_launch(const ScoreCall& c) {
+    hipStream_t stream = (hipStream_t)c.stream;
+    const dim3 grid((unsigned)c.B), block(64 * DS_SCORE_WAVES);
+    if (c.K == 256)
+        hipLaunchKernelGGL((ds_score_tail_kernel<4>), grid, block, 0, stream, c.logits, c.x0, c.xt, c.t, c.sched, c.term,
+                           c.dbg_pos, c.lrows, c.L, c.T);
+    else
+        hipLaunchKernelGGL((ds_score_tail_kernel<8>), grid, block, 0, stream, c.logits, c.x0, c.xt, c.t, c.sched, c.term,
+                           c.dbg_pos, c.lrows, c.L, c.T);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        ds_set_error("%s: launch failed: %s", c.who, hipGetErrorString(e));
+        return -2;
+    }
+    return 0;
+}
+
+extern "C" int ds_score_tail(const float* logits, const int64_t* x0, const int64_t* xt, const int64_t* t, const float* sched,
+                             double* term, float* dbg_pos, int lrows, int B, int L, int K, int T, ds_stream_t stream) {
+    const ScoreCall c{__func__, stream, logits, x0, xt, t, sched, term, dbg_pos, lrows, B, L, K, T};
+    const int rc = ds_score_tail_check(c);
+    return rc ? rc : ds_score_tail_launch(c);
+}

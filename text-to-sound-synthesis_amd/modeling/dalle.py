@@ -328,6 +328,57 @@ class DALLE(nn.Module):
         self.train()
         return {"content": content, "content_token": tokens}
 
+    # ---- likelihood scoring (not in the reference; DiffusionTransformer.score_tokens) ---------------------
+    def _score_keywords(self, batch, condition):
+        kw = dict(condition_token=condition.get("condition_token"), condition_embed=condition.get("condition_embed_token"))
+        if batch.get("caption_ids") is not None:
+            kw["caption_ids"] = batch["caption_ids"]
+        if batch.get("seed") is not None:
+            kw["seed"] = int(batch["seed"])
+        return kw
+
+    def _content_tokens(self, batch):
+        """batch['content_token'], or the batch's content ('image', or 'audio' with 'audio_rate') through prepare_content"""
+        tokens = batch.get("content_token")
+        if tokens is None:
+            tokens = self.prepare_content(batch)["content_token"]
+        return torch.as_tensor(tokens).to(self.device).long()
+
+    @torch.no_grad()
+    def score_content(self, batch, timesteps=None, draws=1):
+        """How well the batch's clips fit its captions: the variational bound of each clip's tokens under its caption.  batch:
+        the caption as in prepare_condition and the content as 'content_token' i64[B, 265], 'image' or 'audio' (+ 'audio_rate');
+        'caption_ids' / 'seed' select the noise of the forward diffusion as in generate_content (default ids 0 .. B-1).
+        timesteps / draws: DiffusionTransformer.score_tokens.  Returns {'nats' f64[B] (lower = better fit), 'bits_per_token'
+        f64[B] = nats / (265 ln 2), 'terms' f64[B, n_t]}."""
+        import math
+        condition = self.prepare_condition(batch=batch)
+        tokens = self._content_tokens(batch)
+        nats, terms = self.transformer.score_tokens(tokens, timesteps=timesteps, draws=draws, return_terms=True,
+                                                    **self._score_keywords(batch, condition))
+        return {"nats": nats, "bits_per_token": nats / (tokens.shape[1] * math.log(2.0)), "terms": terms}
+
+    @torch.no_grad()
+    def rank_captions(self, batch, captions, timesteps=None, draws=1):
+        """Generative zero-shot tagging: every clip of the batch (content as in score_content; the batch needs no caption)
+        scored under each of the C `captions` (a list of strings, token ids i64[C, 77] or embeddings f32[C, 77, 512]) ->
+        f64[N, C] nats, lower = better fit.  Every caption of a clip is scored on the clip's own id (batch['caption_ids'],
+        default 0 .. N-1) and seed: the same forward-diffused states, so a row's entries differ by the captions alone."""
+        tokens = self._content_tokens(batch)
+        N = tokens.shape[0]
+        if isinstance(captions, (list, tuple, str)):
+            condition = self.prepare_condition({self.condition_info["key"]: [captions] if isinstance(captions, str) else list(captions)})
+        else:
+            condition = self.prepare_condition(batch={}, condition=captions if captions.dtype != torch.long else {"condition_token": captions})
+        cond_emb = self.transformer._cond(condition.get("condition_token"), condition.get("condition_embed_token"))
+        C = cond_emb.shape[0]
+        ids = batch.get("caption_ids")
+        ids = torch.arange(N) if ids is None else torch.as_tensor(ids, dtype=torch.long).reshape(-1)
+        kw = {} if batch.get("seed") is None else {"seed": int(batch["seed"])}
+        nats = self.transformer.score_tokens(tokens.repeat_interleave(C, 0), condition_embed=cond_emb.repeat(N, 1, 1),
+                                             timesteps=timesteps, draws=draws, caption_ids=ids.repeat_interleave(C), **kw)
+        return nats.view(N, C)
+
     @torch.no_grad()
     def sample(self, batch, clip=None, temperature=1., return_rec=True, filter_ratio=[0, 0.5, 1.0], content_ratio=[1],
                return_att_weight=False, return_logits=False, sample_type="normal", **kwargs):

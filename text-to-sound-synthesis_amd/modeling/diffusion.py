@@ -59,6 +59,24 @@ def purity_plan(S, L, log_cumprod_ct):
     return plan
 
 
+def score_plan(T, n=None):
+    """The timesteps and weights of a likelihood score -> (timesteps, weights), two lists.
+    n None or T: every timestep 0 .. T-1 with weight 1 -- the full variational bound, T forwards per clip.
+    2 <= n < T: t = 0 with weight 1 (the decoder term is not interpolated) and n - 1 distinct timesteps, the midpoints of n - 1
+    equal strata of 1 .. T-1 (t_k = 1 + floor((2k + 1)(T - 1) / (2(n - 1)))), each with weight (T - 1) / (n - 1): the weights
+    sum to T.  Anything else raises ValueError.  Pure host arithmetic."""
+    T = int(T)
+    if T < 1:
+        raise ValueError("a diffusion has at least one timestep, got T = %r" % (T,))
+    if n is None or (not isinstance(n, bool) and isinstance(n, (int, np.integer)) and int(n) == T):
+        return list(range(T)), [1.0] * T
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 2 <= int(n) < T:
+        raise ValueError("timesteps must be None, T = %d, or an integer in 2 .. %d, got %r" % (T, T - 1, n))
+    n = int(n)
+    ts = [0] + [1 + ((2 * k + 1) * (T - 1)) // (2 * (n - 1)) for k in range(n - 1)]
+    return ts, [1.0] + [(T - 1) / (n - 1)] * (n - 1)
+
+
 def _log_1_min_a(a):
     return torch.log(1 - a.exp() + 1e-40)
 
@@ -704,3 +722,80 @@ class DiffusionTransformer(nn.Module):
         plan = purity_plan(S, self.content_seq_len, self.log_cumprod_ct)
         return self._guarded(self._purity_once, cond_emb, plan, weight, noise_fn, return_logits, start_tokens=x,
                              caption_ids=caption_ids, seed=seed, guide=guide)
+
+    # ---- likelihood scoring (csrc/sampler.hip ds_score_tail_kernel) ---------------------------------------
+    def _score_once(self, x0, cond_emb, ts, draws, gids, seed, rows_per_launch, want_map):
+        """The rows of a score: per draw r, row k N + n is clip n at timestep ts[k] (timestep-major, so consecutive launches of
+        a batch of clips see the same clips and share one caption K/V), cut into launches of at most rows_per_launch rows; a
+        launch never spans two draws (the draw index is the launch's Philox call).  -> (terms f64[draws, n_t, N], per-position
+        values f32[draws, n_t, N, L] or None)."""
+        device = self.device
+        N, L = x0.shape
+        n_t, rows = len(ts), len(ts) * N
+        sched = self._schedule_table()
+        tr = self.transformer
+        p = tr.packed(sched)
+        lib = _lib.lib()
+        t_rows = torch.tensor(ts, dtype=torch.long, device=device).repeat_interleave(N).contiguous()
+        terms = torch.full((draws, rows), float("nan"), dtype=torch.float64, device=device)
+        pos = torch.full((draws, rows, L), float("nan"), dtype=torch.float32, device=device) if want_map else None
+        kv_of = {}                                        # (first clip, rows) of a launch -> its replicated inputs
+        for r in range(draws):
+            for a in range(0, rows, rows_per_launch):
+                B = min(rows, a + rows_per_launch) - a
+                key = (a % N, B)
+                if key not in kv_of:
+                    clip = (torch.arange(a, a + B, device=device) % N)
+                    kv_of.clear()                         # one launch shape alive at a time: the K/V of 64 rows is large
+                    kv_of[key] = (x0[clip].contiguous(), gids[clip].contiguous(),
+                                  tr.condition_kv(cond_emb[clip].contiguous(), sched))
+                x_rows, g_rows, kv = kv_of[key]
+                xt = torch.empty_like(x_rows)
+                t_l, term_l = t_rows[a:a + B], terms[r, a:a + B]
+                pos_l = None if pos is None else pos[r, a:a + B]
+                _lib.check(lib.ds_denoiser_score_rng(p["handle"], _lib.ptr(x_rows), _lib.ptr(t_l), _lib.ptr(kv), _lib.ptr(g_rows),
+                                                     self._seed(seed), r, B, _lib.ptr(tr.workspace(B, sched)), _lib.ptr(xt),
+                                                     _lib.ptr(term_l), _lib.ptr(pos_l), _lib.stream()))
+        return terms.view(draws, n_t, N), None if pos is None else pos.view(draws, n_t, N, L)
+
+    @torch.no_grad()
+    def score_tokens(self, content_token, condition_token=None, condition_embed=None, timesteps=None, draws=1,
+                     caption_ids=None, seed=None, rows_per_launch=64, return_terms=False, return_map=False):
+        """How well clips fit their captions: the variational bound of content_token i64[N, L] (every value < K) under the
+        captions (condition_token i64[N, 77] or condition_embed f32[N, 77, 512]), in nats, f64[N] -- lower is a better fit.
+            score = (1 / draws) sum_r sum_k w_k term(x0, c, t_k, r),   (t_k, w_k) = score_plan(T, timesteps)
+        term: the decoder NLL at t = 0, the KL between the true and the modelled posterior at t > 0, summed over the grid, on
+        x_t = q_sample(x0, t_k) drawn from stream 1 of (caption_ids[n], seed) at Philox call r -- the same uniforms at every
+        t and in every batch, so a score does not depend on how its rows are cut into launches, and one clip scored under
+        several captions with one id sees common random numbers.  The prior term KL(q(x_T | x0) || p(x_T)) is left out, as the
+        reference's loss leaves it out; mask weights are (1, 1) and there is no auxiliary term: this is the bound, not the
+        training loss.  timesteps None (or T): the full bound, T forwards per clip; an integer n in 2 .. T-1: t = 0 and n - 1
+        evenly spread timesteps, re-weighted.  The (clip, timestep) rows run draws x ceil(N n_t / rows_per_launch) launches of
+        ds_denoiser_score_rng (64 rows: the batch the per-sample GEMM program is tuned for), under the range guard of the
+        sampling chains.  return_terms: also terms f64[N, n_t] (unweighted, mean over draws); return_map: also f32[N, L], the
+        weighted per-position sum (mean over draws) -- returned as a tuple in that order."""
+        L, K, T = self.content_seq_len, self.num_classes - 1, self.num_timesteps
+        device = self.device
+        x0 = torch.as_tensor(content_token).to(device).long().contiguous()
+        if x0.dim() != 2 or x0.shape[1] != L or x0.shape[0] < 1:
+            raise ValueError("content_token must be i64[N, %d] with N >= 1, got %s" % (L, tuple(x0.shape)))
+        if int(x0.max()) >= K or int(x0.min()) < 0:
+            raise ValueError("content_token holds values outside 0 .. %d ([MASK] = %d is not a valid x0)" % (K - 1, K))
+        draws, rows_per_launch = int(draws), int(rows_per_launch)
+        if draws < 1 or rows_per_launch < 1:
+            raise ValueError("draws and rows_per_launch must be at least 1, got %d and %d" % (draws, rows_per_launch))
+        ts, weights = score_plan(T, timesteps)
+        N = x0.shape[0]
+        cond_emb = self._cond(condition_token, condition_embed).to(device)
+        if cond_emb.shape[0] != N:
+            raise ValueError("%d conditions for %d clips" % (cond_emb.shape[0], N))
+        gids = self._caption_ids(caption_ids, N, device)
+        terms, pos = self._guarded(self._score_once, x0, cond_emb, ts, draws, gids, seed, rows_per_launch, return_map)
+        w = torch.tensor(weights, dtype=torch.float64, device=device)
+        terms = terms.mean(0)                                        # [n_t, N]
+        out = [(terms * w[:, None]).sum(0)]
+        if return_terms:
+            out.append(terms.t().contiguous())
+        if return_map:
+            out.append((pos.double() * w[None, :, None, None]).sum(1).mean(0).float())
+        return out[0] if len(out) == 1 else tuple(out)

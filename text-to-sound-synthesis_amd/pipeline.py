@@ -418,6 +418,63 @@ class Diffsound:
                                 start_token=start, purity_steps=purity_steps, purity_weight=purity_weight)
         return self._render_long(out, windows, n, samples, save_root, sample_rate)
 
+    # ---- likelihood scoring (DiffusionTransformer.score_tokens) -------------------------------------------
+    @torch.no_grad()
+    def score_audio(self, audio, text, audio_rate=None, timesteps=None, draws=1, caption_ids=None, seed=None):
+        """How well recordings fit captions: audio / audio_rate as in generate_sample_from_audio (encoded to their 5 x 53
+        tokens), text = one caption per recording (strings, token ids or embeddings).  Returns DALLE.score_content's
+        {'nats' f64[B] -- the variational bound, lower = better fit --, 'bits_per_token', 'terms'}; timesteps / draws /
+        caption_ids / seed as in DiffusionTransformer.score_tokens."""
+        batch = dict(self._caption_batch(text), audio=audio, audio_rate=audio_rate)
+        if caption_ids is not None:
+            batch["caption_ids"] = caption_ids
+        if seed is not None:
+            batch["seed"] = seed
+        return self.model.score_content(batch, timesteps=timesteps, draws=draws)
+
+    @torch.no_grad()
+    def generate_best_of(self, cond, n, score_timesteps=None, truncation_rate=0.85, fast=False, caption_ids=None, seed=None,
+                         sample_rate=None, guidance_scale=None, negative_text=None, purity_steps=None, purity_weight=0.0,
+                         score_draws=1):
+        """Best-of-n generation: n candidates per caption, the one that fits its caption best is rendered.  cond and the
+        keywords as in generate_sample_with_condition, whose `replicate` is n here; the candidates are its tokens at
+        replicate = n with per-caption in-kernel noise (caption_ids default 0 .. B-1; replicate r of caption i draws as id
+        ids[i] + r 2^24).  Candidate r of caption i is scored by DiffusionTransformer.score_tokens under the caption, on the
+        caption's own id ids[i] and `seed` -- all n candidates of a caption see the same forward-diffusion uniforms --
+        with score_timesteps / score_draws as its timesteps / draws (None: the full bound, T forwards per candidate).  The
+        lowest score wins, ties go to the lowest replicate; only the winners are decoded and vocoded.
+        Returns (mel01 f32[B,80,848], wave or None, tokens i64[B,265], scores f64[B, n] in nats)."""
+        n = int(n)
+        if n < 1:
+            raise ValueError("generate_best_of needs at least one candidate per caption, got n = %r" % (n,))
+        model = self.model
+        batch = dict(self._caption_batch(cond))
+        condition = model.prepare_condition(batch=batch)
+        B = next(v.shape[0] for v in condition.values() if torch.is_tensor(v))
+        ids = torch.arange(B) if caption_ids is None else torch.as_tensor(caption_ids, dtype=torch.long).reshape(-1)
+        batch["caption_ids"] = ids
+        if seed is not None:
+            batch["seed"] = seed
+        if negative_text is not None:
+            batch["negative_text"] = negative_text
+        sample_type = purity_sample_type("top" + str(truncation_rate) + ("r,fast" + str(fast - 1) if fast else "r"),
+                                         purity_steps, purity_weight)
+        model.eval()
+        replicated = {k: (torch.cat([v for _ in range(n)], dim=0) if torch.is_tensor(v) else v) for k, v in condition.items()}
+        tokens = model._run_chain(batch, replicated, model._free_keywords(0, 1.0, False, sample_type), n, sample_type,
+                                  guidance_scale)                                   # [n B, 265], replicate-major
+        model.train()
+        kw = {} if seed is None else {"seed": int(seed)}
+        scores = model.transformer.score_tokens(tokens, condition_token=replicated.get("condition_token"),
+                                                condition_embed=replicated.get("condition_embed_token"),
+                                                timesteps=score_timesteps, draws=score_draws, caption_ids=ids.repeat(n), **kw)
+        scores = scores.view(n, B).t().contiguous()                                # [B, n]
+        import numpy as np
+        best = torch.from_numpy(np.argmin(scores.cpu().numpy(), axis=1)).to(tokens.device)   # first minimum: the lowest replicate
+        winners = tokens.view(n, B, -1)[best, torch.arange(B, device=tokens.device)].contiguous()
+        mel01, wave, winners = self._render(winners, (B, 256, 5, 53), None, sample_rate)
+        return mel01, wave, winners, scores
+
     @torch.no_grad()
     def inference_generate_sample_with_condition(self, text, truncation_rate, save_root, batch_size, fast=False,
                                                  guidance_scale=None, negative_text=None, purity_steps=None, purity_weight=0.0):
