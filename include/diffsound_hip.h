@@ -246,6 +246,32 @@ int ds_sample_tail_guided_rng(const float* logits_c, const float* logits_u, cons
                               int64_t* out_tokens, int B, int L, int K, int T, int initial, float trunc_r, int trunc_k,
                               float scale, const unsigned char* keep, const int64_t* known, int mode, ds_stream_t stream);
 
+/* Caption tracks in the tail: several captions per clip, each weighted per grid position (the conjunction of Liu et al.,
+ * "Compositional Visual Generation with Composable Diffusion Models", 2022, with weights that vary over the token grid;
+ * guidance is its one-track, constant-weight case).  C = n_tracks, 1 <= C <= DS_MAX_TRACKS.
+ *   logits   f32[C + 1][B*L][K]: the denoiser's logits under track 0 .. C-1's captions, the null condition's LAST; all on
+ *            the same x_t and t
+ *   weights  f32[B][C][L]
+ * With lu / l_i = predict_start of the null row and of track i's row (as in ds_sample_tail_guided), in float64:
+ *     g = lu;   for i = 0 .. C-1 in this order:  g = g + weights[b][i][pos] (l_i - lu);   g <- g - logsumexp(g)  (max-shifted),
+ * rounded to f32 and clamped to [-70, 0] ([MASK] row -70) is the log_pred that truncation, posterior and Gumbel-argmax
+ * consume unchanged; dbg_log_pred dumps it.  One track of constant weight s gives ds_sample_tail_guided's results at scale
+ * s bit for bit.  A track whose weight at a position is exactly 0 is not read at that position (its logits may hold
+ * anything there); all weights 0: the null prediction.  Negative weights push away from a caption.  The noise is the plain
+ * tail's: one stream per clip (gids[b], call).  keep / known / mode as in ds_sample_tail_guided; keep == NULL: unheld.
+ * Rejected (-1, nothing launched): null weights, n_tracks outside 1 .. DS_MAX_TRACKS, and what ds_sample_tail_guided
+ * rejects.  The VALUES of weights are on the device and are not checked (that would take a synchronisation): the caller
+ * passes finite weights -- the Python layer checks them -- and a non-finite weight gives a non-finite prediction. */
+#define DS_MAX_TRACKS 4
+int ds_sample_tail_composed(const float* logits, const int64_t* xt, const int64_t* t, const float* u, const float* sched,
+                            int64_t* out_tokens, float* dbg_log_pred, float* dbg_trunc, float* dbg_post, int B, int L,
+                            int K, int T, int initial, float trunc_r, int trunc_k, int n_tracks, const float* weights,
+                            const unsigned char* keep, const int64_t* known, int mode, ds_stream_t stream);
+int ds_sample_tail_composed_rng(const float* logits, const int64_t* xt, const int64_t* t, const int64_t* gids,
+                                unsigned long long seed, int call, const float* sched, int64_t* out_tokens, int B, int L,
+                                int K, int T, int initial, float trunc_r, int trunc_k, int n_tracks, const float* weights,
+                                const unsigned char* keep, const int64_t* known, int mode, ds_stream_t stream);
+
 /* Purity-prior sampling in the tail (the high-quality inference strategy of Tang et al., "Improved Vector Quantized
  * Diffusion Models", 2022; specification: DESIGN.md section 4).  One step reveals an exact number of [MASK] positions per
  * sample, the most confident first, and never re-samples a revealed token; it uses no posterior and no schedule table.
@@ -556,6 +582,35 @@ int ds_denoiser_sample_guided_rng(const ds_denoiser* h, int64_t* tokens, int64_t
                                   int n_calls, const float* kv, const int64_t* gids, unsigned long long seed, int call0,
                                   int B, int initial, float trunc_r, int trunc_k, float scale, const unsigned char* keep,
                                   const int64_t* known, int mode, int64_t* tokens2, void* workspace, ds_stream_t stream);
+
+/* Composed forms (caption tracks, see ds_sample_tail_composed) of the three guided entries: one forward at batch (C+1)B,
+ * C = n_tracks, and the composed tail on the C + 1 slabs of its logits.
+ *   kv         ds_denoiser_cond_kv at batch (C+1)B, track-major: track 0's B embeddings, ..., track C-1's, then the B null
+ *              embeddings
+ *   workspace  ds_denoiser_workspace_bytes(h, (C+1)B)
+ *   tokensN    i64[(C+1)B][seq_len] scratch of the caller: receives the tokens of every step copied C + 1 times (on the
+ *              call's stream)
+ *   t, t_post  (C+1)B entries, the caller's B repeated (the posterior reads the first B); for the chain t_steps is
+ *              i64[n_calls][2][(C+1)B]
+ *   weights    f32[B][C][seq_len], finite (see ds_sample_tail_composed)
+ * tokens_in / tokens_out / tokens / tokens_tmp / keep / known stay [B][seq_len]; keep == NULL: unheld.  The rows per sample
+ * are those of the forward's batch, ds_denoiser_rows_per_sample(h, (C+1)B): the padded-row mode may switch on at a smaller
+ * B than unguided.  Argument checks (n_tracks, null weights, the mode / keep / known rules) come before anything is
+ * enqueued. */
+int ds_denoiser_step_composed(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const int64_t* t_post,
+                              const float* kv, const float* u, int B, int initial, float trunc_r, int trunc_k,
+                              int n_tracks, const float* weights, const unsigned char* keep, const int64_t* known, int mode,
+                              int64_t* tokensN, void* workspace, int64_t* tokens_out, ds_stream_t stream);
+int ds_denoiser_step_composed_rng(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t, const int64_t* t_post,
+                                  const float* kv, const int64_t* gids, unsigned long long seed, int call, int B,
+                                  int initial, float trunc_r, int trunc_k, int n_tracks, const float* weights,
+                                  const unsigned char* keep, const int64_t* known, int mode, int64_t* tokensN,
+                                  void* workspace, int64_t* tokens_out, ds_stream_t stream);
+int ds_denoiser_sample_composed_rng(const ds_denoiser* h, int64_t* tokens, int64_t* tokens_tmp, const int64_t* t_steps,
+                                    int n_calls, const float* kv, const int64_t* gids, unsigned long long seed, int call0,
+                                    int B, int initial, float trunc_r, int trunc_k, int n_tracks, const float* weights,
+                                    const unsigned char* keep, const int64_t* known, int mode, int64_t* tokensN,
+                                    void* workspace, ds_stream_t stream);
 
 /* Purity-prior steps and chains (see ds_sample_tail_purity): forward + purity tail.  t drives the network only (AdaLN);
  * remain = the [MASK] positions a sample may still have after the step; weight = the sharpening weight r.  Region-held

@@ -191,7 +191,23 @@ _PROTOS = {
                                  C.c_int, _f, _f, _f, _f, _f, _vp, _vp]),
     "ds_resample": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp]),
 }
-EXPORTED = tuple(_PROTOS)
+# The caption-track entries (csrc/sampler.hip SampleCompose), a table of their own: tests/test_driver_host.py walks the
+# sampling entries of _PROTOS against its closed list of their rejections; these entries' rejections are walked by
+# tests/test_compose_host.py.
+_PROTOS_COMPOSED = {
+    "ds_sample_tail_composed": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f, C.c_int, C.c_int, _vp, _vp, _vp,
+                                          C.c_int, _vp]),
+    "ds_sample_tail_composed_rng": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, C.c_int, _f, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
+    "ds_denoiser_step_composed": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _f, C.c_int, C.c_int, _vp, _vp,
+                                            _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "ds_denoiser_step_composed_rng": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, C.c_int, C.c_int, C.c_int, _f,
+                                                C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "ds_denoiser_sample_composed_rng": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_uint64, C.c_int, C.c_int, C.c_int,
+                                                  _f, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+}
+EXPORTED = tuple(_PROTOS) + tuple(_PROTOS_COMPOSED)
 
 _lib = None
 
@@ -205,7 +221,7 @@ def lib():
                 "libdiffsound_hip.so is missing (%s). Build it with `python __graft_entry__.py` -- "
                 "there is no CPU or PyTorch fallback for the Diffsound HIP path." % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in _PROTOS.items():
+        for name, (res, args) in list(_PROTOS.items()) + list(_PROTOS_COMPOSED.items()):
             fn = getattr(L, name)   # AttributeError here == header/library mismatch
             fn.restype = res
             fn.argtypes = args

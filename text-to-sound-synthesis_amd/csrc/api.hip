@@ -427,7 +427,7 @@ extern "C" int ds_denoiser_forward(const ds_denoiser* h, const int64_t* tokens, 
 // ---- sampling steps and chains: forward + sampling tail (sampler.h TailCall) -------------------------------------------------
 // One step, as every ds_denoiser_step* / ds_denoiser_sample* entry describes it.  The entry fills the tail's who, stream, B,
 // noise source, truncation, `initial` and its hold / guidance / purity fields; aim_tail adds what the handle and the workspace
-// give.  kv and workspace are at the forward's batch: B, or 2B with tokens2.
+// give.  kv and workspace are at the forward's batch: B, or n_cond B with tokens2.
 struct StepCall {
     TailCall tail;
     const int64_t* tokens_in = nullptr;
@@ -442,6 +442,9 @@ struct StepCall {
     // the null condition (kv: ds_denoiser_cond_kv of the caption embeddings followed by the null embeddings; t, t_post: the
     // caller's B entries repeated, the posterior reads the first B), and the tail mixes the two halves of the logits
     int64_t* tokens2 = nullptr;
+    // conditions per clip with tokens2: 2 guided; n_tracks + 1 composed (sampler.hip SampleCompose: tokens2 is
+    // i64[n_cond B][seq_len], kv is track-major with the null condition last, and the tail reads n_cond slabs of the logits)
+    int n_cond = 2;
     bool zero_kv_pad = true;           // forward_impl: false in the later steps of a chain
 };
 
@@ -454,11 +457,13 @@ static int step_error(const StepCall& s, int rc, const char* what, const char* d
 // only.  The purity tail reads no timestep and no schedule table: t, sched and T stay zero.  Returns the rows per sample.
 static int aim_tail(const ds_denoiser* h, StepCall& s, Carve* w) {
     TailCall& c = s.tail;
-    const int Bf = s.tokens2 ? 2 * c.B : c.B, Lp = rows_per_sample(h, Bf);
+    const int Bf = s.tokens2 ? s.n_cond * c.B : c.B, Lp = rows_per_sample(h, Bf);
     carve(h, Bf, s.workspace, w, Lp);
     c.L = h->d.seq_len; c.K = h->d.n_codes;
     c.logits = w->logits; c.logits_rows = Lp;
-    c.logits_u = s.tokens2 ? w->logits + (size_t)c.B * Lp * c.K : nullptr;
+    const bool composed = c.weights != nullptr;
+    c.logits_u = s.tokens2 && !composed ? w->logits + (size_t)c.B * Lp * c.K : nullptr;
+    c.track_stride = composed ? (size_t)c.B * Lp * c.K : 0;
     c.xt = s.tokens_in; c.out_tokens = s.tokens_out;
     if (c.kind == DS_TAIL_POSTERIOR) {
         c.t = s.t_post ? s.t_post : s.t; c.sched = h->d.sched; c.T = h->d.n_steps;
@@ -478,14 +483,14 @@ static int step_check(const ds_denoiser* h, StepCall s) {
 static int run_step(const ds_denoiser* h, StepCall& s) {
     hipStream_t stream = (hipStream_t)s.tail.stream;
     const size_t n_tok = (size_t)s.tail.B * h->d.seq_len;
-    for (int half = 0; s.tokens2 && half < 2; ++half) {
+    for (int half = 0; s.tokens2 && half < s.n_cond; ++half) {
         hipError_t e = hipMemcpyAsync(s.tokens2 + half * n_tok, s.tokens_in, n_tok * sizeof(int64_t), hipMemcpyDeviceToDevice,
                                       stream);
         if (e != hipSuccess) return step_error(s, -2, "hipMemcpyAsync: ", hipGetErrorString(e));
     }
     Carve w;
     const int Lp = aim_tail(h, s, &w);
-    TRY(forward_impl(h, s.tokens2 ? s.tokens2 : s.tokens_in, s.t, s.kv, s.tokens2 ? 2 * s.tail.B : s.tail.B, w, w.logits, 0,
+    TRY(forward_impl(h, s.tokens2 ? s.tokens2 : s.tokens_in, s.t, s.kv, s.tokens2 ? s.n_cond * s.tail.B : s.tail.B, w, w.logits, 0,
                      stream, Lp, s.zero_kv_pad));
     return ds_sample_tail_launch(s.tail);
 }
@@ -682,6 +687,61 @@ extern "C" int ds_denoiser_sample_guided_rng(const ds_denoiser* h, int64_t* toke
     s.kv = kv; s.workspace = workspace; s.tokens2 = tokens2;
     return run_chain(h, s, ChainCall{tokens, tokens_tmp, t_steps, n_calls, 4 * (size_t)B, 2 * (size_t)B, nullptr});
 }
+
+// ---- caption tracks (sampler.hip SampleCompose; StepCall::tokens2 with n_cond = n_tracks + 1, which these entries require);
+// workspace: ds_denoiser_workspace_bytes(h, (n_tracks + 1) B); keep == NULL: unheld.  n_tracks sizes the forward, so its range
+// is the entry's own test; the tail's checker states it again for the tail entries.
+#define DS_COMPOSED_ARGS(noise_) \
+    DS_CHECK_ARG((noise_) && tokensN && weights, "bad arguments (null noise source, tokensN or weights)"); \
+    DS_CHECK_ARG(n_tracks >= 1 && n_tracks <= DS_MAX_TRACKS, "n_tracks must be in 1 .. 4")
+extern "C" int ds_denoiser_step_composed(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t,
+                                         const int64_t* t_post, const float* kv, const float* u, int B, int initial,
+                                         float trunc_r, int trunc_k, int n_tracks, const float* weights,
+                                         const unsigned char* keep, const int64_t* known, int mode, int64_t* tokensN,
+                                         void* workspace, int64_t* tokens_out, ds_stream_t stream) {
+    DS_COMPOSED_ARGS(u);
+    StepCall s{{__func__, DS_TAIL_POSTERIOR, stream}};
+    TailCall& c = s.tail;
+    c.B = B; c.u = u; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    c.keep = keep; c.known = known; c.mode = mode; c.weights = weights; c.n_tracks = n_tracks;
+    s.tokens_in = tokens_in; s.tokens_out = tokens_out; s.t = t; s.t_post = t_post; s.kv = kv; s.workspace = workspace;
+    s.tokens2 = tokensN; s.n_cond = n_tracks + 1;
+    return step(h, s);
+}
+
+extern "C" int ds_denoiser_step_composed_rng(const ds_denoiser* h, const int64_t* tokens_in, const int64_t* t,
+                                             const int64_t* t_post, const float* kv, const int64_t* gids,
+                                             unsigned long long seed, int call, int B, int initial, float trunc_r,
+                                             int trunc_k, int n_tracks, const float* weights, const unsigned char* keep,
+                                             const int64_t* known, int mode, int64_t* tokensN, void* workspace,
+                                             int64_t* tokens_out, ds_stream_t stream) {
+    DS_COMPOSED_ARGS(gids);
+    StepCall s{{__func__, DS_TAIL_POSTERIOR, stream}};
+    TailCall& c = s.tail;
+    c.B = B; c.gids = gids; c.seed = seed; c.call = call; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    c.keep = keep; c.known = known; c.mode = mode; c.weights = weights; c.n_tracks = n_tracks;
+    s.tokens_in = tokens_in; s.tokens_out = tokens_out; s.t = t; s.t_post = t_post; s.kv = kv; s.workspace = workspace;
+    s.tokens2 = tokensN; s.n_cond = n_tracks + 1;
+    return step(h, s);
+}
+
+// the whole composed chain: t_steps is i64[n_calls][2][(n_tracks + 1) B]
+extern "C" int ds_denoiser_sample_composed_rng(const ds_denoiser* h, int64_t* tokens, int64_t* tokens_tmp,
+                                               const int64_t* t_steps, int n_calls, const float* kv, const int64_t* gids,
+                                               unsigned long long seed, int call0, int B, int initial, float trunc_r,
+                                               int trunc_k, int n_tracks, const float* weights, const unsigned char* keep,
+                                               const int64_t* known, int mode, int64_t* tokensN, void* workspace,
+                                               ds_stream_t stream) {
+    DS_COMPOSED_ARGS(gids);
+    StepCall s{{__func__, DS_TAIL_POSTERIOR, stream}};
+    TailCall& c = s.tail;
+    c.B = B; c.gids = gids; c.seed = seed; c.call = call0; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    c.keep = keep; c.known = known; c.mode = mode; c.weights = weights; c.n_tracks = n_tracks;
+    s.kv = kv; s.workspace = workspace; s.tokens2 = tokensN; s.n_cond = n_tracks + 1;
+    const size_t Bf = (size_t)(n_tracks + 1) * B;
+    return run_chain(h, s, ChainCall{tokens, tokens_tmp, t_steps, n_calls, 2 * Bf, Bf, nullptr});
+}
+#undef DS_COMPOSED_ARGS
 
 // ---- purity-prior sampling (sampler.hip SamplePurity): forward + purity tail.  tokens2 == NULL: the forward at batch B; else
 // the guided forward at batch 2B, the tail mixing the two halves of the logits.  scratch: ds_purity_scratch_bytes, a pointer

@@ -32,6 +32,9 @@ struct TailCall {
     const int64_t* known = nullptr;
     int mode = 0;
     float scale = 0.f;                       // the guidance scale, read with logits_u
+    const float* weights = nullptr;          // non-null: composed (caption tracks); f32[B][n_tracks][L] track weights, and
+    int n_tracks = 0;                        //   logits holds n_tracks + 1 slabs (tracks, then the null condition),
+    size_t track_stride = 0;                 //   track_stride floats apart.  Not with logits_u, not with DS_TAIL_PURITY.
     int remain = 0;                          // purity only, from here on
     float weight = 0.f;
     void* scratch = nullptr;                 // ds_purity_scratch_bytes
@@ -40,6 +43,8 @@ struct TailCall {
     int32_t* dbg_cand = nullptr;
 };
 
+// (The VALUES of weights live on the device: checking that they are finite would take a synchronisation, so it is the
+// caller's job -- the Python layer does it, DiffusionTransformer._tracks.  A non-finite weight gives a non-finite prediction.)
 int ds_sample_tail_check(const TailCall& c);    // every argument rule, once: -1 and a message naming c.who, no HIP call
 int ds_sample_tail_launch(const TailCall& c);   // a checked call: fills the kernel arguments, selects the kernel
 

@@ -142,6 +142,24 @@ struct SamplePurity {
     float weight;                // r >= 0
 };
 
+// COMPOSED form (caption tracks: the *_composed entries).  The general form of the guided mix: C = n_tracks captions per clip,
+// each with its own weight at every grid position.  p.logits holds C + 1 slabs, track_stride floats apart, each in the row
+// layout of the plain tail (same lrows): tracks 0 .. C-1, the null condition LAST.  Per column, in float64,
+//   g = lu;  for i = 0 .. C-1 in index order:  g = g + w[b][i][pos] (l_i - lu);   g <- g - logsumexp(g)  (max-shifted),
+// with lu, l_i the predict_start of the null row and of track i's row; rounded to f32 and clamped to [-70, 0] it is the log_pred
+// that truncation, posterior and Gumbel-argmax consume unchanged.  C = 1 with a constant weight s is the guided kernel's own
+// expression (lu + s (lc - lu): the same f64 operations in the same order), so its results are the guided tail's bit for bit.
+// A track whose weight at the position is exactly 0 is NOT READ there: the weight is wave-uniform (one per column), so one
+// scalar branch skips its predict_start; its term is exactly 0, so no bit changes.  All weights zero: the null prediction.
+// Negative weights push away from a caption.  A separate kernel argument and ONE separate __global__ wrapper per (K, noise
+// source), taking SampleHold with keep == nullptr meaning unheld, as the guided wrapper does: the other kernels keep their
+// arguments, registers and code.
+struct SampleCompose {
+    const float* weights;        // [B][n_tracks][L]
+    size_t track_stride;         // floats between two slabs of p.logits
+    int n_tracks;                // 1 .. DS_MAX_TRACKS
+};
+
 __device__ __forceinline__ double wmaxd(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
@@ -178,10 +196,11 @@ __device__ __forceinline__ double wmaxd(double v) {
         }                                                                                \
     }
 
-template <int NPL, bool RNG, bool HOLD, bool GUIDED = false, bool PURITY = false>
+template <int NPL, bool RNG, bool HOLD, bool GUIDED = false, bool PURITY = false, bool COMPOSED = false>
 __device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const SampleRng& g, const SampleHold& h,
                                                     const SampleGuide& gd = SampleGuide{nullptr, 1.f},
-                                                    const SamplePurity& pu = SamplePurity{nullptr, nullptr, nullptr, 0.f}) {
+                                                    const SamplePurity& pu = SamplePurity{nullptr, nullptr, nullptr, 0.f},
+                                                    const SampleCompose& cp = SampleCompose{nullptr, 0, 0}) {
     constexpr int K = NPL * 64;
     __shared__ float s_lp[4][K];
     __shared__ __attribute__((aligned(16))) float s_pr[4][K];
@@ -192,7 +211,7 @@ __device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const
     if (!live) col = p.B * p.L - 1;
     const int b = col / p.L, pos = col - b * p.L;
     if constexpr (HOLD) {
-        if ((!GUIDED || h.keep) && h.keep[col]) {       // wave-uniform: the whole wave leaves (no block-wide barrier below in this form)
+        if ((!(GUIDED || COMPOSED) || h.keep) && h.keep[col]) {       // wave-uniform: the whole wave leaves (no block-wide barrier below in this form)
             int tok = (int)h.known[col];
             if constexpr (RNG) {
                 const int tp = (int)p.t[b];
@@ -207,11 +226,32 @@ __device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const
 
     // ---- predict_start: float64 log-softmax over the K real classes ----
     float lp[NPL];
+    if constexpr (COMPOSED) {    // the null condition's row (the last slab) first: lp is lu until the mix below replaces it
+        DS_PREDICT_START_ROW(p.logits + (size_t)cp.n_tracks * cp.track_stride + ((size_t)b * p.lrows + pos) * K, lp)
+    } else {
     DS_PREDICT_START_ROW(p.logits + ((size_t)b * p.lrows + pos) * K, lp)
-    if constexpr (GUIDED) {
+    }
+    if constexpr (GUIDED || COMPOSED) {
         // ---- guidance: lc (in lp), then lu, then the f64 mix and its renormalisation; lp becomes the guided log_pred ----
         double gv[NPL];
-        {
+        if constexpr (COMPOSED) {
+            // ---- caption tracks: g = lu + sum_i w_i (l_i - lu), one track at a time in index order; weight 0: track not read ----
+#pragma unroll
+            for (int j = 0; j < NPL; ++j) gv[j] = (double)lp[j];
+            const float* wp = cp.weights + (size_t)b * cp.n_tracks * p.L + pos;
+            const float* lt = p.logits + ((size_t)b * p.lrows + pos) * K;
+            for (int i = 0; i < cp.n_tracks; ++i) {
+                // one weight per column: made scalar, so the test is one scalar branch of the whole wave
+                const float wi = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(wp[(size_t)i * p.L])));
+                if (wi != 0.f) {
+                    float li[NPL];
+                    DS_PREDICT_START_ROW(lt + (size_t)i * cp.track_stride, li)
+                    const double s = (double)wi;
+#pragma unroll
+                    for (int j = 0; j < NPL; ++j) gv[j] = gv[j] + s * ((double)li[j] - (double)lp[j]);
+                }
+            }
+        } else {
             float lu[NPL];
             DS_PREDICT_START_ROW(gd.logits_u + ((size_t)b * p.lrows + pos) * K, lu)
             const double s = (double)gd.scale;
@@ -496,6 +536,14 @@ template <int NPL, bool RNG, bool GUIDED>
 __global__ __launch_bounds__(256) void ds_sample_purity_rows_kernel(const SampleParams p, const SampleRng g, const SampleGuide gd,
                                                                     const SamplePurity pu) {
     ds_sample_tail_body<NPL, RNG, false, GUIDED, true>(p, g, SampleHold{nullptr, nullptr, 0}, gd, pu);
+}
+
+// the composed tail (see SampleCompose): the posterior tail on the mix of n_tracks captions and the null condition
+template <int NPL, bool RNG>
+__global__ __launch_bounds__(256) void ds_sample_tail_composed_kernel(const SampleParams p, const SampleRng g, const SampleHold h,
+                                                                      const SampleCompose cp) {
+    ds_sample_tail_body<NPL, RNG, true, false, false, true>(p, g, h, SampleGuide{nullptr, 1.f},
+                                                            SamplePurity{nullptr, nullptr, nullptr, 0.f}, cp);
 }
 
 // step 6: one workgroup per sample.  m = its [MASK] positions, n = max(0, m - remain); the n masked positions of largest key
@@ -885,14 +933,20 @@ extern "C" int ds_philox_uniforms(const int64_t* gids, unsigned long long seed, 
 // Every rule of every tail, stated once.  A field a form does not have stays zero in the TailCall and passes its rule.
 int ds_sample_tail_check(const TailCall& c) {
     const bool purity = c.kind == DS_TAIL_PURITY, guided = c.logits_u != nullptr;
+    const bool composed = c.weights != nullptr || c.n_tracks != 0;        // a composed entry; its rules are the guided form's plus:
     const char* msg =
-        !(c.logits && c.xt && (c.u || c.gids) && c.out_tokens && (purity ? c.scratch && c.B > 0 : c.t && c.sched))
+        (composed && !c.weights)                                          ? "null pointer (weights: the track weights)"
+        : (composed && !(c.n_tracks >= 1 && c.n_tracks <= DS_MAX_TRACKS)) ? "n_tracks must be in 1 .. 4"
+        : (composed && guided)  ? "caption tracks carry their own null condition: not together with logits_u"
+        : (composed && purity)                                            ? "caption tracks have no purity form"
+        : !(c.logits && c.xt && (c.u || c.gids) && c.out_tokens && (purity ? c.scratch && c.B > 0 : c.t && c.sched))
                                                                          ? "null pointer"
         // (the unguided posterior tails never tested these three, and which calls are accepted is part of the ABI)
-        : (!purity && guided && !(c.B > 0 && c.L > 0 && c.T > 0))         ? "B, L and T must be positive"
+        : (!purity && (guided || composed) && !(c.B > 0 && c.L > 0 && c.T > 0)) ? "B, L and T must be positive"
         : !(c.K == 256 || c.K == 512)                                     ? "codebook size must be 256 or 512"
         : (purity && !(c.L > 0 && c.L <= DS_PURITY_MAX_L))                ? "L must be in 1 .. 288"
         : !(c.logits_rows >= c.L && c.L < 65536)                          ? "logits rows per sample"
+        : (composed && c.track_stride < (size_t)c.B * c.logits_rows * c.K) ? "track_stride is smaller than one slab of logits"
         : (purity && c.remain < 0)                                        ? "remain must be >= 0"
         : (purity && !(c.weight >= 0.f && c.weight - c.weight == 0.f))    ? "the purity weight must be finite and >= 0"
         : (guided && !(c.scale - c.scale == 0.f))                         ? "the guidance scale must be finite"
@@ -907,7 +961,7 @@ int ds_sample_tail_check(const TailCall& c) {
 }
 
 // The (K, noise source) ladder, once: LAUNCH_(NPL, RNG) launches that instantiation of the call's kernel family.  The families
-// stand in the order held, plain, guided, purity because hipcc emits the kernels in the order of their first mention: it
+// stand in the order held, plain, guided, purity, composed because hipcc emits the kernels in the order of their first mention: it
 // is the order the code object has always had, which keeps its device code comparable byte for byte across host-side edits.
 #define DS_TAIL_LADDER(LAUNCH_)                   \
     do {                                          \
@@ -920,6 +974,8 @@ int ds_sample_tail_check(const TailCall& c) {
 #define DS_TAIL_PLAIN(NPL_, RNG_) hipLaunchKernelGGL((ds_sample_tail_kernel<NPL_, RNG_>), grid, block, 0, stream, p, g)
 #define DS_TAIL_GUIDED(NPL_, RNG_) \
     hipLaunchKernelGGL((ds_sample_tail_guided_kernel<NPL_, RNG_>), grid, block, 0, stream, p, g, h, gd)
+#define DS_TAIL_COMPOSED(NPL_, RNG_) \
+    hipLaunchKernelGGL((ds_sample_tail_composed_kernel<NPL_, RNG_>), grid, block, 0, stream, p, g, h, cp)
 #define DS_TAIL_PURITY(NPL_, RNG_)                                                                                           \
     do {                                                                                                                     \
         if (guided) hipLaunchKernelGGL((ds_sample_purity_rows_kernel<NPL_, RNG_, true>), grid, block, 0, stream, p, g, gd, pu); \
@@ -928,7 +984,7 @@ int ds_sample_tail_check(const TailCall& c) {
 
 int ds_sample_tail_launch(const TailCall& c) {
     hipStream_t stream = (hipStream_t)c.stream;
-    const bool purity = c.kind == DS_TAIL_PURITY, guided = c.logits_u != nullptr;
+    const bool purity = c.kind == DS_TAIL_PURITY, guided = c.logits_u != nullptr, composed = c.weights != nullptr;
     const long long cols = (long long)c.B * c.L;
     int* cand = (int*)c.scratch;                             // purity: the rows kernel leaves (candidate, key) per grid position
     float* key = purity ? (float*)(cand + cols) : nullptr;   //   here, and the select kernel writes the tokens
@@ -938,11 +994,13 @@ int ds_sample_tail_launch(const TailCall& c) {
     const SampleHold h{c.keep, c.known, c.mode};             // the guided kernels take it with keep == nullptr: unheld
     const SampleGuide gd{c.logits_u, c.scale};
     const SamplePurity pu{cand, key, c.dbg_sharp, c.weight};
+    const SampleCompose cp{c.weights, c.track_stride, c.n_tracks};
     const dim3 grid((unsigned)((cols + 3) / 4)), block(256);
-    if (!purity && !guided && c.keep) DS_TAIL_LADDER(DS_TAIL_HOLD);
-    else if (!purity && !guided) DS_TAIL_LADDER(DS_TAIL_PLAIN);
-    else if (!purity) DS_TAIL_LADDER(DS_TAIL_GUIDED);
-    else DS_TAIL_LADDER(DS_TAIL_PURITY);
+    if (!purity && !guided && !composed && c.keep) DS_TAIL_LADDER(DS_TAIL_HOLD);
+    else if (!purity && !guided && !composed) DS_TAIL_LADDER(DS_TAIL_PLAIN);
+    else if (!purity && !composed) DS_TAIL_LADDER(DS_TAIL_GUIDED);
+    else if (purity) DS_TAIL_LADDER(DS_TAIL_PURITY);
+    else DS_TAIL_LADDER(DS_TAIL_COMPOSED);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && purity) {
         hipLaunchKernelGGL(ds_sample_purity_select_kernel, dim3(c.B), dim3(256), 0, stream, c.xt, (const int*)cand,
@@ -966,6 +1024,7 @@ int ds_sample_tail_launch(const TailCall& c) {
 #undef DS_TAIL_PLAIN
 #undef DS_TAIL_GUIDED
 #undef DS_TAIL_PURITY
+#undef DS_TAIL_COMPOSED
 
 static int tail_run(const TailCall& c) {
     const int rc = ds_sample_tail_check(c);
@@ -1056,6 +1115,40 @@ extern "C" int ds_sample_tail_guided_rng(const float* logits_c, const float* log
     DS_CHECK_ARG(gids && logits_u, "null pointer (logits_u: the null-condition logits)");
     TailCall c{__func__, DS_TAIL_POSTERIOR, stream};
     c.logits = logits_c; c.logits_u = logits_u; c.scale = scale; c.logits_rows = L;
+    c.xt = xt; c.t = t; c.sched = sched; c.out_tokens = out_tokens;
+    c.gids = gids; c.seed = seed; c.call = call;
+    c.B = B; c.L = L; c.K = K; c.T = T; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    c.keep = keep; c.known = known; c.mode = mode;
+    return tail_run(c);
+}
+
+// the composed tails (see SampleCompose): logits f32[n_tracks + 1][B * L][K], tracks first, the null condition last;
+// weights f32[B][n_tracks][L] (finite: not checked here, see the header); keep == nullptr: unheld
+extern "C" int ds_sample_tail_composed(const float* logits, const int64_t* xt, const int64_t* t, const float* u,
+                                       const float* sched, int64_t* out_tokens, float* dbg_log_pred, float* dbg_trunc,
+                                       float* dbg_post, int B, int L, int K, int T, int initial, float trunc_r, int trunc_k,
+                                       int n_tracks, const float* weights, const unsigned char* keep, const int64_t* known,
+                                       int mode, ds_stream_t stream) {
+    DS_CHECK_ARG(u && weights, "null pointer (weights: the track weights)");
+    TailCall c{__func__, DS_TAIL_POSTERIOR, stream};
+    c.logits = logits; c.logits_rows = L; c.weights = weights; c.n_tracks = n_tracks;
+    c.track_stride = B > 0 && L > 0 && K > 0 ? (size_t)B * L * K : 0;
+    c.xt = xt; c.t = t; c.u = u; c.sched = sched; c.out_tokens = out_tokens;
+    c.dbg_log_pred = dbg_log_pred; c.dbg_trunc = dbg_trunc; c.dbg_post = dbg_post;
+    c.B = B; c.L = L; c.K = K; c.T = T; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    c.keep = keep; c.known = known; c.mode = mode;
+    return tail_run(c);
+}
+
+extern "C" int ds_sample_tail_composed_rng(const float* logits, const int64_t* xt, const int64_t* t, const int64_t* gids,
+                                           unsigned long long seed, int call, const float* sched, int64_t* out_tokens, int B,
+                                           int L, int K, int T, int initial, float trunc_r, int trunc_k, int n_tracks,
+                                           const float* weights, const unsigned char* keep, const int64_t* known, int mode,
+                                           ds_stream_t stream) {
+    DS_CHECK_ARG(gids && weights, "null pointer (weights: the track weights)");
+    TailCall c{__func__, DS_TAIL_POSTERIOR, stream};
+    c.logits = logits; c.logits_rows = L; c.weights = weights; c.n_tracks = n_tracks;
+    c.track_stride = B > 0 && L > 0 && K > 0 ? (size_t)B * L * K : 0;
     c.xt = xt; c.t = t; c.sched = sched; c.out_tokens = out_tokens;
     c.gids = gids; c.seed = seed; c.call = call;
     c.B = B; c.L = L; c.K = K; c.T = T; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;

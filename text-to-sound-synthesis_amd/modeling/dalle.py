@@ -144,6 +144,61 @@ class DALLE(nn.Module):
             null = torch.cat([null for _ in range(replicate)], dim=0)
         return {"guidance_scale": float(guidance_scale), "null_condition_embed": null}
 
+    def _track_keywords(self, batch, tracks, replicate, sample_type, total_cols=None):
+        """sample()'s caption-track keywords (DiffusionTransformer.sample: track_embed, track_weight) from `tracks`, a dict:
+        'text' -- C captions (each for the whole batch) or C lists of B captions, each track through prepare_condition's text
+        stage once; 'weight' -- f32[B, C, 265] (time-major like content_token; pipeline.track_weights builds it from
+        seconds), or f32[B, C, 5 total_cols] for the long form.  A model without a text stage takes 'embed' f32[C, B, 77, 512]
+        instead of 'text', mirroring null_condition_embed_token.  The null condition is batch['negative_text'] or the empty
+        caption, as for guidance.  None: no keywords, today's path.  The rules are checked before anything runs."""
+        if tracks is None:
+            return None
+        if replicate != 1:
+            raise ValueError("replicate must be 1 with tracks: repeat the scene under different caption_ids instead")
+        if self._purity_part(sample_type) is not None:
+            raise ValueError("caption tracks have no purity form: sample type %r" % (sample_type,))
+        if tracks.get("weight") is None:
+            raise ValueError("tracks needs 'weight': f32[B, C, 265]")
+        tr = self.transformer
+        w = torch.as_tensor(tracks["weight"]).float()
+        L = tr.content_seq_len if total_cols is None else 5 * int(total_cols)
+        if w.dim() != 3 or w.shape[2] != L or not 1 <= w.shape[1] <= tr.MAX_TRACKS:
+            raise ValueError("tracks['weight'] must be f32[B, C, %d] with 1 <= C <= %d, got %s" % (L, tr.MAX_TRACKS, tuple(w.shape)))
+        if not bool(torch.isfinite(w).all()):
+            raise ValueError("tracks['weight'] must be finite")
+        B, C = w.shape[0], w.shape[1]
+        if self.condition_codec is None or tr.condition_emb is None:
+            if tracks.get("embed") is None:
+                raise ValueError("this model has no text stage (condition_codec / condition_emb): pass tracks['embed'] "
+                                 "f32[C, B, 77, 512]")
+            emb = torch.as_tensor(tracks["embed"]).float().to(self.device)
+        else:
+            text = tracks.get("text")
+            if text is None or isinstance(text, str) or len(text) != C:
+                raise ValueError("tracks['text'] must hold one caption (or one list of B captions) per track: %d" % C)
+            embs = []
+            for caps in text:
+                caps = [caps] * B if isinstance(caps, str) else list(caps)
+                if len(caps) != B:
+                    raise ValueError("a track's caption list must have B = %d entries, got %d" % (B, len(caps)))
+                cond = self.prepare_condition({self.condition_info["key"]: caps})
+                embs.append(tr._cond(cond.get("condition_token"), cond.get("condition_embed_token")).to(self.device))
+            emb = torch.stack(embs, 0)
+        if tuple(emb.shape[:2]) != (C, B):
+            raise ValueError("tracks['embed'] must be f32[C, B, 77, 512] = [%d, %d, ...], got %s" % (C, B, tuple(emb.shape)))
+        return {"track_embed": emb, "track_weight": w, "null_condition_embed": self.null_condition(batch.get("negative_text"), batch=batch)}
+
+    @staticmethod
+    def _window_tracks(kw, w, overlap_cols):
+        """the track keywords of window w of the long form: the weight's slice over the window's own global columns
+        [w (53 - n), w (53 - n) + 53), time-major"""
+        from ..pipeline import GRID_COLS
+        if kw is None:
+            return None
+        wt = kw["track_weight"]
+        c0 = w * (GRID_COLS - overlap_cols)
+        return dict(kw, track_weight=wt[:, :, 5 * c0:5 * (c0 + GRID_COLS)].contiguous())
+
     def _install_sample_type(self, sample_type):
         """The `sample_type` mini-language (:179-247) applied to the transformer; returns its comma-separated parts."""
         parts = sample_type.split(",")
@@ -201,7 +256,7 @@ class DALLE(nn.Module):
         """the chain keywords of inpaint_content: the positions of `keep` carry `tokens`"""
         return dict(content_token=tokens, filter_ratio=0, return_logits=False, print_log=False, keep_mask=keep, keep_mode=keep_mode)
 
-    def _run_chain(self, batch, condition, kw, replicate, sample_type, guidance_scale):
+    def _run_chain(self, batch, condition, kw, replicate, sample_type, guidance_scale, tracks=None):
         """What generate_content, inpaint_content and generate_long_content share once the chain's own keywords `kw` are set:
         install the sample type, add the (replicated) condition, the guidance and the noise keywords of `batch`, run sample(),
         sample_fast() or -- for a sample type with a ",purity{S}" part (_purity_part) -- sample_purity() -> tokens i64[B r, 265]."""
@@ -211,6 +266,8 @@ class DALLE(nn.Module):
         kw = dict(kw, condition_token=condition.get("condition_token"), condition_mask=condition.get("condition_mask"),
                   condition_embed=condition.get("condition_embed_token"))
         kw.update(self._guidance(batch, guidance_scale, replicate))
+        if tracks is not None:                               # caption tracks (_track_keywords): guidance_scale must be None
+            kw.update(tracks, guidance_scale=guidance_scale)
         if batch.get("caption_ids") is not None:             # per-caption in-kernel noise (diffusion.py rng_mode)
             kw["caption_ids"] = self._replicated_caption_ids(batch, replicate)
         if batch.get("seed") is not None:
@@ -222,7 +279,8 @@ class DALLE(nn.Module):
         return tr.sample(**kw)["content_token"]
 
     @torch.no_grad()
-    def inpaint_content(self, *, batch, keep_mask, keep_mode="clamp", replicate=1, sample_type="top0.85r", guidance_scale=None):
+    def inpaint_content(self, *, batch, keep_mask, keep_mode="clamp", replicate=1, sample_type="top0.85r", guidance_scale=None,
+                        tracks=None):
         """Region-held generation (not in the reference, whose content_ratio slices the token vector and cannot run for any
         value but 1): the positions of `keep_mask` (bool[B, 265], True = held, time-major like content_token;
         pipeline.spans_to_keep_mask builds it from seconds) keep the tokens of the batch's content, the others are generated
@@ -234,9 +292,11 @@ class DALLE(nn.Module):
 
         The held TOKENS of the result are exactly the input's.  The mel is the codec's rendering of the whole grid, held
         region included: not the input's samples (the decoder's lowest level attends over all 265 positions), and the
-        original mel or audio is not pasted back."""
+        original mel or audio is not pasted back.
+        tracks: caption tracks as in generate_content -- the free positions are generated under the scene."""
+        trk = self._track_keywords(batch, tracks, replicate, sample_type)
         self.eval()
-        condition = self.prepare_condition(batch=batch)
+        condition = self.prepare_condition(batch=batch) if trk is None else {}
         tokens = batch.get("content_token")
         if tokens is None:
             tokens = self.prepare_content(batch)["content_token"]
@@ -249,27 +309,32 @@ class DALLE(nn.Module):
             tokens = torch.cat([tokens for _ in range(replicate)], dim=0)
             keep = torch.cat([keep for _ in range(replicate)], dim=0)
         out_tokens = self._run_chain(batch, condition, self._hold_keywords(tokens, keep, keep_mode), replicate, sample_type,
-                                     guidance_scale)
+                                     guidance_scale, trk)
         content = self.decode_to_img(out_tokens, (out_tokens.shape[0], 256, 5, 53))
         self.train()
         return {"content": content, "content_token": out_tokens}
 
     @torch.no_grad()
     def generate_content(self, *, batch, condition=None, filter_ratio=0.5, temperature=1.0, content_ratio=0.0,
-                         replicate=1, return_att_weight=False, sample_type="top0.85r", guidance_scale=None):
+                         replicate=1, return_att_weight=False, sample_type="top0.85r", guidance_scale=None,
+                         tracks=None):
         """guidance_scale (not in the reference): classifier-free guidance of every sampler step against the null condition
         -- the empty caption, or batch['negative_text'] (a caption or a list of B) -- see DiffusionTransformer.sample and
         null_condition; None or exactly 1 is the unguided path.
         sample_type (beyond the reference's forms): a ",purity{S}" or ",purity{S}w{r}" part, e.g. "top0.85r,purity25", runs an
-        S-step purity-prior chain instead (_purity_part, DiffusionTransformer.sample_purity; filter_ratio must resolve to 0)."""
+        S-step purity-prior chain instead (_purity_part, DiffusionTransformer.sample_purity; filter_ratio must resolve to 0).
+        tracks (not in the reference): caption tracks, a scene instead of one caption -- {'text': C captions or C lists of B,
+        'weight': f32[B, C, 265]} (_track_keywords; pipeline.track_weights builds both from (caption, start, end) triples).
+        The batch then needs no caption; replicate must be 1 and guidance_scale None."""
+        trk = self._track_keywords(batch, tracks, replicate, sample_type)
         self.eval()
-        condition = self.prepare_condition(batch=batch, condition=condition)
+        condition = self.prepare_condition(batch=batch, condition=condition) if trk is None else {}
         if replicate != 1:
             for k in condition:
                 if condition[k] is not None:
                     condition[k] = torch.cat([condition[k] for _ in range(replicate)], dim=0)
         tokens = self._run_chain(batch, condition, self._free_keywords(filter_ratio, temperature, return_att_weight, sample_type),
-                                 replicate, sample_type, guidance_scale)
+                                 replicate, sample_type, guidance_scale, trk)
         zshape = (tokens.shape[0], 256, 5, 53)   # hard-coded in the reference too (:236)
         content = self.decode_to_img(tokens, zshape)
         self.train()
@@ -277,7 +342,7 @@ class DALLE(nn.Module):
 
     @torch.no_grad()
     def generate_long_content(self, *, batch, windows, overlap_cols, keep_mode="clamp", sample_type="top0.85r",
-                              guidance_scale=None, start_token=None):
+                              guidance_scale=None, start_token=None, tracks=None):
         """A clip longer than one token grid as `windows` overlapping 5 x 53 grids (not in the reference; the plan comes from
         pipeline.long_plan).  Window 0 is what generate_content(filter_ratio=0, content_ratio=1) generates with per-caption
         in-kernel noise (batch['caption_ids'], default 0 .. B-1; batch['seed']) -- or start_token (i64[B, 265], e.g. a
@@ -287,6 +352,8 @@ class DALLE(nn.Module):
         with the caption ids + w 2^20 (pipeline.window_caption_ids: ids must be below 2^20, which keeps the windows apart from
         each other and from the replicate stride 2^24).  All windows are decoded in ONE decode_to_img call at batch B W.
         The model's truncation settings are this call's only: saved before and restored after.
+        tracks: caption tracks as in generate_content with 'weight' f32[B, C, 5 total columns], total columns =
+        53 + (W - 1)(53 - overlap_cols); window w runs under the slice over its own global columns (_window_tracks).
         Returns {'content_token': i64[B, W, 265], 'content': mel image [B W, 1, 80, 848], clip-major (index b W + w)}."""
         from ..pipeline import GRID_COLS, MAX_WINDOWS, continuation_tokens, window_caption_ids
         windows, n = int(windows), int(overlap_cols)
@@ -294,9 +361,10 @@ class DALLE(nn.Module):
             raise ValueError("windows must be in 1 .. %d, got %r" % (MAX_WINDOWS, windows))
         if not 1 <= n <= GRID_COLS // 2:
             raise ValueError("overlap_cols must be in 1 .. %d, got %r" % (GRID_COLS // 2, overlap_cols))
+        trk = self._track_keywords(batch, tracks, 1, sample_type, GRID_COLS + (windows - 1) * (GRID_COLS - n))
         self.eval()
-        condition = self.prepare_condition(batch=batch)
-        B = next(v.shape[0] for v in condition.values() if torch.is_tensor(v))
+        condition = self.prepare_condition(batch=batch) if trk is None else {}
+        B = next(v.shape[0] for v in condition.values() if torch.is_tensor(v)) if trk is None else trk["track_weight"].shape[0]
         ids = batch.get("caption_ids")
         ids = torch.arange(B) if ids is None else torch.as_tensor(ids, dtype=torch.long).reshape(-1)
         if ids.numel() != B:
@@ -313,12 +381,13 @@ class DALLE(nn.Module):
                     raise ValueError("start_token must be i64[%d, %d], got %s" % (B, tr.content_seq_len, tuple(cur.shape)))
             else:
                 cur = self._run_chain(dict(batch, caption_ids=ids), condition, self._free_keywords(0, 1.0, False, sample_type), 1,
-                                      sample_type, guidance_scale)
+                                      sample_type, guidance_scale, self._window_tracks(trk, 0, n))
             toks = [cur]
             for w in range(1, windows):
                 known, keep = continuation_tokens(cur, n)
                 cur = self._run_chain(dict(batch, caption_ids=window_caption_ids(ids, w)), condition,
-                                      self._hold_keywords(known, keep, keep_mode), 1, sample_type, guidance_scale)
+                                      self._hold_keywords(known, keep, keep_mode), 1, sample_type, guidance_scale,
+                                      self._window_tracks(trk, w, n))
                 toks.append(cur)
         finally:
             tr.truncation_r, tr.truncation_k, tr.repeat_rate, self.truncation_forward = saved

@@ -216,31 +216,41 @@ class DiffusionTransformer(nn.Module):
     def _step_entry(self, chain, noise, B, initial, hold, guide, slot=0):
         """The C entry of one reverse step (chain False: ds_denoiser_step_*) or of a whole chain (True: ds_denoiser_sample_*)
         and the arguments its forms share.  noise: the uniforms u, or (caption_ids, call, seed) for the in-kernel Philox draw;
-        hold: None or (keep, known, mode) -- plain and held are different entries; guide: None or (kv2, scale, tokens2).
+        hold: None or (keep, known, mode) -- plain and held are different entries; guide: None, (kv2, scale, tokens2), or
+        the composed form (kvN, None, tokensN, weights, C) of caption tracks (_guide_start).
         Returns (entry, the noise arguments, the arguments from B to the workspace); the caller's part is what comes
         before (handle, tokens, timesteps, kv) and after (the step's output tokens, the stream)."""
         rng = isinstance(noise, tuple)
-        family = "_guided" if guide is not None else "_hold" if hold is not None else ""
+        composed = guide is not None and len(guide) == 5
+        family = "_composed" if composed else "_guided" if guide is not None else "_hold" if hold is not None else ""
         name = "ds_denoiser_%s%s%s" % ("sample" if chain else "step", family, "_rng" if rng else "" if family else "_ex")
         r, k = self._truncation()
         args = [B, 0 if hold is not None else int(initial), r, k]
-        if guide is not None:
+        if composed:
+            args += [int(guide[4]), _lib.ptr(guide[3])]
+        elif guide is not None:
             args.append(float(guide[1]))
         if family:
             keep, known, mode = hold if hold is not None else (None, None, 0)
             args += [_lib.ptr(keep), _lib.ptr(known), int(mode)]
         if guide is not None:
             args.append(_lib.ptr(guide[2]))
-        args.append(_lib.ptr(self.transformer.workspace(2 * B if guide is not None else B, self._schedule_table(), slot)))
+        args.append(_lib.ptr(self.transformer.workspace(self._n_cond(guide) * B, self._schedule_table(), slot)))
         noise = [_lib.ptr(noise[0]), self._seed(noise[2]), int(noise[1])] if rng else [_lib.ptr(noise)]
         return getattr(_lib.lib(), name), noise, args
+
+    @staticmethod
+    def _n_cond(guide):
+        """conditions per clip of a step: 1 unguided, 2 guided, C + 1 with C caption tracks"""
+        return 1 if guide is None else guide[4] + 1 if len(guide) == 5 else 2
 
     def _p_sample(self, x_t, kv, t, noise, initial, out, t_post, slot, hold, guide):
         p = self.transformer.packed(self._schedule_table())
         if out is None:
             out = torch.empty_like(x_t)
         if guide is not None:                        # (named: alive until the launch is enqueued)
-            kv, t, t_post = guide[0], t.repeat(2), None if t_post is None else t_post.repeat(2)
+            n = self._n_cond(guide)
+            kv, t, t_post = guide[0], t.repeat(n), None if t_post is None else t_post.repeat(n)
         entry, noise, args = self._step_entry(False, noise, x_t.shape[0], initial, hold, guide, slot)
         _lib.check(entry(p["handle"], _lib.ptr(x_t), _lib.ptr(t), _lib.ptr(t_post), _lib.ptr(kv), *noise, *args, _lib.ptr(out),
                          _lib.stream()))
@@ -252,7 +262,7 @@ class DiffusionTransformer(nn.Module):
         vector when it differs from the network's (sample_fast).  hold: (keep u8[B,L], known i64[B,L], mode) of the
         region-held step (_hold_start); on caller uniforms only mode 0 (clamp) exists.  guide: (kv2, scale, tokens2) of
         the guided step (_guide_start: the K/V of captions + null conditions at batch 2B, the guidance scale, an
-        i64[2B,L] scratch); kv is not read then."""
+        i64[2B,L] scratch) or its composed form (kvN, None, tokensN, weights, C) for C caption tracks; kv is not read then."""
         return self._p_sample(x_t, kv, t, u, initial, out, t_post, slot, hold, guide)
 
     @torch.no_grad()
@@ -460,11 +470,55 @@ class DiffusionTransformer(nn.Module):
                              % (want[1:], want, tuple(torch.as_tensor(null_condition_embed).shape)))
         return null.to(self.device), scale
 
+    MAX_TRACKS = 4       # DS_MAX_TRACKS (include/diffsound_hip.h)
+
+    def _tracks(self, track_embed, track_weight, null_condition_embed, guidance_scale):
+        """Caption tracks of sample() / sample_fast(): None when both keywords are None (today's path), else
+        (null f32[B,77,512], weights f32[B,C,L], embeds f32[C,B,77,512]) on the model's device -- the `guide` of the composed
+        entries.  Every rule that can be checked on the host is, before anything runs; the weights' finiteness is one of
+        them (the C layer cannot see device values without a synchronisation)."""
+        if track_embed is None and track_weight is None:
+            return None
+        if track_embed is None or track_weight is None:
+            raise ValueError("caption tracks need both track_embed f32[C,B,77,512] and track_weight f32[B,C,%d]"
+                             % self.content_seq_len)
+        if guidance_scale is not None:
+            raise ValueError("caption tracks carry their own weights: guidance_scale must be None with track_embed")
+        emb, w = torch.as_tensor(track_embed).float(), torch.as_tensor(track_weight).float()
+        if emb.dim() != 4 or not 1 <= emb.shape[0] <= self.MAX_TRACKS:
+            raise ValueError("track_embed must be f32[C,B,77,512] with 1 <= C <= %d: got %s" % (self.MAX_TRACKS, tuple(emb.shape)))
+        C, B = emb.shape[0], emb.shape[1]
+        if tuple(w.shape) != (B, C, self.content_seq_len):
+            raise ValueError("track_weight must be f32[B,C,%d] = %s for track_embed %s: got %s"
+                             % (self.content_seq_len, (B, C, self.content_seq_len), tuple(emb.shape), tuple(w.shape)))
+        if not bool(torch.isfinite(w).all()):
+            raise ValueError("track_weight must be finite")
+        if null_condition_embed is None:
+            raise ValueError("caption tracks need the null condition: pass null_condition_embed f32[77,512] or [B,77,512] "
+                             "(DALLE.null_condition())")
+        null, _ = self._guide(0.0, null_condition_embed, emb[0])
+        return null, w.to(self.device).contiguous(), emb.to(self.device)
+
+    def _cond_guide(self, condition_token, condition_embed, guidance_scale, null_condition_embed, track_embed, track_weight):
+        """(cond_emb, guide) of sample() / sample_fast(): with caption tracks the guide is _tracks' and cond_emb, which then
+        only gives the batch its size, is track 0's embeddings (condition_embed may be None)."""
+        tracks = self._tracks(track_embed, track_weight, null_condition_embed, guidance_scale)
+        if tracks is not None:
+            return tracks[2][0], tracks
+        cond_emb = self._cond(condition_token, condition_embed)
+        return cond_emb, self._guide(guidance_scale, null_condition_embed, cond_emb)
+
     def _guide_start(self, guide, cond_emb, sched):
         """(kv2, scale, tokens2) of the guided entries: the cross-attention K/V at batch 2B of the captions followed by the
-        null conditions, and the scratch that receives the duplicated tokens of every step."""
-        null, scale = guide
+        null conditions, and the scratch that receives the duplicated tokens of every step.  A 3-tuple of _tracks gives the
+        composed entries' (kvN, None, tokensN, weights, C): K/V at batch (C+1)B, track-major, the null conditions last."""
         B = cond_emb.shape[0]
+        if len(guide) == 3:
+            null, weights, emb = guide
+            C = emb.shape[0]
+            kvn = self.transformer.condition_kv(torch.cat((emb.reshape(C * B, *emb.shape[2:]), null), 0).contiguous(), sched)
+            return kvn, None, torch.empty((C + 1) * B, self.content_seq_len, device=self.device, dtype=torch.long), weights, C
+        null, scale = guide
         kv2 = self.transformer.condition_kv(torch.cat((cond_emb.float(), null), 0).contiguous(), sched)
         return kv2, scale, torch.empty(2 * B, self.content_seq_len, device=self.device, dtype=torch.long)
 
@@ -523,7 +577,7 @@ class DiffusionTransformer(nn.Module):
             p = self.transformer.packed(sched)
             gids = self._caption_ids(caption_ids, B, device)
             t_steps = torch.tensor(calls, dtype=torch.long, device=device).view(-1, 2, 1)
-            t_steps = t_steps.expand(-1, 2, 2 * B if guide is not None else B).contiguous()
+            t_steps = t_steps.expand(-1, 2, self._n_cond(guide) * B).contiguous()
             call0 = 1 if hold is not None and hold[2] == 1 else 0   # renoise: stream-1 call 0 was the start state's q_sample
             entry, noise, args = self._step_entry(True, (gids, call0, seed), B, start_tokens is None, hold, guide)
             _lib.check(entry(p["handle"], _lib.ptr(x), _lib.ptr(nxt), _lib.ptr(t_steps), len(calls),
@@ -551,7 +605,7 @@ class DiffusionTransformer(nn.Module):
     def sample(self, condition_token, condition_mask, condition_embed, content_token=None, filter_ratio=0.5,
                temperature=1.0, return_att_weight=False, return_logits=False, content_logits=None,
                print_log=True, noise_fn=None, caption_ids=None, seed=None, keep_mask=None, keep_mode="clamp",
-               guidance_scale=None, null_condition_embed=None, **kwargs):
+               guidance_scale=None, null_condition_embed=None, track_embed=None, track_weight=None, **kwargs):
         """Reverse diffusion from the all-[MASK] state (:587-659, filter_ratio == 0 branch).
 
         noise_fn(step, shape) may supply the uniforms (tests inject the oracle's noise; with the 'q' repeat sampler
@@ -566,9 +620,15 @@ class DiffusionTransformer(nn.Module):
         guidance_scale (not in the reference): classifier-free guidance -- every step evaluates the denoiser under the
         caption and under null_condition_embed (f32[77,512] or [B,77,512]) in one forward at batch 2B and samples from
         the renormalised mix  log p_null + scale (log p_caption - log p_null)  (csrc/sampler.hip SampleGuide).  None or
-        exactly 1: today's path, untouched, no null forward."""
-        cond_emb = self._cond(condition_token, condition_embed)
-        guide = self._guide(guidance_scale, null_condition_embed, cond_emb)
+        exactly 1: today's path, untouched, no null forward.
+
+        track_embed f32[C,B,77,512] / track_weight f32[B,C,L] (not in the reference): caption tracks -- C <= 4 captions per
+        clip, each weighted per grid position; every step evaluates the denoiser under each of them and under
+        null_condition_embed in one forward at batch (C+1)B and samples from the renormalised mix
+        log p_null + sum_i w_i(pos) (log p_i - log p_null)  (csrc/sampler.hip SampleCompose).  guidance_scale must be None,
+        condition_embed may be; both None: today's path, untouched."""
+        cond_emb, guide = self._cond_guide(condition_token, condition_embed, guidance_scale, null_condition_embed, track_embed,
+                                           track_weight)
         T = self.num_timesteps
         start_step = int(T * filter_ratio)
         if keep_mask is not None:
@@ -611,14 +671,15 @@ class DiffusionTransformer(nn.Module):
     def sample_fast(self, condition_token, condition_mask, condition_embed, content_token=None, filter_ratio=0.5,
                     temperature=1.0, return_att_weight=False, return_logits=False, content_logits=None,
                     print_log=True, skip_step=1, noise_fn=None, caption_ids=None, seed=None, keep_mask=None,
-                    keep_mode="clamp", guidance_scale=None, null_condition_embed=None, **kwargs):
+                    keep_mode="clamp", guidance_scale=None, null_condition_embed=None, track_embed=None, track_weight=None,
+                    **kwargs):
         """Skip-step sampler (:748-812): timesteps T-1, T-2-skip, ... (0 appended), the network sees t, the
         posterior t - skip_step while t > skip_step.  The reference calls p_pred's pieces directly, so the 'q'
         wrapper on p_sample never applies here.  keep_mask / keep_mode: region-held sampling as in sample(); the
         posterior's timestep governs what a renoised position is drawn at.  guidance_scale / null_condition_embed:
-        classifier-free guidance as in sample()."""
-        cond_emb = self._cond(condition_token, condition_embed)
-        guide = self._guide(guidance_scale, null_condition_embed, cond_emb)
+        classifier-free guidance as in sample().  track_embed / track_weight: caption tracks as in sample()."""
+        cond_emb, guide = self._cond_guide(condition_token, condition_embed, guidance_scale, null_condition_embed, track_embed,
+                                           track_weight)
         if keep_mask is not None and int(self.num_timesteps * filter_ratio) != 0:
             raise ValueError("keep_mask samples the free positions from [MASK]: filter_ratio must resolve to step 0")
         assert int(self.num_timesteps * filter_ratio) == 0     # the reference asserts start_step == 0 (:787)
@@ -713,6 +774,8 @@ class DiffusionTransformer(nn.Module):
         repeat sampler and a filter_ratio that does not resolve to step 0).  guidance_scale / null_condition_embed,
         caption_ids / seed as in sample(); noise_fn(k, shape) gets the call index k = 0 .. S-1.  What this sampler does to
         audio quality is unmeasured: no trained checkpoint has been available to this project."""
+        if kwargs.get("track_embed") is not None or kwargs.get("track_weight") is not None:
+            raise ValueError("caption tracks have no purity form: track_embed / track_weight go to sample() or sample_fast()")
         S, weight = self._purity_check(steps, purity_weight, keep_mode, filter_ratio)
         cond_emb = self._cond(condition_token, condition_embed)
         guide = self._guide(guidance_scale, null_condition_embed, cond_emb)

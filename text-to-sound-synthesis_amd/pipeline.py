@@ -146,6 +146,57 @@ def window_caption_ids(caption_ids, window):
     return ids + int(window) * WINDOW_ID_STRIDE
 
 
+MAX_TRACKS = 4                # caption tracks per scene (DS_MAX_TRACKS, include/diffsound_hip.h)
+
+
+def track_weights(tracks, total_cols=GRID_COLS, batch=None):
+    """The caption tracks of a scene (DALLE.generate_content: tracks) from seconds.  A track is (text, t0, t1) or
+    (text, t0, t1, scale): the caption applies over the half-open span [t0, t1) seconds with weight `scale` (default 1;
+    Diffsound.generate_scene fills in its own default); t1 None: to the end of the clip.  `tracks` is one scene -- a list of
+    tracks, shared by `batch` clips (default 1) -- or a list of B scenes.  Column c of a track gets scale x the fraction of the
+    column's 4096 samples [4096 c, 4096 (c + 1)) the span covers (seconds -> samples snapped as in spans_to_keep_mask): scale
+    inside the span, exactly 0 outside, the proportional value in an edge column -- the ramp, with no further parameter --
+    and all five rows of a column share it.  Scenes with fewer tracks are padded with zero-weight tracks of the empty caption
+    up to the largest C.  More than 4 tracks, a span outside [0, 4096 total_cols / 22050], an empty span or a non-finite
+    scale raise ValueError.  Returns (C lists of B captions, f32[B, C, 5 total_cols] time-major like content_token)."""
+    import math
+    is_seq = lambda x: isinstance(x, (list, tuple))
+    is_track = lambda x: is_seq(x) and len(x) in (3, 4) and isinstance(x[0], str)
+    tracks = list(tracks)
+    if all(is_track(t) for t in tracks):
+        scenes = [tracks] * (1 if batch is None else int(batch))
+    elif all(is_seq(sc) and all(is_track(t) for t in sc) for sc in tracks):
+        scenes = [list(sc) for sc in tracks]
+        if batch is not None and len(scenes) != batch:
+            raise ValueError("per-clip scenes: %d lists for a batch of %d" % (len(scenes), batch))
+    else:
+        raise ValueError("a track is (text, t0, t1) or (text, t0, t1, scale); tracks is one scene or a list of scenes")
+    total_cols = int(total_cols)
+    C = max((len(sc) for sc in scenes), default=0)
+    if not 1 <= C <= MAX_TRACKS or not scenes:
+        raise ValueError("a scene has 1 .. %d tracks, got %d" % (MAX_TRACKS, C))
+    end = total_cols * COLUMN_SAMPLES
+    texts = [["" for _ in scenes] for _ in range(C)]
+    weight = torch.zeros(len(scenes), C, total_cols)
+    for b, sc in enumerate(scenes):
+        for i, trk in enumerate(sc):
+            scale = float(trk[3]) if len(trk) == 4 else 1.0
+            if not math.isfinite(scale):
+                raise ValueError("track %r: the scale must be finite" % (trk,))
+            s0, s1 = _seconds_to_samples(trk[1]), float(end) if trk[2] is None else _seconds_to_samples(trk[2])
+            if not (0.0 <= s0 and s1 <= end):
+                raise ValueError("track %r is outside the clip [0, %d / %d s]" % (trk, end, VOCODER_RATE))
+            if not s1 > s0:
+                raise ValueError("track %r is empty: t1 must be greater than t0" % (trk,))
+            texts[i][b] = trk[0]
+            for c in range(total_cols):
+                cover = min(s1, COLUMN_SAMPLES * (c + 1)) - max(s0, COLUMN_SAMPLES * c)
+                if cover > 0:
+                    weight[b, i, c] = scale * (cover / COLUMN_SAMPLES)
+    weight = weight[:, :, :, None].expand(-1, -1, -1, GRID_ROWS).reshape(len(scenes), C, total_cols * GRID_ROWS)
+    return texts, weight.contiguous()
+
+
 def purity_sample_type(sample_type, purity_steps, purity_weight=0.0):
     """sample_type + the ",purity{S}" / ",purity{S}w{r}" part the drivers' purity_steps / purity_weight keywords stand for
     (DALLE._purity_part); purity_steps None: sample_type as it is -- purity_weight is not looked at."""
@@ -276,10 +327,10 @@ class Diffsound:
         return {"condition_token": text} if text.dtype == torch.long else {"condition_embed_token": text}
 
     def _inpaint_tokens(self, tokens, keep, text, keep_mode, truncation_rate, caption_ids, seed, guidance_scale=None,
-                        negative_text=None, purity_steps=None, purity_weight=0.0):
+                        negative_text=None, purity_steps=None, purity_weight=0.0, tracks=None):
         """DALLE.inpaint_content at this call's truncation rate (the facade installs a rate once and keeps it: set and
         restored around the call, like generate_sample_from_audio does)."""
-        batch = dict(self._caption_batch(text), content_token=tokens)
+        batch = dict({} if tracks is not None and text is None else self._caption_batch(text), content_token=tokens)
         if caption_ids is not None:
             batch["caption_ids"] = caption_ids
         if seed is not None:
@@ -291,6 +342,7 @@ class Diffsound:
         tr.truncation_r, tr.truncation_k, model.truncation_forward = float(truncation_rate), None, True
         try:
             out = model.inpaint_content(batch=batch, keep_mask=keep, keep_mode=keep_mode, guidance_scale=guidance_scale,
+                                        **({} if tracks is None else {"tracks": tracks}),
                                         sample_type=purity_sample_type("top" + str(truncation_rate) + "r", purity_steps,
                                                                        purity_weight))
         finally:
@@ -309,6 +361,7 @@ class Diffsound:
         caption_ids / seed / sample_rate / guidance_scale / negative_text / purity_steps / purity_weight as in
         generate_sample_with_condition (a purity chain holds positions clean: keep_mode "clamp" only).  Returns
         (mel01, wave or None, tokens) and writes the files generate_sample_from_audio writes.
+        inpaint_scene regenerates the spans under a scene (caption tracks) instead of one caption.
 
         What is kept is the TOKENS: exact.  The returned audio is the codec's and the vocoder's rendering everywhere -- the
         held region is not the input's samples (the decoder's lowest level attends over all 265 positions), and the original
@@ -318,6 +371,23 @@ class Diffsound:
         keep = spans_to_keep_mask(spans, known.shape[0], known.device)
         tokens = self._inpaint_tokens(known, keep, text, keep_mode, truncation_rate, caption_ids, seed, guidance_scale,
                                       negative_text, purity_steps, purity_weight)
+        return self._render(tokens, content["content_quant"].shape, save_root, sample_rate)
+
+    @torch.no_grad()
+    def inpaint_scene(self, audio, tracks, spans, scale=3.0, keep_mode="clamp", truncation_rate=0.85, save_root=None,
+                      audio_rate=None, caption_ids=None, seed=None, sample_rate=None, negative_text=None):
+        """inpaint_audio under a scene instead of one caption: the spans are regenerated under `tracks` -- caption tracks as
+        in generate_scene, [(text, t0, t1[, scale]), ...] in the clip's own seconds, one scene or one per clip; a track that
+        names no scale gets `scale` -- and the rest of the recording is kept, as tokens, exactly.  The other arguments and
+        the return are inpaint_audio's.  (A method of its own: inpaint_audio's keywords are what they were.)"""
+        content = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})
+        known = content["content_token"]
+        keep = spans_to_keep_mask(spans, known.shape[0], known.device)
+        is_scenes = len(tracks) > 0 and isinstance(tracks[0], (list, tuple)) and len(tracks[0]) > 0 \
+            and isinstance(tracks[0][0], (list, tuple))
+        trk = self._scene(tracks, GRID_COLS, None if is_scenes else known.shape[0], scale)
+        tokens = self._inpaint_tokens(known, keep, None, keep_mode, truncation_rate, caption_ids, seed, None, negative_text,
+                                      tracks=trk)
         return self._render(tokens, content["content_quant"].shape, save_root, sample_rate)
 
     @torch.no_grad()
@@ -336,20 +406,23 @@ class Diffsound:
         return self._render(tokens, content["content_quant"].shape, save_root, sample_rate)
 
     def _long_tokens(self, text, windows, overlap_cols, keep_mode, truncation_rate, caption_ids, seed,
-                     guidance_scale, negative_text, start_token=None, purity_steps=None, purity_weight=0.0):
+                     guidance_scale, negative_text, start_token=None, purity_steps=None, purity_weight=0.0, tracks=None,
+                     sample_type=None):
         """DALLE.generate_long_content under this call's caption / noise keywords (the truncation rate is the call's: the
         facade saves and restores the model's own)."""
-        batch = dict(self._caption_batch(text))
+        batch = {} if tracks is not None and text is None else dict(self._caption_batch(text))
         if caption_ids is not None:
             batch["caption_ids"] = caption_ids
         if seed is not None:
             batch["seed"] = seed
         if negative_text is not None:
             batch["negative_text"] = negative_text
+        if sample_type is None:
+            sample_type = purity_sample_type("top" + str(truncation_rate) + "r", purity_steps, purity_weight)
+        kw = {} if tracks is None else {"tracks": tracks}       # (without tracks: the call as it always was)
         return self.model.generate_long_content(batch=batch, windows=windows, overlap_cols=overlap_cols, keep_mode=keep_mode,
-                                                sample_type=purity_sample_type("top" + str(truncation_rate) + "r", purity_steps,
-                                                                               purity_weight),
-                                                guidance_scale=guidance_scale, start_token=start_token)
+                                                sample_type=sample_type, guidance_scale=guidance_scale, start_token=start_token,
+                                                **kw)
 
     VOCODER_CHUNK_FRAMES = 64 * 848       # mel frames per vocoder call of a long clip: the largest call the benchmarks run
 
@@ -398,6 +471,46 @@ class Diffsound:
         windows, n, _, samples = long_plan(seconds, overlap_seconds)
         out = self._long_tokens(text, windows, n, keep_mode, truncation_rate, caption_ids, seed, guidance_scale, negative_text,
                                 purity_steps=purity_steps, purity_weight=purity_weight)
+        return self._render_long(out, windows, n, samples, save_root, sample_rate)
+
+    SCENE_SCALE = 3.0     # generate_scene's default track weight: the scale the guidance tests run at; a design choice
+
+    @staticmethod
+    def _scene(tracks, total_cols=GRID_COLS, batch=None, scale=None):
+        """tracks of generate_scene / inpaint_audio -> the dict DALLE's `tracks` keyword takes (None stays None); a track that
+        names no scale gets `scale` (default SCENE_SCALE)"""
+        if tracks is None:
+            return None
+        scale = Diffsound.SCENE_SCALE if scale is None else float(scale)
+        fill = lambda t: tuple(t) + (scale,) if isinstance(t, (list, tuple)) and len(t) == 3 and isinstance(t[0], str) else t
+        tracks = [fill(t) if not (isinstance(t, (list, tuple)) and t and isinstance(t[0], (list, tuple))) else [fill(q) for q in t]
+                  for t in tracks]
+        text, weight = track_weights(tracks, total_cols, batch)
+        return {"text": text, "weight": weight}
+
+    @torch.no_grad()
+    def generate_scene(self, tracks, seconds=None, scale=3.0, overlap_seconds=2.4, truncation_rate=0.85, keep_mode="clamp",
+                       fast=False, caption_ids=None, seed=None, negative_text=None, sample_rate=None, save_root=None):
+        """A scene instead of one caption: tracks = [(text, t0, t1[, scale]), ...] in seconds (track_weights: t1 None = to the
+        end; at most 4 tracks), one scene or a list of B scenes -> what generate_long returns: (mel01, wave or None, tokens
+        i64[B, W, 265]).  Every sampler step evaluates the denoiser under each track's caption and under the null condition
+        (the empty caption, or negative_text) and samples each grid position from
+            log p_null + sum_i w_i(pos) (log p_i - log p_null),   renormalised
+        (csrc/sampler.hip SampleCompose) -- the conjunction of Liu et al. 2022 with weights that vary over the token grid;
+        w_i is the track's scale inside its span, 0 outside, proportional in an edge column.  scale: the default for tracks
+        that name none (3.0: the scale the guidance tests run at -- a design choice, not a measured optimum).  seconds None
+        or at most one grid (217 088 samples): one window; longer: the windows of generate_long (long_plan, overlap_seconds,
+        keep_mode), each under the slice of the weights over its own columns.  fast / caption_ids / seed / sample_rate /
+        save_root as in the other drivers; a scene is repeated by calling again under other caption_ids.
+
+        No trained checkpoint has been available to this project: what scenes SOUND like, and whether event order and
+        placement improve over one caption, is unmeasured."""
+        windows, n, total, samples = long_plan(CLIP_SAMPLES / VOCODER_RATE if seconds is None else seconds, overlap_seconds)
+        is_scenes = len(tracks) > 0 and isinstance(tracks[0], (list, tuple)) and len(tracks[0]) > 0 \
+            and isinstance(tracks[0][0], (list, tuple))
+        trk = self._scene(tracks, total, None if is_scenes else 1, scale)
+        out = self._long_tokens(None, windows, n, keep_mode, truncation_rate, caption_ids, seed, None, negative_text, tracks=trk,
+                                sample_type="top" + str(truncation_rate) + ("r,fast" + str(fast - 1) if fast else "r"))
         return self._render_long(out, windows, n, samples, save_root, sample_rate)
 
     @torch.no_grad()
