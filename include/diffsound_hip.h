@@ -783,6 +783,45 @@ int ds_wave_to_mel(const float* wave, int B, int T, int length, int pad, const f
  * launch.  L / M in lowest terms, both < 2^20; 1024 M / L + 2 W + 2 <= 15360 (M / L up to ~13); n_out == 0 is a no-op. */
 int ds_resample(const float* x, int B, int T, const int32_t* lengths, int L, int M, const float* taps, int W,
                 float* y, int n_out, ds_stream_t stream);
+/* Output levelling (csrc/loudness.hip): gated loudness after ITU-R BS.1770-4, sample peak, mean square and x4 true peak of
+ * a batch of mono rows, the gain a strategy asks for, and the gain applied.  x f32[B][T] (T = row stride), lengths i32[B] on
+ * the device (clamped to 0..T) or NULL (= T); row b is x[b][0 .. len_b), and a sample at or past len_b is never loaded.
+ * S = floor(0.1 fs + 0.5) samples per segment.  kw f64[26], built in float64 on the host (audio.kweight_coeffs, audio.level_plan):
+ *   kw[0..4] = b0 b1 b2 a1 a2 of the shelf, kw[5..9] = 1 -2 1 a1 a2 of the high-pass, both from the analogue prototypes
+ *       K = tan(pi f0 / fs), a0 = 1 + K/Q + K^2, a1 = 2 (K^2 - 1) / a0, a2 = (1 - K/Q + K^2) / a0,
+ *       shelf b = [Vh + Vb K/Q + K^2, 2 (K^2 - Vh), Vh - Vb K/Q + K^2] / a0,  Vh = 10^(G/20), Vb = Vh^0.4996667741545416,
+ *       shelf f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196; high-pass f0 = 38.13547087602444,
+ *       Q = 0.5003270373238773;
+ *   kw[10..25] = P = A^S row-major, A the 4x4 state transition of the two biquads in series in transposed direct form II.
+ * All filter state and every sum is float64.  With y the K-weighted row (zero state at sample 0):
+ *   n_seg  = floor(len_b / S),   seg[b][j] = sum of y^2 over samples [j S, (j+1) S) in sample order, 0 for j >= n_seg
+ *   z_j    = (((seg[j] + seg[j+1]) + seg[j+2]) + seg[j+3]) / (4 S),   j = 0 .. n_seg - 4          (400-ms blocks, 75 % overlap)
+ *   A      = { j : z_j > 10^((-70 + 0.691)/10) },   G = { j in A : z_j > 0.1 mean_A z }
+ *   lufs   = -0.691 + 10 log10(mean_G z),   -inf when A is empty (silence, or len_b < 4 S)
+ *   peaks[b] = { max |x|,  max(max |x|, max_n |r[n]|) },  r = the row through the ds_resample sum with L = 4, M = 1 and
+ *              taps f32[4][69] = audio.resample_taps(fs, 4 fs) (W = 34; fp32 fma over j ascending; n < 4 len_b); r is never stored
+ *   mean_sq  = sum x^2 / len_b (0 for an empty row)
+ * Gain of row b, in float64:  DS_LEVEL_PEAK g = 10^(target/20) / max |x|;  DS_LEVEL_RMS g = 10^(target/20) / sqrt(mean_sq);
+ * DS_LEVEL_LOUDNESS g = 10^((target - lufs)/20), the target being target_dev[b] (target_n == B) or target_dev[0] (target_n == 1)
+ * where target_dev (f64 on the device, e.g. the lufs another call wrote) is not NULL;  DS_LEVEL_MEASURE g = 1.  A measure that is
+ * 0 or -inf, or a target that is not finite, gives g = 1.  Then the ceiling c = 10^(ceiling_db/20): if g true_peak > c,
+ * g = c / true_peak -- a static cut, not a limiter.  g is rounded to fp32 once, one step further down where that rounding lifted
+ * g true_peak above c.  counts (may be NULL) i32[B][2] = |A|, |G|.  ds_level_apply: out[b][i] = fl32(gain[b] x[b][i]) for
+ * i < len_b, 0 past it; out may be x; 16-byte accesses where T % 4 == 0 and both pointers are 16-byte aligned.
+ * No entry allocates or synchronises: `scratch` (ds_level_scratch_bytes bytes for the same B, T, S; 8-byte aligned) carries the
+ * segment states and the partial peaks from ds_level_segments and ds_level_true_peak to ds_level_gain, which runs after both on
+ * the same stream.  n_seg_max >= floor(T / S) is the row stride of seg.  A row's every result is bit-identical whatever the batch,
+ * its position in it, T and the launch.  Bad arguments return -1 and launch nothing. */
+enum { DS_LEVEL_MEASURE = 0, DS_LEVEL_PEAK = 1, DS_LEVEL_RMS = 2, DS_LEVEL_LOUDNESS = 3 };
+int64_t ds_level_scratch_bytes(int B, int T, int S);
+int ds_level_segments(const float* x, int B, int T, const int32_t* lengths, int S, const double* kw, double* seg,
+                      int n_seg_max, void* scratch, int64_t scratch_bytes, ds_stream_t stream);
+int ds_level_true_peak(const float* x, int B, int T, const int32_t* lengths, int S, const float* taps, void* scratch,
+                       int64_t scratch_bytes, ds_stream_t stream);
+int ds_level_gain(const double* seg, int n_seg_max, int B, int T, const int32_t* lengths, int S, int strategy, double target,
+                  const double* target_dev, int target_n, double ceiling_db, const void* scratch, int64_t scratch_bytes,
+                  double* lufs, float* peaks, double* mean_sq, int32_t* counts, float* gain, ds_stream_t stream);
+int ds_level_apply(const float* x, const float* gain, float* out, int B, int T, const int32_t* lengths, ds_stream_t stream);
 
 #ifdef __cplusplus
 }

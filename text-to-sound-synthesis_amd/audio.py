@@ -1,7 +1,8 @@
 """Host side of the audio front end: the mel filterbank, the FFT tables of `ds_wave_to_mel`, a RIFF reader, and the thin
 launcher of the kernel (csrc/stft_mel.hip) that `modeling.vocoder.Audio2Mel` and `modeling.melspec.WaveToMel` share; the
 polyphase table of `ds_resample` (csrc/resample.hip) and its launcher: audio at any integer sample rate in and out; the
-cross-fade table of `ds_mel_stitch` (csrc/misc.hip) and its launcher: window mels joined into one long mel.
+cross-fade table of `ds_mel_stitch` (csrc/misc.hip) and its launcher: window mels joined into one long mel; the K-weighting
+coefficients and segment plan of the `ds_level_*` entries (csrc/loudness.hip) and their launchers: loudness, true peak, gain.
 
 The reference extracts mels with librosa on the host (Diffsound/vocoder/mel2wav/extract_mel_spectrogram.py:15-38,141-187)
 and reads audio with `librosa.load(path, sr=None)` (:167); its data preparation resamples with `librosa.load(path, sr=22050)`
@@ -194,6 +195,189 @@ def resample(wave, src, dst, *, lengths=None, n_out=None):
     _lib.check(_lib.lib().ds_resample(_lib.ptr(wave), B, T, _lib.ptr(lengths), L, M, _lib.ptr(taps), W, _lib.ptr(out),
                                       int(n_out), _lib.stream()))
     return out
+
+
+# ---- output levelling: BS.1770 loudness, true peak and gain (csrc/loudness.hip) -------------------------------------------------
+KW_SHELF = (1681.974450955533, 3.999843853973347, 0.7071752369554196)      # f0 Hz, gain dB, Q of the analogue prototype
+KW_SHELF_VB_EXP = 0.4996667741545416
+KW_HIGHPASS = (38.13547087602444, 0.5003270373238773)                      # f0 Hz, Q
+LEVEL_STRATEGIES = {"peak": -1.0, "rms": -20.0, "loudness": -23.0, "match": None}     # name -> default target (dBFS / LUFS)
+
+
+def _level_rate(rate):
+    if isinstance(rate, bool) or not isinstance(rate, (int, np.integer)) or rate < 1:
+        raise ValueError("the sample rate must be a positive integer, got %r" % (rate,))
+    return int(rate)
+
+
+def kweight_coeffs(rate):
+    """The K-weighting of ITU-R BS.1770 at any integer rate, from the analogue prototypes, in float64:
+    {"shelf": (b f64[3], a f64[3]), "highpass": (b f64[3], a f64[3])} with a[0] = 1 (include/diffsound_hip.h: ds_level_segments).
+    At 48 000 Hz these are the seven table values of BS.1770-4."""
+    fs = float(_level_rate(rate))
+    f0, G, Q = KW_SHELF
+    K = math.tan(math.pi * f0 / fs)
+    Vh = 10.0 ** (G / 20.0)
+    Vb = Vh ** KW_SHELF_VB_EXP
+    a0 = 1.0 + K / Q + K * K
+    shelf = (np.array([(Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0]),
+             np.array([1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0]))
+    f0, Q = KW_HIGHPASS
+    K = math.tan(math.pi * f0 / fs)
+    a0 = 1.0 + K / Q + K * K
+    highpass = (np.array([1.0, -2.0, 1.0]), np.array([1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0]))
+    return {"shelf": shelf, "highpass": highpass}
+
+
+def level_plan(rate):
+    """{"S": samples per 100-ms segment = floor(0.1 rate + 0.5), "block": 4 S (a 400-ms gating block, hop S), "transition":
+    f64[4, 4] = A^S, A the state transition of the two biquads in series in transposed direct form II on (s1, s2, t1, t2) --
+    what carries a row's filter state from one segment's start to the next (csrc/loudness.hip)."""
+    rate = _level_rate(rate)
+    c = kweight_coeffs(rate)
+    (_, a), (_, d) = c["shelf"], c["highpass"]
+    S = int(math.floor(0.1 * rate + 0.5))
+    if S < 1:
+        raise ValueError("the sample rate %d is too low for a 100-ms segment" % rate)
+    A = np.array([[-a[1], 1.0, 0.0, 0.0],
+                  [-a[2], 0.0, 0.0, 0.0],
+                  [-2.0 - d[1], 0.0, -d[1], 1.0],
+                  [1.0 - d[2], 0.0, -d[2], 0.0]])
+    return {"S": S, "block": 4 * S, "transition": np.linalg.matrix_power(A, S)}
+
+
+_LEVEL_TABLES = {}
+
+
+def _level_tables(rate, device):
+    """(S, kw f64[26] on the device, x4 taps f32[4, 69] on the device)"""
+    key = (rate, device.type, device.index)
+    if key not in _LEVEL_TABLES:
+        c, plan = kweight_coeffs(rate), level_plan(rate)
+        kw = np.concatenate([c["shelf"][0], c["shelf"][1][1:], c["highpass"][0], c["highpass"][1][1:],
+                             plan["transition"].reshape(-1)])
+        taps, L, M, W = resample_taps(1, 4)                    # the table depends on the ratio alone
+        assert (L, M, W) == (4, 1, 34) and kw.shape == (26,)
+        _LEVEL_TABLES[key] = (plan["S"], torch.from_numpy(kw).to(device), taps.contiguous().to(device))
+    return _LEVEL_TABLES[key]
+
+
+def _level_rows(wave, lengths):
+    if not torch.is_tensor(wave) or wave.dim() != 2:
+        raise ValueError("wave must be a tensor f32[B, T]")
+    if not wave.is_cuda:
+        raise _lib.DiffsoundHipError("wave is not on a GPU: the HIP path has no CPU fallback")
+    wave = wave.float().contiguous()
+    host_lens = None
+    if lengths is None:
+        host_lens = [wave.shape[1]] * wave.shape[0]
+    elif not (torch.is_tensor(lengths) and lengths.is_cuda):
+        host_lens = [int(n) for n in torch.as_tensor(lengths).reshape(-1).tolist()]
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths, dtype=torch.int32).to(wave.device).contiguous()
+        if lengths.shape != (wave.shape[0],):
+            raise ValueError("lengths must hold one count per row")
+    return wave, lengths, host_lens
+
+
+def _level_run(wave, rate, lengths, strategy, target, target_dev, ceiling_db, counts=False):
+    """the three measuring launches and the gain launch on rows already checked -> dict of device tensors (+ 'gain')"""
+    B, T = wave.shape
+    dev = wave.device
+    S, kw, taps = _level_tables(rate, dev)
+    n_seg_max = T // S
+    L = _lib.lib()
+    nbytes = int(L.ds_level_scratch_bytes(B, T, S))
+    scratch = torch.empty(nbytes // 8 + 1, device=dev, dtype=torch.float64)
+    seg = torch.empty(B, max(n_seg_max, 1), device=dev, dtype=torch.float64)
+    lufs = torch.empty(B, device=dev, dtype=torch.float64)
+    mean_sq = torch.empty(B, device=dev, dtype=torch.float64)
+    peaks = torch.empty(B, 2, device=dev, dtype=torch.float32)
+    gain = torch.empty(B, device=dev, dtype=torch.float32)
+    cnt = torch.empty(B, 2, device=dev, dtype=torch.int32) if counts else None
+    st = _lib.stream()
+    _lib.check(L.ds_level_segments(_lib.ptr(wave), B, T, _lib.ptr(lengths), S, _lib.ptr(kw), _lib.ptr(seg), max(n_seg_max, 1),
+                                   _lib.ptr(scratch), nbytes, st))
+    _lib.check(L.ds_level_true_peak(_lib.ptr(wave), B, T, _lib.ptr(lengths), S, _lib.ptr(taps), _lib.ptr(scratch), nbytes, st))
+    _lib.check(L.ds_level_gain(_lib.ptr(seg), max(n_seg_max, 1), B, T, _lib.ptr(lengths), S, int(strategy), float(target),
+                               _lib.ptr(target_dev), 0 if target_dev is None else int(target_dev.numel()), float(ceiling_db),
+                               _lib.ptr(scratch), nbytes, _lib.ptr(lufs), _lib.ptr(peaks), _lib.ptr(mean_sq), _lib.ptr(cnt),
+                               _lib.ptr(gain), st))
+    out = {"lufs": lufs, "sample_peak": peaks[:, 0], "true_peak": peaks[:, 1], "rms": mean_sq.sqrt(), "gain": gain,
+           "seg": seg[:, :n_seg_max]}
+    if counts:
+        out["gate_counts"] = cnt
+    return out
+
+
+def measure_level(wave, rate, lengths=None, segments=False):
+    """The level of wave f32[B, T] (device) at `rate` Hz, row b being wave[b, :lengths[b]] (lengths: i32[B] on the device or a
+    list; None = T) -> a dict of device tensors: 'lufs' f64[B] (integrated loudness after BS.1770-4, -inf for silence and
+    for rows shorter than four segments), 'sample_peak' f32[B], 'true_peak' f32[B] (x4 through the resampler's own filter,
+    never below the sample peak) and 'rms' f64[B].  segments=True adds 'seg' f64[B, T // S], the K-weighted energy of every
+    100-ms segment, and 'gate_counts' i32[B, 2], the blocks that pass the absolute gate and both gates.  Four launches, no
+    host synchronisation; the formulas are in include/diffsound_hip.h (ds_level_segments).  A host tensor raises."""
+    rate = _level_rate(rate)
+    wave, lengths, _ = _level_rows(wave, lengths)
+    if wave.shape[0] == 0:
+        raise ValueError("wave holds no rows")
+    r = _level_run(wave, rate, lengths, _lib.LEVEL_MEASURE, 0.0, None, 0.0, counts=segments)
+    keys = ("lufs", "sample_peak", "true_peak", "rms") + (("seg", "gate_counts") if segments else ())
+    return {k: r[k] for k in keys}
+
+
+def level(wave, rate, strategy, target=None, ceiling_db=-1.0, lengths=None, reference=None):
+    """Bring wave f32[B, T] (device, `rate` Hz; lengths as in measure_level) to a level -> (out f32[B, T], gain f32[B]):
+    one gain per row, out = gain x in fp32, exact zeros past a row's length.  strategy "peak": the sample peak to `target`
+    dBFS (default -1); "rms": the root mean square to `target` dBFS (-20); "loudness": the integrated loudness to `target`
+    LUFS (-23); "match": to the integrated loudness of `reference` = (wave, rate, lengths) -- one row, or one per row of
+    `wave` --, measured by the same kernels (or an f64 device tensor of 1 or B loudness values such a measurement gave).
+    Then the ceiling: a gain that would lift the x4 true peak above ceiling_db dBFS is cut to reach exactly that -- a static
+    cut of the whole row, its shape untouched.  A silent row, and under "loudness" / "match" a row shorter than 0.4 s, has
+    nothing to scale by and keeps gain 1; where the lengths are known on the host such a short row raises ValueError instead.
+    Everything stays on the device and nothing synchronises."""
+    rate = _level_rate(rate)
+    if strategy not in LEVEL_STRATEGIES:
+        raise ValueError("strategy must be one of %s, got %r" % (", ".join(sorted(LEVEL_STRATEGIES)), strategy))
+    if (strategy == "match") != (reference is not None):
+        raise ValueError('reference goes with strategy "match" and "match" needs one')
+    if strategy == "match" and target is not None:
+        raise ValueError('"match" takes its target from the reference')
+    target = LEVEL_STRATEGIES[strategy] if target is None else float(target)
+    ceiling_db = float(ceiling_db)
+    if strategy != "match" and not math.isfinite(target) or not math.isfinite(ceiling_db):
+        raise ValueError("target and ceiling_db must be finite")
+    wave, lengths, host_lens = _level_rows(wave, lengths)
+    if wave.shape[0] == 0:
+        raise ValueError("wave holds no rows")
+    block = level_plan(rate)["block"]
+    if strategy in ("loudness", "match") and host_lens is not None and min(host_lens) < block:
+        raise ValueError("loudness needs at least one 400-ms block (%d samples at %d Hz); a row has %d"
+                         % (block, rate, min(host_lens)))
+    target_dev = None
+    if strategy == "match":
+        if torch.is_tensor(reference):
+            target_dev = reference
+            if not target_dev.is_cuda:
+                raise _lib.DiffsoundHipError("the reference loudness is not on a GPU: the HIP path has no CPU fallback")
+            target_dev = target_dev.to(torch.float64).reshape(-1).contiguous()
+        else:
+            ref = tuple(reference)
+            if len(ref) not in (2, 3):
+                raise ValueError("reference is (wave, rate) or (wave, rate, lengths)")
+            rwave, rlens, rhost = _level_rows(ref[0], ref[2] if len(ref) == 3 else None)
+            rrate = _level_rate(ref[1])
+            if rhost is not None and rwave.shape[0] and min(rhost) < level_plan(rrate)["block"]:
+                raise ValueError("the reference is shorter than one 400-ms block")
+            target_dev = measure_level(rwave, rrate, rlens)["lufs"]
+        if target_dev.numel() not in (1, wave.shape[0]):
+            raise ValueError("the reference holds %d rows for %d clips" % (target_dev.numel(), wave.shape[0]))
+    code = {"peak": _lib.LEVEL_PEAK, "rms": _lib.LEVEL_RMS, "loudness": _lib.LEVEL_LOUDNESS, "match": _lib.LEVEL_LOUDNESS}[strategy]
+    r = _level_run(wave, rate, lengths, code, 0.0 if target is None else target, target_dev, ceiling_db)
+    out = torch.empty_like(wave)
+    _lib.check(_lib.lib().ds_level_apply(_lib.ptr(wave), _lib.ptr(r["gain"]), _lib.ptr(out), wave.shape[0], wave.shape[1],
+                                         _lib.ptr(lengths), _lib.stream()))
+    return out, r["gain"]
 
 
 def fade_table(V):

@@ -7,7 +7,10 @@ vocoder is Generator(n_mel_channels, ngf, n_residual_layers) as `<ckpt_vocoder>/
 tensor-returning form of the reference's file-writing drivers: mel and waveform stay on the GPU and
 the vocoder runs on the whole batch.
 """
+import functools
+import inspect
 import os
+import threading
 
 import torch
 
@@ -206,6 +209,82 @@ def purity_sample_type(sample_type, purity_steps, purity_weight=0.0):
     return "%s,purity%d%s" % (sample_type, int(purity_steps), "" if w == 0.0 else "w%r" % w)
 
 
+def level_spec(level, takes_recording):
+    """The drivers' `level` keyword -> None or {"strategy", "target", "ceiling_db"}: a strategy name of audio.level ("peak",
+    "rms", "loudness", "match") or a dict {strategy[, target][, ceiling_db]}.  "match" -- the result takes the loudness of the
+    recording the driver was given -- only where there is one (takes_recording).  Anything else raises ValueError."""
+    from . import audio
+    if level is None:
+        return None
+    spec = {"strategy": level} if isinstance(level, str) else level
+    if not isinstance(spec, dict) or "strategy" not in spec or set(spec) - {"strategy", "target", "ceiling_db"}:
+        raise ValueError("level is a strategy name or a dict {strategy, target, ceiling_db}, got %r" % (level,))
+    strategy, target = spec["strategy"], spec.get("target")
+    if strategy not in audio.LEVEL_STRATEGIES:
+        raise ValueError("level: strategy must be one of %s, got %r" % (", ".join(sorted(audio.LEVEL_STRATEGIES)), strategy))
+    if strategy == "match" and not takes_recording:
+        raise ValueError('level="match" needs a recording to match: this driver takes none')
+    if strategy == "match" and target is not None:
+        raise ValueError('level="match" takes its target from the recording')
+    return {"strategy": strategy, "target": None if target is None else float(target),
+            "ceiling_db": float(spec.get("ceiling_db", -1.0))}
+
+
+def recording_loudness(item, rate=None, device="cuda"):
+    """Integrated loudness f64[B] (device) of the recordings a driver was given (`audio` / `audio_rate` as in
+    melspec.mel_image_from_audio), each measured at its own rate and over its own length by audio.measure_level."""
+    from . import audio
+    from .modeling.melspec import SAMPLE_RATE, _clip_rates
+    if torch.is_tensor(item) and item.is_cuda:
+        wave = item[None] if item.dim() == 1 else item
+        rates = [SAMPLE_RATE if r is None else r for r in _clip_rates(rate, wave.shape[0])]
+        if len(set(rates)) == 1:
+            return audio.measure_level(wave, rates[0])["lufs"]
+        return torch.cat([audio.measure_level(wave[i:i + 1], r)["lufs"] for i, r in enumerate(rates)])
+    clips = [item] if isinstance(item, (str, os.PathLike)) or (torch.is_tensor(item) and item.dim() == 1) else list(item)
+    rates = _clip_rates(rate, len(clips))
+    out = []
+    for i, clip in enumerate(clips):
+        if isinstance(clip, (str, os.PathLike)):
+            x, sr = audio.read_wav(clip)
+        else:
+            x, sr = torch.as_tensor(clip).float().reshape(-1), SAMPLE_RATE if rates[i] is None else rates[i]
+        out.append(audio.measure_level(x[None].to(device), int(sr))["lufs"])
+    return torch.cat(out)
+
+
+_LEVEL = threading.local()        # the (spec, recording) of the driver call this thread is inside, read by Diffsound._finish
+
+
+def _levelled(takes_recording):
+    """Gives a driver the keyword `level=None` (level_spec; keyword-only, behind everything the driver declares).  It is a
+    decorator because levelling is one step of the tail the drivers share (Diffsound._finish), not of any driver: the call's
+    checked spec -- and, for "match", the `audio` / `audio_rate` the driver was given -- is held for the duration of the call
+    and _finish applies it; a driver's own parameters stay what they were.  level=None calls the driver as it is."""
+    def deco(fn):
+        sig = inspect.signature(fn)
+
+        @functools.wraps(fn)
+        def driver(self, *args, level=None, **kwargs):
+            spec = level_spec(level, takes_recording)
+            if spec is None:
+                return fn(self, *args, **kwargs)
+            recording = None
+            if spec["strategy"] == "match":
+                given = sig.bind(self, *args, **kwargs).arguments
+                recording = (given["audio"], given.get("audio_rate"))
+            outer = getattr(_LEVEL, "request", None)
+            _LEVEL.request = (spec, recording)
+            try:
+                return fn(self, *args, **kwargs)
+            finally:
+                _LEVEL.request = outer
+        driver.__signature__ = sig.replace(parameters=list(sig.parameters.values())
+                                           + [inspect.Parameter("level", inspect.Parameter.KEYWORD_ONLY, default=None)])
+        return driver
+    return deco
+
+
 class Diffsound:
     def __init__(self, config=None, path=None, ckpt_vocoder=None, device="cuda", random_vocoder=False):
         """ckpt_vocoder falsy: `self.vocoder = None` and the drivers write `.npy` only, as the reference does (:53-56).
@@ -234,6 +313,7 @@ class Diffsound:
             for p in self.vocoder.parameters():
                 p.requires_grad = False
 
+    @_levelled(False)
     @torch.no_grad()
     def generate_sample_with_condition(self, cond, truncation_rate=0.85, replicate=1, fast=False, caption_ids=None,
                                        seed=None, sample_rate=None, guidance_scale=None, negative_text=None, purity_steps=None,
@@ -250,7 +330,12 @@ class Diffsound:
         caption, or one per caption); None or 1: unguided.
         purity_steps = S: an S-step purity-prior chain instead of the reference's 100-step loop (DiffusionTransformer.
         sample_purity: 1 <= S <= 265 forwards, confident positions first, no [MASK] left at any S), purity_weight its
-        sharpening weight; None: today's path, untouched.  Not together with fast.  Its effect on audio quality is unmeasured."""
+        sharpening weight; None: today's path, untouched.  Not together with fast.  Its effect on audio quality is unmeasured.
+        level= (keyword-only, on this and every driver that returns or writes a waveform; _levelled, level_spec): bring every
+        clip to a level on the device, at the output rate -- "peak" (-1 dBFS), "rms" (-20 dBFS), "loudness" (-23 LUFS, BS.1770-4)
+        or a dict {strategy, target, ceiling_db}, under a true-peak ceiling of -1 dBFS (audio.level); the drivers that take a
+        recording also accept "match": the recording's own loudness.  None: the vocoder's own level, no launch.  Mel and tokens
+        are never affected; generate_best_of levels the winners only."""
         if isinstance(cond, (list, tuple, str)):
             batch = {"text": [cond] if isinstance(cond, str) else list(cond)}
         elif cond.dtype == torch.long:
@@ -270,7 +355,7 @@ class Diffsound:
                                               purity_steps, purity_weight))
         mel = out["content"]                                   # [B,1,80,848] in ~[-1,1]
         wave = None if self.vocoder is None else self.vocoder(mel[:, 0], scale=0.5, shift=0.5)   # spec = (x+1)/2, :182
-        return (mel[:, 0] + 1) / 2, self._at_rate(wave, sample_rate), out["content_token"]
+        return (mel[:, 0] + 1) / 2, self._finish(wave, sample_rate), out["content_token"]
 
     @staticmethod
     def _at_rate(wave, sample_rate):
@@ -280,6 +365,24 @@ class Diffsound:
         from . import audio
         return audio.resample(wave[:, 0], VOCODER_RATE, sample_rate)[:, None]
 
+    @staticmethod
+    def _finish(wave, sample_rate):
+        """The tail every driver shares: the vocoder's f32[B,1,T] -> at `sample_rate` (_at_rate) -> brought to the level the
+        driver call asked for (`level=`, _levelled), at that rate, on the device (audio.level).  No `level`: no launch, the
+        waveform as it is."""
+        wave = Diffsound._at_rate(wave, sample_rate)
+        request = getattr(_LEVEL, "request", None)
+        if wave is None or request is None:
+            return wave
+        from . import audio
+        spec, recording = request
+        rate = VOCODER_RATE if sample_rate is None else int(sample_rate)
+        ref = recording_loudness(recording[0], recording[1], wave.device) if spec["strategy"] == "match" else None
+        out, _ = audio.level(wave[:, 0], rate, spec["strategy"], target=spec["target"], ceiling_db=spec["ceiling_db"],
+                             reference=ref)
+        return out[:, None]
+
+    @_levelled(True)
     @torch.no_grad()
     def generate_sample_from_audio(self, audio, text, filter_ratio=0.5, truncation_rate=0.85, save_root=None, audio_rate=None):
         """Re-sample given recordings under new captions: audio (f32[B, T] on the device, or a list of `.wav` paths / host
@@ -303,12 +406,12 @@ class Diffsound:
         return self._render(out["content_token"], content["content_quant"].shape, save_root)
 
     def _render(self, tokens, zshape, save_root=None, sample_rate=None):
-        """tokens -> decode -> vocoder (-> sample_rate): the tail the audio-in drivers share.  Returns (mel01, wave or None,
+        """tokens -> decode -> vocoder (-> sample_rate -> level: _finish): the tail the audio-in drivers share.  Returns (mel01, wave or None,
         tokens); with save_root also writes `{i:06d}.npy` and, with a vocoder, `{i:06d}.wav`."""
         import numpy as np
         mel = self.model.decode_to_img(tokens, zshape)
         wave = None if self.vocoder is None else self.vocoder(mel[:, 0], scale=0.5, shift=0.5)
-        wave = self._at_rate(wave, sample_rate)
+        wave = self._finish(wave, sample_rate)
         mel01 = (mel[:, 0] + 1) / 2
         if save_root is not None:
             os.makedirs(save_root, exist_ok=True)
@@ -349,6 +452,7 @@ class Diffsound:
             tr.truncation_r, tr.truncation_k, tr.repeat_rate, model.truncation_forward = saved
         return out["content_token"]
 
+    @_levelled(True)
     @torch.no_grad()
     def inpaint_audio(self, audio, text, spans, keep_mode="clamp", truncation_rate=0.85, save_root=None, audio_rate=None,
                       caption_ids=None, seed=None, sample_rate=None, guidance_scale=None, negative_text=None, purity_steps=None,
@@ -365,7 +469,8 @@ class Diffsound:
 
         What is kept is the TOKENS: exact.  The returned audio is the codec's and the vocoder's rendering everywhere -- the
         held region is not the input's samples (the decoder's lowest level attends over all 265 positions), and the original
-        mel or audio is not pasted back."""
+        mel or audio is not pasted back.  level= as in generate_sample_with_condition; "match": the result is brought to the
+        integrated loudness of the recording, measured at the recording's own rate and length."""
         content = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})
         known = content["content_token"]
         keep = spans_to_keep_mask(spans, known.shape[0], known.device)
@@ -373,6 +478,7 @@ class Diffsound:
                                       negative_text, purity_steps, purity_weight)
         return self._render(tokens, content["content_quant"].shape, save_root, sample_rate)
 
+    @_levelled(True)
     @torch.no_grad()
     def inpaint_scene(self, audio, tracks, spans, scale=3.0, keep_mode="clamp", truncation_rate=0.85, save_root=None,
                       audio_rate=None, caption_ids=None, seed=None, sample_rate=None, negative_text=None):
@@ -390,6 +496,7 @@ class Diffsound:
                                       tracks=trk)
         return self._render(tokens, content["content_quant"].shape, save_root, sample_rate)
 
+    @_levelled(True)
     @torch.no_grad()
     def continue_audio(self, audio, text, keep_seconds, keep_mode="clamp", truncation_rate=0.85, save_root=None,
                        audio_rate=None, caption_ids=None, seed=None, sample_rate=None, guidance_scale=None, negative_text=None,
@@ -428,7 +535,7 @@ class Diffsound:
 
     def _render_long(self, out, windows, overlap_cols, samples, save_root, sample_rate):
         """window mels -> ds_mel_stitch (codec domain) -> ONE vocoder pass per clip over its whole stitched mel -> both cut to
-        `samples` (the vocoder's reflection at the far end lies past the cut) -> sample_rate, files.  Clips go through the
+        `samples` (the vocoder's reflection at the far end lies past the cut) -> sample_rate -> level (_finish), files.  Clips go through the
         vocoder in batch chunks of at most VOCODER_CHUNK_FRAMES mel frames; a clip is never split."""
         import numpy as np
         from . import audio
@@ -439,7 +546,7 @@ class Diffsound:
         if self.vocoder is not None:
             step = max(1, self.VOCODER_CHUNK_FRAMES // mel.shape[2])
             wave = torch.cat([self.vocoder(mel[i:i + step], scale=0.5, shift=0.5) for i in range(0, B, step)], 0)
-            wave = self._at_rate(wave[:, :, :samples].contiguous(), sample_rate)
+            wave = self._finish(wave[:, :, :samples].contiguous(), sample_rate)
         mel01 = ((mel + 1) / 2)[:, :, :-(-samples // 256)].contiguous()
         if save_root is not None:
             os.makedirs(save_root, exist_ok=True)
@@ -451,6 +558,7 @@ class Diffsound:
                     write_wav_pcm24(path + ".wav", w_[i], VOCODER_RATE if sample_rate is None else int(sample_rate))
         return mel01, wave, out["content_token"]
 
+    @_levelled(False)
     @torch.no_grad()
     def generate_long(self, text, seconds, overlap_seconds=2.4, truncation_rate=0.85, keep_mode="clamp", caption_ids=None,
                       seed=None, sample_rate=None, guidance_scale=None, negative_text=None, save_root=None, purity_steps=None,
@@ -488,6 +596,7 @@ class Diffsound:
         text, weight = track_weights(tracks, total_cols, batch)
         return {"text": text, "weight": weight}
 
+    @_levelled(False)
     @torch.no_grad()
     def generate_scene(self, tracks, seconds=None, scale=3.0, overlap_seconds=2.4, truncation_rate=0.85, keep_mode="clamp",
                        fast=False, caption_ids=None, seed=None, negative_text=None, sample_rate=None, save_root=None):
@@ -513,6 +622,7 @@ class Diffsound:
                                 sample_type="top" + str(truncation_rate) + ("r,fast" + str(fast - 1) if fast else "r"))
         return self._render_long(out, windows, n, samples, save_root, sample_rate)
 
+    @_levelled(True)
     @torch.no_grad()
     def extend_audio(self, audio, text, seconds, overlap_seconds=2.4, truncation_rate=0.85, keep_mode="clamp", caption_ids=None,
                      seed=None, sample_rate=None, guidance_scale=None, negative_text=None, save_root=None, audio_rate=None,
@@ -545,6 +655,7 @@ class Diffsound:
             batch["seed"] = seed
         return self.model.score_content(batch, timesteps=timesteps, draws=draws)
 
+    @_levelled(False)
     @torch.no_grad()
     def generate_best_of(self, cond, n, score_timesteps=None, truncation_rate=0.85, fast=False, caption_ids=None, seed=None,
                          sample_rate=None, guidance_scale=None, negative_text=None, purity_steps=None, purity_weight=0.0,
@@ -588,6 +699,7 @@ class Diffsound:
         mel01, wave, winners = self._render(winners, (B, 256, 5, 53), None, sample_rate)
         return mel01, wave, winners, scores
 
+    @_levelled(False)
     @torch.no_grad()
     def inference_generate_sample_with_condition(self, text, truncation_rate, save_root, batch_size, fast=False,
                                                  guidance_scale=None, negative_text=None, purity_steps=None, purity_weight=0.0):
@@ -624,6 +736,7 @@ class Diffsound:
                 caps.setdefault(row["file_name"], []).append(row["caption"])
         return caps
 
+    @_levelled(False)
     @torch.no_grad()
     def generate_sample(self, val_path, truncation_rate, save_root, fast=False, replicate=2, sample_rate=None,
                         guidance_scale=None, purity_steps=None, purity_weight=0.0):
