@@ -1,12 +1,14 @@
 """The synthetic-weight profiles (text_to_sound_synthesis_amd/synth.py): "init" and "trained" stay byte-identical -- the goldens'
 SHA-256 input fingerprints depend on them -- and "trained_conv" changes exactly the codec (content_codec.*) and vocoder
-(model.*) tensors.  CPU only."""
+(model.*) tensors, "trained_clip" exactly the text tower's (transformer.condition_emb.*).  CPU only."""
 import hashlib
+import json
+import os
 
 import pytest
 import torch
 
-from conftest import key_contract
+from conftest import GOLDEN, key_contract
 from text_to_sound_synthesis_amd.synth import synth_state_dict
 
 # SHA-256 over (key, bytes) of every tensor, keys sorted: recorded from the profiles as they were before "trained_conv" existed
@@ -14,6 +16,12 @@ PINNED = {("dalle", "init"): "b478bd0dcae9aab6b549929e5d77f67471aa7189d8b1ac0411
           ("dalle", "trained"): "a11bfd0bfff702f179e9ab88f8de085f52baed71c1b05b4452228ce282ed2955",
           ("generator", "init"): "c3bc803aac43d46933a052b3af0fd3afb8fc42e665b1110ad32b2b47c24ec26e",
           ("encoder", "init"): "facb3e08d30ce66e1799ae3ab658e81ce9dabd4a4c4103360b58fdcebe501972"}
+
+# the same for "trained_conv", recorded before "trained_clip" existed
+PINNED_CONV = {"dalle": "d0a2821298c76c057dd81d2ebe1e22500e8ae72351b9b627694d89980e1c0451",
+               "generator": "0a6947c18f2cd2f83960054cfb9d88d8d9bcaa23f39d610bd3a41508b90d37ab",
+               "encoder": "71135d579aff108711f6a2f434091bb862e8c37bc7c42165725cbd1855c6f66b"}
+CLIP = "transformer.condition_emb."
 
 
 def digest(sd):
@@ -26,6 +34,11 @@ def digest(sd):
 
 def _sd(which, profile):
     return synth_state_dict(key_contract()[which]["params"], 0, profile)
+
+
+def _clip_shapes():
+    with open(os.path.join(GOLDEN, "state_dict_keys_clip.json")) as f:
+        return json.load(f)
 
 
 @pytest.mark.parametrize("which", ["dalle", "generator", "encoder"])
@@ -57,6 +70,46 @@ def test_existing_profiles_are_byte_identical(which, profile):
     assert digest(_sd(which, profile)) == PINNED[(which, profile)]
 
 
+@pytest.mark.parametrize("which", list(PINNED_CONV))
+def test_trained_conv_is_byte_identical(which):
+    assert digest(_sd(which, "trained_conv")) == PINNED_CONV[which]
+
+
+def test_trained_clip_changes_only_clip_keys():
+    shapes = dict(key_contract()["dalle"]["params"], **_clip_shapes())
+    shapes.update(key_contract()["generator"]["params"])
+    shapes.update(key_contract()["encoder"]["params"])
+    a, b = synth_state_dict(shapes, 0, "init"), synth_state_dict(shapes, 0, "trained_clip")
+    assert a.keys() == b.keys()
+    changed = {k for k in a if not torch.equal(a[k], b[k])}
+    assert changed and all(k.startswith(CLIP) for k in changed)
+    leaf = ("ln_1.weight", "ln_2.weight", "ln_final.weight", "token_embedding.weight", "attn.in_proj_weight",
+            "attn.out_proj.weight", "mlp.c_proj.weight")
+    assert changed == {k for k in a if k.startswith(CLIP) and k.endswith(leaf)}
+    for k in changed:
+        assert b[k].shape == a[k].shape and b[k].dtype == a[k].dtype and torch.isfinite(b[k]).all()
+
+
+def test_trained_clip_features():
+    from text_to_sound_synthesis_amd.synth import CLIP_HOT
+    shapes = _clip_shapes()
+    a, b = synth_state_dict(shapes, 0, "init"), synth_state_dict(shapes, 0, "trained_clip")
+    gains = torch.cat([v for k, v in b.items() if k.endswith(("ln_1.weight", "ln_2.weight", "ln_final.weight"))])
+    assert 10 ** -0.5 <= gains.min() < 0.35 and 3.0 < gains.max() <= 10 ** 0.5         # log-uniform over a decade
+    hot = list(CLIP_HOT)
+    cold = [c for c in range(512) if c not in hot]
+    k = CLIP + "token_embedding.weight"
+    assert torch.equal(b[k][:, hot], a[k][:, hot] * 50.0) and torch.equal(b[k][:, cold], a[k][:, cold])
+    for i in (0, 11):
+        blk = CLIP + "transformer.resblocks.%d." % i
+        k = blk + "attn.in_proj_weight"
+        assert torch.equal(b[k][:1024], a[k][:1024] * 4.0) and torch.equal(b[k][1024:], a[k][1024:])
+        for k in (blk + "attn.out_proj.weight", blk + "mlp.c_proj.weight"):
+            assert torch.equal(b[k][hot], a[k][hot] * 8.0) and torch.equal(b[k][cold], a[k][cold])
+
+
 def test_unknown_profile_is_an_error():
     with pytest.raises(ValueError):
         _sd("generator", "trained-conv")
+    with pytest.raises(ValueError):
+        synth_state_dict(_clip_shapes(), 0, "trained-clip")

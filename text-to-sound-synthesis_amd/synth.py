@@ -152,11 +152,43 @@ def _trained_conv_tensor(key, shape, seed):
     return None
 
 
+# ---- "trained-like" statistics for the CLIP text tower (profile="trained_clip") ------------------------------------------
+# The tower runs in fp16 semantics: every op's output is rounded to the fp16 grid.  At init its attention scores stay below 9
+# and its activations are O(1), so that rounding is at its mildest.  This profile starts from the init tensor of each key and
+# gives it what a trained text tower has: LayerNorm gains spread over a decade, three hot residual channels fed by the token
+# table and kept hot by the blocks' output projections, and query / key projections large enough for sharply peaked causal
+# attention (scores in the 30s to 40s on the golden captions).
+CLIP_PREFIX = "transformer.condition_emb."
+CLIP_HOT = (31, 255, 480)                    # residual channels of the 512-wide text tower that run hot
+
+
+def _trained_clip_tensor(key, shape, seed):
+    if not key.startswith(CLIP_PREFIX):
+        return None
+    name = key[len(CLIP_PREFIX):]
+    if name.endswith(("ln_1.weight", "ln_2.weight", "ln_final.weight")):     # log-uniform over 10^-0.5 .. 10^0.5
+        return 10.0 ** (torch.rand(tuple(shape), generator=_gen(seed, "trained_clip:" + key)) - 0.5)
+    if name == "token_embedding.weight":
+        t = synth_tensor(key, shape, seed)
+        t[:, list(CLIP_HOT)] *= 50.0
+        return t
+    if name.endswith("attn.in_proj_weight"):
+        t = synth_tensor(key, shape, seed)
+        t[:2 * shape[1]] *= 4.0                                                # the query and the key rows
+        return t
+    if name.endswith(("attn.out_proj.weight", "mlp.c_proj.weight")):
+        t = synth_tensor(key, shape, seed)
+        t[list(CLIP_HOT)] *= 8.0                                               # the blocks keep writing into the hot channels
+        return t
+    return None
+
+
 def synth_state_dict(shapes, seed=0, profile="init"):
     """shapes: {key: shape}.  Returns {key: tensor}; weight_g follows weight_v.  profile = "trained": the denoiser's
     tensors (keys under transformer.transformer.) get trained-like statistics, see above; profile = "trained_conv": the
-    codec's (content_codec.*) and the vocoder's (model.*) tensors do; everything else as "init"."""
-    if profile not in ("init", "trained", "trained_conv"):
+    codec's (content_codec.*) and the vocoder's (model.*) tensors do; profile = "trained_clip": the text tower's
+    (transformer.condition_emb.*) do; everything else as "init"."""
+    if profile not in ("init", "trained", "trained_conv", "trained_clip"):
         raise ValueError("unknown profile %r" % (profile,))
     out = {}
     factor_g = set()
@@ -169,6 +201,8 @@ def synth_state_dict(shapes, seed=0, profile="init"):
             t = _trained_conv_tensor(k, shp, seed)
             if t is not None and k.endswith("weight_g"):
                 factor_g.add(k)
+        elif profile == "trained_clip":
+            t = _trained_clip_tensor(k, shp, seed)
         out[k] = synth_tensor(k, shp, seed) if t is None else t
     for k in list(out):
         if k.endswith("weight_g"):
