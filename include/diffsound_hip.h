@@ -822,6 +822,35 @@ int ds_level_gain(const double* seg, int n_seg_max, int B, int T, const int32_t*
                   const double* target_dev, int target_n, double ceiling_db, const void* scratch, int64_t scratch_bytes,
                   double* lufs, float* peaks, double* mean_sq, int32_t* counts, float* gain, ds_stream_t stream);
 int ds_level_apply(const float* x, const float* gain, float* out, int B, int T, const int32_t* lengths, ds_stream_t stream);
+/* Pasting a recording back over a rendering of it (csrc/paste.hip): outside the regenerated columns the recording's own values
+ * replace the rendering's, cross-faded inside the regenerated columns, with one gain per clip on the rendering.
+ * ren / out f32[B C][T] (rows of clip b: b C .. b C + C - 1; C = 1 for waveforms, the mel channels for mel images), rec f32[B C][Tr];
+ * off i64[B], rec_len i32[B] (clamped to 0..Tr; NULL = Tr) and keep_cols u8[B][n_cols] on the device.  Position n of a row of
+ * clip b reads the recording at i = n + off[b]:  x = rec[row][i] for 0 <= i < rec_len[b], +0 outside (never loaded).
+ * A column is col_num / col_den positions long (1 <= both < 2^31):  c = min(n col_den div col_num, n_cols - 1) in int64, and
+ *   kept column (keep_cols[b][c] != 0):  out = x, a copy of its 32 bits whatever ren holds;  otherwise, in float64,
+ *   dl = (n col_den - c col_num) / col_den        if c > 0 and column c - 1 is kept, else +inf      (numerators exact in int64)
+ *   dr = ((c + 1) col_num - n col_den) / col_den  if c < n_cols - 1 and column c + 1 is kept, else +inf
+ *   u  = 1 if fade_len == 0 or dl = dr = +inf, else min(1, min(dl, dr) / fade_len)
+ *   u == 0: out = x (a copy);   u == 1: out = fl32(g ren) (a copy of ren where sums == NULL);
+ *   else out = fl32(g ren wr + x wo),   DS_PASTE_EQUAL_POWER: wr = sin(pi u / 2), wo = cos(pi u / 2);   DS_PASTE_LINEAR: wr = u,
+ *   wo = 1 - u.  The fade lies inside the regenerated columns; a clip boundary has none.
+ * g = 1 where sums == NULL; else sums f64[B][2] = { S_o, S_r } (what the sums entry below wrote) and g = sqrt(S_o / S_r) clamped
+ * to [1/4, 4], g = 1 where either sum is 0 or not finite; sums go with DS_PASTE_EQUAL_POWER only.  out may be ren itself, not rec.
+ * Full groups of four positions are stored with 16-byte stores whatever T and the pointers' alignment.
+ * The sums entry (C = 1):  S_o = sum x^2, S_r = sum ren^2 over the positions n < T of kept columns with 0 <= n + off[b] <
+ * rec_len[b], in float64 (the products are exact) over a fixed partition in a fixed order, without atomics: a row's sums have the
+ * same bits whatever the batch, T's padding and the launch.  scratch: ds_paste_scratch_bytes(B, T) bytes, 8-byte aligned.
+ * No entry allocates or synchronises.  A null pointer, T <= 0, n_cols < 1, col_num or col_den < 1, a negative or non-finite
+ * fade_len or an unknown curve return -1 and launch nothing. */
+enum { DS_PASTE_EQUAL_POWER = 0, DS_PASTE_LINEAR = 1 };
+int64_t ds_paste_scratch_bytes(int B, int T);
+int ds_paste_sums(const float* ren, const float* rec, int B, int T, int Tr, const int64_t* off, const int32_t* rec_len,
+                  const uint8_t* keep_cols, int n_cols, int64_t col_num, int64_t col_den, void* scratch, int64_t scratch_bytes,
+                  double* sums, ds_stream_t stream);
+int ds_paste(const float* ren, const float* rec, float* out, int B, int C, int T, int Tr, const int64_t* off,
+             const int32_t* rec_len, const uint8_t* keep_cols, int n_cols, int64_t col_num, int64_t col_den, double fade_len,
+             int curve, const double* sums, ds_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,7 @@ LOAD_DENSE, LOAD_CONV2D, LOAD_CONV1D, LOAD_CONVT1D = 0, 1, 2, 3
 PRO_NONE, PRO_AFFINE, PRO_AFFINE_SWISH, PRO_LRELU = 0, 1, 2, 3
 ACT_NONE, ACT_GELU2, ACT_TANH = 0, 1, 2
 LEVEL_MEASURE, LEVEL_PEAK, LEVEL_RMS, LEVEL_LOUDNESS = 0, 1, 2, 3
+PASTE_EQUAL_POWER, PASTE_LINEAR = 0, 1
 STORE_ROW, STORE_BATCH_T, STORE_CONVT, STORE_ATTN = 0, 1, 2, 3
 (LP_ADALN1, LP_W_QKV, LP_B_QKV, LP_W_PROJ1, LP_B_PROJ1, LP_ADALN2, LP_W_Q2, LP_B_Q2, LP_W_KV2, LP_B_KV2,
  LP_W_PROJ2, LP_B_PROJ2, LP_LN2_G, LP_LN2_B, LP_W_FC1, LP_B_FC1, LP_W_FC2, LP_B_FC2, LP_COUNT) = range(19)
@@ -197,6 +198,10 @@ _PROTOS = {
     "ds_level_gain": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_double, _vp, C.c_int, C.c_double,
                                 _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ds_level_apply": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "ds_paste_scratch_bytes": (_i64, [C.c_int, C.c_int]),
+    "ds_paste_sums": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "ds_paste": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _i64, _i64, C.c_double,
+                           C.c_int, _vp, _vp]),
 }
 # The caption-track entries (csrc/sampler.hip SampleCompose), a table of their own: tests/test_driver_host.py walks the
 # sampling entries of _PROTOS against its closed list of their rejections; these entries' rejections are walked by

@@ -2,7 +2,8 @@
 launcher of the kernel (csrc/stft_mel.hip) that `modeling.vocoder.Audio2Mel` and `modeling.melspec.WaveToMel` share; the
 polyphase table of `ds_resample` (csrc/resample.hip) and its launcher: audio at any integer sample rate in and out; the
 cross-fade table of `ds_mel_stitch` (csrc/misc.hip) and its launcher: window mels joined into one long mel; the K-weighting
-coefficients and segment plan of the `ds_level_*` entries (csrc/loudness.hip) and their launchers: loudness, true peak, gain.
+coefficients and segment plan of the `ds_level_*` entries (csrc/loudness.hip) and their launchers: loudness, true peak, gain;
+the launchers of `ds_paste_sums` / `ds_paste` (csrc/paste.hip): a recording pasted back over a rendering of it.
 
 The reference extracts mels with librosa on the host (Diffsound/vocoder/mel2wav/extract_mel_spectrogram.py:15-38,141-187)
 and reads audio with `librosa.load(path, sr=None)` (:167); its data preparation resamples with `librosa.load(path, sr=22050)`
@@ -419,6 +420,84 @@ def stitch_mel(win, hop_frames, scale=1.0, shift=0.0):
     out = torch.empty(B, C, max(F + (W - 1) * S, 0), device=win.device, dtype=torch.float32)
     _lib.check(_lib.lib().ds_mel_stitch(_lib.ptr(win), _lib.ptr(fade), _lib.ptr(out), B, W, C, F, S, float(scale), float(shift),
                                         _lib.stream()))
+    return out
+
+
+# ---- pasting a recording back over a rendering of it (csrc/paste.hip) ----------------------------------------------------------
+PASTE_CURVES = {"equal_power": _lib.PASTE_EQUAL_POWER, "linear": _lib.PASTE_LINEAR}
+
+
+def _paste_rows(ren, rec, keep_cols, off, rec_len, col_num, col_den):
+    """the checked, contiguous device operands the two paste entries share"""
+    if not torch.is_tensor(ren) or not torch.is_tensor(rec) or ren.dim() not in (2, 3) or rec.dim() != ren.dim():
+        raise ValueError("ren and rec must be tensors f32[B, T] or f32[B, C, T] of the same rank")
+    if not ren.is_cuda or not rec.is_cuda:
+        raise _lib.DiffsoundHipError("ren / rec is not on a GPU: the HIP path has no CPU fallback")
+    if ren.shape[:-1] != rec.shape[:-1]:
+        raise ValueError("ren %s and rec %s differ in rows" % (tuple(ren.shape), tuple(rec.shape)))
+    ren, rec = ren.float().contiguous(), rec.float().contiguous()
+    B = ren.shape[0]
+    keep_cols = torch.as_tensor(keep_cols)
+    if keep_cols.dim() != 2 or keep_cols.shape[0] != B or keep_cols.shape[1] < 1:
+        raise ValueError("keep_cols must be u8[B, n_cols] with n_cols >= 1")
+    keep_cols = (keep_cols != 0).to(torch.uint8).to(ren.device).contiguous()
+    off = torch.as_tensor(off, dtype=torch.int64).reshape(-1)
+    off = (off.expand(B) if off.numel() == 1 else off).to(ren.device).contiguous()
+    if off.shape != (B,):
+        raise ValueError("off must hold one offset, or one per clip")
+    if rec_len is not None:
+        rec_len = torch.as_tensor(rec_len, dtype=torch.int32).to(ren.device).contiguous()
+        if rec_len.shape != (B,):
+            raise ValueError("rec_len must hold one length per clip")
+    for v in (col_num, col_den):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("col_num and col_den must be integers, got %r" % (v,))
+    return ren, rec, keep_cols, off, rec_len
+
+
+def paste_sums(ren, rec, keep_cols, *, off=0, col_num, col_den=1, rec_len=None):
+    """ds_paste_sums on ren f32[B, T] and rec f32[B, Tr] (device) -> sums f64[B, 2] on the device: over the positions of kept
+    columns whose recording index n + off[b] is inside the recording, S_o = sum rec^2 and S_r = sum ren^2 in float64, in a
+    fixed order (include/diffsound_hip.h: ds_paste).  Two launches, no host synchronisation."""
+    ren, rec, keep_cols, off, rec_len = _paste_rows(ren, rec, keep_cols, off, rec_len, col_num, col_den)
+    if ren.dim() != 2:
+        raise ValueError("the sums are taken over waveforms f32[B, T]")
+    B, T = ren.shape
+    L = _lib.lib()
+    nbytes = max(int(L.ds_paste_scratch_bytes(B, T)), 8)
+    scratch = torch.empty(nbytes // 8, device=ren.device, dtype=torch.float64)
+    sums = torch.empty(B, 2, device=ren.device, dtype=torch.float64)
+    _lib.check(L.ds_paste_sums(_lib.ptr(ren), _lib.ptr(rec), B, T, rec.shape[1], _lib.ptr(off), _lib.ptr(rec_len),
+                               _lib.ptr(keep_cols), keep_cols.shape[1], int(col_num), int(col_den), _lib.ptr(scratch), nbytes,
+                               _lib.ptr(sums), _lib.stream()))
+    return sums
+
+
+def paste(ren, rec, keep_cols, *, off=0, col_num, col_den=1, fade_len=0.0, curve="equal_power", rec_len=None, sums=None,
+          match_gain=False):
+    """ds_paste: the recording `rec` over its rendering `ren` (both on the device, f32[B, T] / f32[B, Tr] waveforms or
+    f32[B, C, T] / f32[B, C, Tr] mel images) -> out like ren.  keep_cols u8[B, n_cols]: the kept columns, each col_num / col_den
+    positions long; position n reads the recording at n + off[b] (off: one offset or one per clip; outside [0, rec_len[b]) the
+    recording is 0).  In kept columns out is a bit copy of the recording; the rest is the rendering, cross-faded into the
+    recording over fade_len positions at the edge of a kept column, inside the regenerated column (curve "equal_power":
+    sin / cos, for waveforms; "linear": for mel images).  sums (paste_sums) or match_gain=True (waveforms, "equal_power"): the
+    rendering is scaled by g = sqrt(S_o / S_r) clamped to [1/4, 4].  The formula is in include/diffsound_hip.h (ds_paste).
+    No host synchronisation; a host tensor raises (there is no CPU path)."""
+    if curve not in PASTE_CURVES:
+        raise ValueError("curve must be one of %s, got %r" % (", ".join(sorted(PASTE_CURVES)), curve))
+    ren, rec, keep_cols, off, rec_len = _paste_rows(ren, rec, keep_cols, off, rec_len, col_num, col_den)
+    if match_gain and sums is None:
+        sums = paste_sums(ren, rec, keep_cols, off=off, col_num=col_num, col_den=col_den, rec_len=rec_len)
+    if sums is not None:
+        if not (torch.is_tensor(sums) and sums.is_cuda and sums.dtype == torch.float64 and tuple(sums.shape) == (ren.shape[0], 2)):
+            raise ValueError("sums must be f64[B, 2] on the device (paste_sums)")
+        sums = sums.contiguous()
+    B, T = ren.shape[0], ren.shape[-1]
+    C = ren.shape[1] if ren.dim() == 3 else 1
+    out = torch.empty_like(ren)
+    _lib.check(_lib.lib().ds_paste(_lib.ptr(ren), _lib.ptr(rec), _lib.ptr(out), B, C, T, rec.shape[-1], _lib.ptr(off),
+                                   _lib.ptr(rec_len), _lib.ptr(keep_cols), keep_cols.shape[1], int(col_num), int(col_den),
+                                   float(fade_len), PASTE_CURVES[curve], _lib.ptr(sums), _lib.stream()))
     return out
 
 

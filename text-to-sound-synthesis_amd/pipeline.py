@@ -253,34 +253,162 @@ def recording_loudness(item, rate=None, device="cuda"):
     return torch.cat(out)
 
 
+# Where the recording lies under the rendering -- a definition, from the two front ends in the code.  Content-image frame j is
+# front-end frame j + 6 (the centre crop of melspec.WaveToMel: (860 - 848) / 2), and that frame is centred on recording sample
+# 256 (j + 6) (frames are centred: PAD = N_FFT / 2).  The vocoder renders frame j into output samples [256 j, 256 j + 256), and
+# under the MelGAN Audio2Mel convention (pad (1024 - 256) / 2, no centring) frame j is centred on sample 256 j + 128.  So output
+# sample n at 22 050 Hz is recording sample n + 6 * 256 - 128: a constant shift, no drift.
+RECORDING_OFFSET = 6 * 256 - 128          # 1408
+FADE_SECONDS = 1024 / VOCODER_RATE        # the default cross-fade at the edge of a kept column: 4 mel frames
+KEEP_ORIGINAL = (None, "mel", "audio")
+
+
+def recording_offset(rate=None, shift_columns=0):
+    """The recording sample under output sample 0 at `rate` Hz (None: 22 050): floor((1408 + 4096 shift_columns) rate / 22050
+    + 0.5) -- 1408, 2816 at 44 100, 3065 at 48 000, 1022 at 16 000; shift_columns: the columns continue_audio skips."""
+    rate = VOCODER_RATE if rate is None else int(rate)
+    at_22k = RECORDING_OFFSET + COLUMN_SAMPLES * int(shift_columns)
+    return (2 * at_22k * rate + VOCODER_RATE) // (2 * VOCODER_RATE)
+
+
+def _check_keep_original(keep_original, fade_seconds, has_vocoder):
+    """the ValueErrors of the `keep_original` / `fade_seconds` keywords -> fade_seconds as a float"""
+    import math
+    if keep_original not in KEEP_ORIGINAL:
+        raise ValueError('keep_original must be None, "mel" or "audio", got %r' % (keep_original,))
+    if keep_original == "audio" and not has_vocoder:
+        raise ValueError('keep_original="audio" needs a vocoder: there is no waveform to paste into')
+    fade_seconds = float(fade_seconds)
+    if keep_original is not None and not (math.isfinite(fade_seconds) and fade_seconds >= 0.0):
+        raise ValueError("fade_seconds must be finite and >= 0, got %r" % (fade_seconds,))
+    return fade_seconds
+
+
+def paste_plan(driver, keep_original, *, batch, spans=None, keep_seconds=None, seconds=None, sample_rate=None,
+               fade_seconds=FADE_SECONDS, match_gain=True, has_vocoder=True):
+    """What `keep_original` means for one driver call, on the host: None for keep_original None, else
+      {"mode": "mel" | "audio", "keep_cols": u8[batch, n_cols] (1 = the recording's column is kept), "match_gain",
+       "mel":   {"off", "col_num": 16, "col_den": 1, "fade_len"}   in mel frames,
+       "audio": {"off", "col_num", "col_den", "fade_len", "rate"}  in samples at the output rate; col_num / col_den =
+                4096 rate / 22050 in lowest terms}.
+    driver "inpaint_audio" / "inpaint_scene": the columns spans_to_keep_mask(spans) holds; "continue_audio": the first
+    n = continuation_columns(keep_seconds) columns, which are the recording's last n -- the offsets grow by 53 - n columns
+    (16 (53 - n) frames; 4096 (53 - n) samples at 22 050 Hz, scaled with the 1408 and rounded once); "extend_audio": the first
+    53 of the ceil(samples / 4096) columns of a clip of `seconds`.  fade_len = fade_seconds x 22050 / 256 frames and
+    fade_seconds x rate samples.  An unknown keep_original, "audio" without a vocoder and a negative or non-finite
+    fade_seconds raise ValueError."""
+    import math
+    fade_seconds = _check_keep_original(keep_original, fade_seconds, has_vocoder)
+    if keep_original is None:
+        return None
+    batch, shift = int(batch), 0
+    if driver in ("inpaint_audio", "inpaint_scene"):
+        keep_cols = spans_to_keep_mask(spans, batch).view(batch, GRID_COLS, GRID_ROWS)[:, :, 0]
+    elif driver == "continue_audio":
+        n = continuation_columns(keep_seconds)
+        keep_cols = torch.zeros(batch, GRID_COLS, dtype=torch.bool)
+        keep_cols[:, :n] = True
+        shift = GRID_COLS - n
+    elif driver == "extend_audio":
+        n_cols = -(-int(round(_seconds_to_samples(seconds))) // COLUMN_SAMPLES)       # long_plan's samples
+        if n_cols <= GRID_COLS:
+            raise ValueError("extend_audio: seconds must exceed one grid, got %r" % (seconds,))
+        keep_cols = torch.zeros(batch, n_cols, dtype=torch.bool)
+        keep_cols[:, :GRID_COLS] = True
+    else:
+        raise ValueError("paste_plan: no driver %r" % (driver,))
+    rate = VOCODER_RATE if sample_rate is None else int(sample_rate)
+    g = math.gcd(COLUMN_SAMPLES * rate, VOCODER_RATE)
+    return {"mode": keep_original, "keep_cols": keep_cols.to(torch.uint8).contiguous(), "match_gain": bool(match_gain),
+            "mel": {"off": COLUMN_FRAMES * shift, "col_num": COLUMN_FRAMES, "col_den": 1,
+                    "fade_len": fade_seconds * VOCODER_RATE / 256},
+            "audio": {"off": recording_offset(rate, shift), "col_num": COLUMN_SAMPLES * rate // g, "col_den": VOCODER_RATE // g,
+                      "fade_len": fade_seconds * rate, "rate": rate}}
+
+
+def recording_at_rate(item, rate, out_rate, device="cuda"):
+    """The recordings a driver was given (`audio` / `audio_rate` as in melspec.mel_image_from_audio: a device tensor, host
+    arrays or `.wav` paths; one rate or one per clip) at `out_rate` Hz -> (f32[B, Tr] on the device, lengths i32[B] on the
+    device).  Rows are grouped by rate, one audio.resample per distinct rate; a clip whose rate already is out_rate is NOT
+    resampled: its samples go through untouched."""
+    from . import audio
+    from .modeling.melspec import SAMPLE_RATE, _clip_rates
+    out_rate = int(out_rate)
+    if torch.is_tensor(item) and item.is_cuda:
+        wave = (item[None] if item.dim() == 1 else item).float()
+        rates = [SAMPLE_RATE if r is None else int(r) for r in _clip_rates(rate, wave.shape[0])]
+        clips, lens_in, device = None, [wave.shape[1]] * wave.shape[0], wave.device
+        if len(set(rates)) == 1:
+            out = wave.contiguous() if rates[0] == out_rate else audio.resample(wave, rates[0], out_rate)
+            return out, torch.full((out.shape[0],), out.shape[1], dtype=torch.int32, device=device)
+    else:
+        clips = [item] if isinstance(item, (str, os.PathLike)) or (torch.is_tensor(item) and item.dim() == 1) else list(item)
+        rates = _clip_rates(rate, len(clips))
+        waves = []
+        for i, clip in enumerate(clips):
+            if isinstance(clip, (str, os.PathLike)):
+                x, rates[i] = audio.read_wav(clip)
+            else:
+                x, rates[i] = torch.as_tensor(clip).float().reshape(-1), SAMPLE_RATE if rates[i] is None else int(rates[i])
+            waves.append(x)
+        lens_in = [x.numel() for x in waves]
+    lens = [audio.resample_length(n, r, out_rate) for n, r in zip(lens_in, rates)]
+    buf = torch.zeros(len(lens), max(max(lens), 1), device=device)
+    for r in sorted(set(rates)):
+        rows = [i for i, q in enumerate(rates) if q == r]
+        if clips is None:
+            part = wave[rows]
+        else:
+            part = torch.zeros(len(rows), max(max(lens_in[i] for i in rows), 1))
+            for k, i in enumerate(rows):
+                part[k, :lens_in[i]] = waves[i]
+            part = part.to(device)
+        if r != out_rate:
+            part = audio.resample(part, r, out_rate, lengths=[lens_in[i] for i in rows])
+        buf[rows, :part.shape[1]] = part[:, :buf.shape[1]]
+    return buf, torch.tensor(lens, dtype=torch.int32).to(device)
+
+
 _LEVEL = threading.local()        # the (spec, recording) of the driver call this thread is inside, read by Diffsound._finish
+_PASTE = threading.local()        # the keep_original request of the driver call this thread is inside (Diffsound._paste_plan)
 
 
-def _levelled(takes_recording):
-    """Gives a driver the keyword `level=None` (level_spec; keyword-only, behind everything the driver declares).  It is a
-    decorator because levelling is one step of the tail the drivers share (Diffsound._finish), not of any driver: the call's
-    checked spec -- and, for "match", the `audio` / `audio_rate` the driver was given -- is held for the duration of the call
-    and _finish applies it; a driver's own parameters stay what they were.  level=None calls the driver as it is."""
+def _levelled(takes_recording, pastes=False):
+    """Gives a driver the keyword `level=None` (level_spec; keyword-only, behind everything the driver declares) and, with
+    pastes=True, `keep_original=None`, `fade_seconds` and `match_gain` (paste_plan).  It is a decorator because levelling
+    and pasting are steps of the tail the drivers share (Diffsound._finish), not of any driver: the call's checked spec
+    -- and, for "match" and for pasting, the `audio` / `audio_rate` the driver was given -- is held for the duration of the call
+    and the tail applies it; a driver's own parameters stay what they were.  level=None and keep_original=None call the
+    driver as it is."""
     def deco(fn):
         sig = inspect.signature(fn)
 
         @functools.wraps(fn)
-        def driver(self, *args, level=None, **kwargs):
+        def driver(self, *args, level=None, keep_original=None, fade_seconds=FADE_SECONDS, match_gain=True, **kwargs):
+            if not pastes and (keep_original is not None or fade_seconds != FADE_SECONDS or match_gain is not True):
+                raise TypeError("%s() takes no keep_original / fade_seconds / match_gain: it holds no recording" % fn.__name__)
             spec = level_spec(level, takes_recording)
-            if spec is None:
+            _check_keep_original(keep_original, fade_seconds, getattr(self, "vocoder", None) is not None)
+            if spec is None and keep_original is None:
                 return fn(self, *args, **kwargs)
             recording = None
-            if spec["strategy"] == "match":
+            if keep_original is not None or spec["strategy"] == "match":
                 given = sig.bind(self, *args, **kwargs).arguments
                 recording = (given["audio"], given.get("audio_rate"))
-            outer = getattr(_LEVEL, "request", None)
-            _LEVEL.request = (spec, recording)
+            outer = getattr(_LEVEL, "request", None), getattr(_PASTE, "request", None)
+            _LEVEL.request = None if spec is None else (spec, recording)
+            _PASTE.request = None if keep_original is None else {
+                "keep_original": keep_original, "fade_seconds": fade_seconds, "match_gain": match_gain, "recording": recording}
             try:
                 return fn(self, *args, **kwargs)
             finally:
-                _LEVEL.request = outer
-        driver.__signature__ = sig.replace(parameters=list(sig.parameters.values())
-                                           + [inspect.Parameter("level", inspect.Parameter.KEYWORD_ONLY, default=None)])
+                _LEVEL.request, _PASTE.request = outer
+        extra = [inspect.Parameter("level", inspect.Parameter.KEYWORD_ONLY, default=None)]
+        if pastes:
+            extra += [inspect.Parameter("keep_original", inspect.Parameter.KEYWORD_ONLY, default=None),
+                      inspect.Parameter("fade_seconds", inspect.Parameter.KEYWORD_ONLY, default=FADE_SECONDS),
+                      inspect.Parameter("match_gain", inspect.Parameter.KEYWORD_ONLY, default=True)]
+        driver.__signature__ = sig.replace(parameters=list(sig.parameters.values()) + extra)
         return driver
     return deco
 
@@ -365,12 +493,45 @@ class Diffsound:
         from . import audio
         return audio.resample(wave[:, 0], VOCODER_RATE, sample_rate)[:, None]
 
+    def _paste_plan(self, driver, batch, **where):
+        """paste_plan for the driver call this thread is inside (None without keep_original) + the recording it was given"""
+        request = getattr(_PASTE, "request", None)
+        if request is None:
+            return None
+        plan = paste_plan(driver, request["keep_original"], batch=batch, fade_seconds=request["fade_seconds"],
+                          match_gain=request["match_gain"], has_vocoder=self.vocoder is not None, **where)
+        return dict(plan, recording=request["recording"])
+
     @staticmethod
-    def _finish(wave, sample_rate):
-        """The tail every driver shares: the vocoder's f32[B,1,T] -> at `sample_rate` (_at_rate) -> brought to the level the
-        driver call asked for (`level=`, _levelled), at that rate, on the device (audio.level).  No `level`: no launch, the
-        waveform as it is."""
-        wave = Diffsound._at_rate(wave, sample_rate)
+    def _paste_mel(mel, plan):
+        """the decoder's mel f32[B,80,F] in [-1,1] -> with the recording's own content image in the kept columns (plan None:
+        as it is)"""
+        if plan is None:
+            return mel
+        from . import audio
+        from .modeling.melspec import mel_image_from_audio
+        image = mel_image_from_audio(plan["recording"][0], mel.device, rate=plan["recording"][1])[:, 0]
+        p = plan["mel"]
+        return audio.paste(mel, image, plan["keep_cols"], off=p["off"], col_num=p["col_num"], col_den=p["col_den"],
+                           fade_len=p["fade_len"], curve="linear")
+
+    @staticmethod
+    def _paste_audio(wave, plan):
+        """the rendering f32[B,1,T] at the output rate -> with the recording's own samples in the kept columns (mode "audio")"""
+        if wave is None or plan is None or plan["mode"] != "audio":
+            return wave
+        from . import audio
+        p = plan["audio"]
+        rec, lens = recording_at_rate(plan["recording"][0], plan["recording"][1], p["rate"], wave.device)
+        return audio.paste(wave[:, 0], rec, plan["keep_cols"], off=p["off"], col_num=p["col_num"], col_den=p["col_den"],
+                           fade_len=p["fade_len"], curve="equal_power", rec_len=lens, match_gain=plan["match_gain"])[:, None]
+
+    @staticmethod
+    def _finish(wave, sample_rate, paste=None):
+        """The tail every driver shares: the vocoder's f32[B,1,T] -> at `sample_rate` (_at_rate) -> the recording's samples
+        pasted over it (paste = a paste_plan of mode "audio") -> brought to the level the driver call asked for (`level=`,
+        _levelled), at that rate, on the device (audio.level).  No plan and no `level`: no launch, the waveform as it is."""
+        wave = Diffsound._paste_audio(Diffsound._at_rate(wave, sample_rate), paste)
         request = getattr(_LEVEL, "request", None)
         if wave is None or request is None:
             return wave
@@ -405,13 +566,16 @@ class Diffsound:
             tr.truncation_r, tr.truncation_k = keep
         return self._render(out["content_token"], content["content_quant"].shape, save_root)
 
-    def _render(self, tokens, zshape, save_root=None, sample_rate=None):
-        """tokens -> decode -> vocoder (-> sample_rate -> level: _finish): the tail the audio-in drivers share.  Returns (mel01, wave or None,
-        tokens); with save_root also writes `{i:06d}.npy` and, with a vocoder, `{i:06d}.wav`."""
+    def _render(self, tokens, zshape, save_root=None, sample_rate=None, paste=None):
+        """tokens -> decode (-> the recording's mel pasted: paste = a paste_plan) -> vocoder (-> sample_rate -> the recording's
+        samples pasted -> level: _finish): the tail the audio-in drivers share.  Returns (mel01, wave or None, tokens); with
+        save_root also writes `{i:06d}.npy` and, with a vocoder, `{i:06d}.wav`."""
         import numpy as np
         mel = self.model.decode_to_img(tokens, zshape)
+        if paste is not None:
+            mel = self._paste_mel(mel[:, 0], paste)[:, None]
         wave = None if self.vocoder is None else self.vocoder(mel[:, 0], scale=0.5, shift=0.5)
-        wave = self._finish(wave, sample_rate)
+        wave = self._finish(wave, sample_rate, paste)
         mel01 = (mel[:, 0] + 1) / 2
         if save_root is not None:
             os.makedirs(save_root, exist_ok=True)
@@ -452,7 +616,7 @@ class Diffsound:
             tr.truncation_r, tr.truncation_k, tr.repeat_rate, model.truncation_forward = saved
         return out["content_token"]
 
-    @_levelled(True)
+    @_levelled(True, pastes=True)
     @torch.no_grad()
     def inpaint_audio(self, audio, text, spans, keep_mode="clamp", truncation_rate=0.85, save_root=None, audio_rate=None,
                       caption_ids=None, seed=None, sample_rate=None, guidance_scale=None, negative_text=None, purity_steps=None,
@@ -467,25 +631,40 @@ class Diffsound:
         (mel01, wave or None, tokens) and writes the files generate_sample_from_audio writes.
         inpaint_scene regenerates the spans under a scene (caption tracks) instead of one caption.
 
-        What is kept is the TOKENS: exact.  The returned audio is the codec's and the vocoder's rendering everywhere -- the
-        held region is not the input's samples (the decoder's lowest level attends over all 265 positions), and the original
-        mel or audio is not pasted back.  level= as in generate_sample_with_condition; "match": the result is brought to the
-        integrated loudness of the recording, measured at the recording's own rate and length."""
+        What is kept is the TOKENS: exact.  By default (keep_original=None) the returned audio is the codec's and the vocoder's
+        rendering everywhere -- the held region is not the input's samples (the decoder's lowest level attends over all 265
+        positions).  keep_original= (keyword-only, on the four drivers that hold a recording; paste_plan) puts the recording
+        itself back outside the spans:
+          "mel":   the recording's own content image (melspec.mel_image_from_audio) replaces the decoder's mel in the kept
+                   columns, cross-faded linearly into it over fade_seconds inside the regenerated columns; the vocoder renders
+                   the pasted mel, and the returned mel01 is the pasted mel.  The waveform is the vocoder's everywhere.
+          "audio": all of "mel", and the recording's own samples -- at the output rate; a recording already at that rate is not
+                   resampled -- replace the vocoder's in the kept columns: bit-equal to the input at sample n + RECORDING_OFFSET
+                   (scaled to the rate; recording_offset), with an equal-power cross-fade of fade_seconds inside the regenerated
+                   columns and, under match_gain=True, one gain per clip on the rendering, sqrt of the ratio of the two signals'
+                   energies over the kept region, clamped to [1/4, 4].  Needs a vocoder (ValueError without).
+        fade_seconds (default 1024 / 22050, >= 0; 0: a hard cut) and match_gain apply only with keep_original.  Tokens are
+        never affected; the order of the tail is vocoder -> sample_rate -> paste -> level.  The alignment is a definition taken
+        from the code's two front ends (RECORDING_OFFSET), not a measurement on a trained vocoder; there is no phase alignment
+        of the rendering to the recording and no limiter.
+        level= as in generate_sample_with_condition; "match": the result is brought to the integrated loudness of the
+        recording, measured at the recording's own rate and length."""
         content = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})
         known = content["content_token"]
         keep = spans_to_keep_mask(spans, known.shape[0], known.device)
         tokens = self._inpaint_tokens(known, keep, text, keep_mode, truncation_rate, caption_ids, seed, guidance_scale,
                                       negative_text, purity_steps, purity_weight)
-        return self._render(tokens, content["content_quant"].shape, save_root, sample_rate)
+        return self._render(tokens, content["content_quant"].shape, save_root, sample_rate,
+                            self._paste_plan("inpaint_audio", known.shape[0], spans=spans, sample_rate=sample_rate))
 
-    @_levelled(True)
+    @_levelled(True, pastes=True)
     @torch.no_grad()
     def inpaint_scene(self, audio, tracks, spans, scale=3.0, keep_mode="clamp", truncation_rate=0.85, save_root=None,
                       audio_rate=None, caption_ids=None, seed=None, sample_rate=None, negative_text=None):
         """inpaint_audio under a scene instead of one caption: the spans are regenerated under `tracks` -- caption tracks as
         in generate_scene, [(text, t0, t1[, scale]), ...] in the clip's own seconds, one scene or one per clip; a track that
-        names no scale gets `scale` -- and the rest of the recording is kept, as tokens, exactly.  The other arguments and
-        the return are inpaint_audio's.  (A method of its own: inpaint_audio's keywords are what they were.)"""
+        names no scale gets `scale` -- and the rest of the recording is kept, as tokens, exactly (keep_original= as in
+        inpaint_audio: also as its own mel, or its own samples).  The other arguments and the return are inpaint_audio's.  (A method of its own: inpaint_audio's keywords are what they were.)"""
         content = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})
         known = content["content_token"]
         keep = spans_to_keep_mask(spans, known.shape[0], known.device)
@@ -494,23 +673,27 @@ class Diffsound:
         trk = self._scene(tracks, GRID_COLS, None if is_scenes else known.shape[0], scale)
         tokens = self._inpaint_tokens(known, keep, None, keep_mode, truncation_rate, caption_ids, seed, None, negative_text,
                                       tracks=trk)
-        return self._render(tokens, content["content_quant"].shape, save_root, sample_rate)
+        return self._render(tokens, content["content_quant"].shape, save_root, sample_rate,
+                            self._paste_plan("inpaint_scene", known.shape[0], spans=spans, sample_rate=sample_rate))
 
-    @_levelled(True)
+    @_levelled(True, pastes=True)
     @torch.no_grad()
     def continue_audio(self, audio, text, keep_seconds, keep_mode="clamp", truncation_rate=0.85, save_root=None,
                        audio_rate=None, caption_ids=None, seed=None, sample_rate=None, guidance_scale=None, negative_text=None,
                        purity_steps=None, purity_weight=0.0):
         """Generate the clip that follows given recordings: the last ceil(keep_seconds 22050 / 4096) token columns of the
         recording become the first columns of a new 10-s clip (a shift by 5 (53 - n) tokens), held, and the remaining columns
-        are generated under `text`.  Arguments and return as inpaint_audio.  The new clip's head is the codec's rendering of
-        the kept tail (exact tokens, not the input's samples).  This returns the NEW clip only; extend_audio returns the
+        are generated under `text`.  Arguments and return as inpaint_audio.  By default the new clip's head is the codec's
+        rendering of the kept tail (exact tokens, not the input's samples); keep_original="mel" / "audio" (inpaint_audio) makes
+        it the recording's own mel frames from 16 (53 - n) on / its own samples from 4096 (53 - n) + RECORDING_OFFSET on (at
+        22 050 Hz; scaled and rounded once at another output rate).  This returns the NEW clip only; extend_audio returns the
         recording and what follows it as one clip, joined in the mel domain."""
         content = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})
         known, keep = continuation_tokens(content["content_token"], continuation_columns(keep_seconds))
         tokens = self._inpaint_tokens(known, keep, text, keep_mode, truncation_rate, caption_ids, seed, guidance_scale,
                                       negative_text, purity_steps, purity_weight)
-        return self._render(tokens, content["content_quant"].shape, save_root, sample_rate)
+        return self._render(tokens, content["content_quant"].shape, save_root, sample_rate,
+                            self._paste_plan("continue_audio", known.shape[0], keep_seconds=keep_seconds, sample_rate=sample_rate))
 
     def _long_tokens(self, text, windows, overlap_cols, keep_mode, truncation_rate, caption_ids, seed,
                      guidance_scale, negative_text, start_token=None, purity_steps=None, purity_weight=0.0, tracks=None,
@@ -533,8 +716,9 @@ class Diffsound:
 
     VOCODER_CHUNK_FRAMES = 64 * 848       # mel frames per vocoder call of a long clip: the largest call the benchmarks run
 
-    def _render_long(self, out, windows, overlap_cols, samples, save_root, sample_rate):
-        """window mels -> ds_mel_stitch (codec domain) -> ONE vocoder pass per clip over its whole stitched mel -> both cut to
+    def _render_long(self, out, windows, overlap_cols, samples, save_root, sample_rate, paste=None):
+        """window mels -> ds_mel_stitch (codec domain) (-> the recording's mel pasted: paste = a paste_plan; its samples
+        pasted in _finish) -> ONE vocoder pass per clip over its whole stitched mel -> both cut to
         `samples` (the vocoder's reflection at the far end lies past the cut) -> sample_rate -> level (_finish), files.  Clips go through the
         vocoder in batch chunks of at most VOCODER_CHUNK_FRAMES mel frames; a clip is never split."""
         import numpy as np
@@ -542,11 +726,12 @@ class Diffsound:
         win = out["content"]                                          # [B W, 1, 80, 848], clip-major: index b W + w
         B = win.shape[0] // windows
         mel = audio.stitch_mel(win.reshape(B, windows, win.shape[2], win.shape[3]), (GRID_COLS - overlap_cols) * COLUMN_FRAMES)
+        mel = self._paste_mel(mel, paste)
         wave = None
         if self.vocoder is not None:
             step = max(1, self.VOCODER_CHUNK_FRAMES // mel.shape[2])
             wave = torch.cat([self.vocoder(mel[i:i + step], scale=0.5, shift=0.5) for i in range(0, B, step)], 0)
-            wave = self._finish(wave[:, :, :samples].contiguous(), sample_rate)
+            wave = self._finish(wave[:, :, :samples].contiguous(), sample_rate, paste)
         mel01 = ((mel + 1) / 2)[:, :, :-(-samples // 256)].contiguous()
         if save_root is not None:
             os.makedirs(save_root, exist_ok=True)
@@ -622,7 +807,7 @@ class Diffsound:
                                 sample_type="top" + str(truncation_rate) + ("r,fast" + str(fast - 1) if fast else "r"))
         return self._render_long(out, windows, n, samples, save_root, sample_rate)
 
-    @_levelled(True)
+    @_levelled(True, pastes=True)
     @torch.no_grad()
     def extend_audio(self, audio, text, seconds, overlap_seconds=2.4, truncation_rate=0.85, keep_mode="clamp", caption_ids=None,
                      seed=None, sample_rate=None, guidance_scale=None, negative_text=None, save_root=None, audio_rate=None,
@@ -630,8 +815,9 @@ class Diffsound:
         """Extend given recordings to `seconds` in total (more than one grid, 217 088 / 22 050 s): audio / audio_rate as in
         continue_audio; the recording is encoded to its 5 x 53 tokens, which become window 0, and the windows after it are
         generated under `text` as in generate_long.  Returns what generate_long returns; tokens[:, 0] are the recording's.
-        The head of the result is the codec's and the vocoder's rendering of the recording's tokens, not the input's samples
-        (see continue_audio)."""
+        By default the head of the result is the codec's and the vocoder's rendering of the recording's tokens, not the
+        input's samples; keep_original="mel" / "audio" (inpaint_audio) keeps columns 0 .. 52 of the long clip as the recording's
+        own mel / samples, with the cross-fade inside column 53."""
         windows, n, _, samples = long_plan(seconds, overlap_seconds)
         if windows < 2:
             raise ValueError("extend_audio: seconds must exceed one grid (%d samples at %d Hz), got %r"
@@ -639,7 +825,8 @@ class Diffsound:
         start = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})["content_token"]
         out = self._long_tokens(text, windows, n, keep_mode, truncation_rate, caption_ids, seed, guidance_scale, negative_text,
                                 start_token=start, purity_steps=purity_steps, purity_weight=purity_weight)
-        return self._render_long(out, windows, n, samples, save_root, sample_rate)
+        return self._render_long(out, windows, n, samples, save_root, sample_rate,
+                                 self._paste_plan("extend_audio", start.shape[0], seconds=seconds, sample_rate=sample_rate))
 
     # ---- likelihood scoring (DiffusionTransformer.score_tokens) -------------------------------------------
     @torch.no_grad()
