@@ -657,11 +657,16 @@ int ds_profile_collect_n(double* ms, double* flops, int64_t* launches, int n);
 int ds_codebook_gather(const int64_t* tokens, const float* codebook, float* out, int B, int H, int W, int C,
                        int K, ds_stream_t stream);
 /* VectorQuantizer.forward's nearest-code search (vqvae/quantize.py:46-53): z [M][C] encoder output rows,
- * ze [M][K] = z E^T (ds_gemm), ee [K] = row norms^2 of the codebook -> idx [M] (first minimum), dmin [M] optional */
+ * ze [M][K] = z E^T (ds_gemm), ee [K] = row norms^2 of the codebook -> idx [M], dmin [M] optional (may be NULL).
+ * d[k] = (sum_c z[c]^2 + ee[k]) - 2 ze[k] in fp32; idx = torch.argmin(d) on EVERY row: a NaN distance is the minimum and
+ * the first NaN wins, among equal values the lowest index wins, a row of +inf gives 0 -- so 0 <= idx < K whatever the
+ * inputs hold (a non-finite latent, an overflowing |z|^2); dmin = the winning distance, NaN included.  M, C, K > 0. */
 int ds_vq_argmin(const float* z, const float* ze, const float* ee, int64_t* idx, float* dmin, int M, int C, int K,
                  ds_stream_t stream);
 /* GroupNorm(groups, C, eps) statistics of x [B][P][C] folded into per-(b,c) scale/shift
- * (model.py:34-35); work >= B*ceil(P/256)*2*C doubles */
+ * (model.py:34-35); work >= B*ceil(P/256)*2*C doubles.  Sums in double of x minus a per-(sample, group) pivot (the group's
+ * first value), one rounding to fp32: scale within 2^-22 relative of the two-pass float64 value, shift within 2^-22 (|beta| +
+ * |mean rstd gamma|), for group means up to 1e4 standard deviations.  B, P, C > 0; C % 4 == 0, C <= 1024, groups <= 64. */
 int ds_groupnorm_stats(const float* x, int B, int P, int C, int groups, const float* gamma, const float* beta,
                        float eps, double* work, float* scale, float* shift, ds_stream_t stream);
 /* its second half alone: part = [B][nchunk][2][C] double partial sums (sum | sum of squares per channel over a chunk of
@@ -733,13 +738,17 @@ int ds_softmax_rows(float* x, int rows, int n, int ld, float scale, ds_stream_t 
  * ONE-channel image x f32[B][H][W], w [Cout][9] (= weight [Cout][1][3][3]), bias [Cout] -> out f32[B][H][W][Cout]
  * (channels-last).  Direct fp32 multiply-adds, taps in the conv's order; store-bound.  Cout % 4 == 0, divides 1024.  gn_part
  * (may be null): [B][ds_conv3x3_c1_chunks(H, W)][2][Cout] doubles = per-channel sum / sum of squares of the output per row
- * (one chunk per image row), what ds_groupnorm_finish reads (the GroupNorm that follows needs no pass of its own over the
- * output).  W <= 2046. */
+ * (one chunk per image row), summed in double from the first value; what ds_groupnorm_finish reads (the GroupNorm that
+ * follows needs no pass of its own over the output).  W <= 2046. */
 int ds_conv3x3_c1(const float* x, const float* w, const float* bias, float* out, int B, int H, int W, int Cout,
                   double* gn_part, ds_stream_t stream);
 int ds_conv3x3_c1_chunks(int H, int W);
-/* tap-sum for single-output-channel convs fed by a GEMM with N = taps */
+/* tap-sum for single-output-channel convs fed by a GEMM with N = taps: out[b][y][x] = bias + sum over (ky, kx) in that order
+ * of taps[b][y + ky - 1][x + kx - 1][3 ky + kx] (zero padding 1; an fp32 chain), taps [B][H][W][ldt], ldt >= 9; B, H, W > 0 */
 int ds_stencil9(const float* taps, int ldt, float bias, float* out, int B, int H, int W, ds_stream_t stream);
+/* out[b][t] = tanh(bias + sum_{k<7} taps[b][reflect(t + k - 3)][k]), ReflectionPad1d(3): reflect(s) = -s below 0 and
+ * 2 (N - 1) - s past N - 1, ONE bounce -- so N >= 4, like ds_melgan_final's T (PyTorch's ReflectionPad1d(3) refuses N <= 3
+ * too); taps [B][N][ldt], ldt >= 7, B > 0.  N < 4 returns -1 and launches nothing. */
 int ds_stencil7_tanh(const float* taps, int ldt, float bias, float* out, int B, int N, ds_stream_t stream);
 /* mel [B][C][T] -> [B][T][Cpad], y = a*x + b (generate_samples_batch.py:181-182 uses a = b = 0.5) */
 int ds_mel_to_cl(const float* mel, float* out, int B, int C, int T, int Cpad, float a, float b,

@@ -91,7 +91,17 @@ __global__ __launch_bounds__(256) void ds_mel_to_cl_kernel(const float* __restri
 
 // ---- nearest-code search of VectorQuantizer.forward (vqvae/quantize.py:46-53) --------------------------
 // d[k] = (sum_c z[c]^2 + ee[k]) - 2 * ze[k] with ze = z E^T from the GEMM and ee[k] = sum_c E[k][c]^2 -- the
-// reference's expression, same association; argmin with the first index winning ties (torch.argmin).
+// reference's expression, same association; argmin with torch.argmin's semantics on every row: a NaN distance is the
+// minimum and the first NaN wins, among equal values the lowest index wins (an all-+inf row gives 0), so the index written
+// is always in [0, K).  (The first version updated only on d < best from (INFINITY, 0x7fffffff): a row of NaNs or of +inf
+// left the sentinel in idx[row], and the consumers index the codebook with it.)
+// `a` at index ia is ahead of `b` at index ib in that order:
+__device__ __forceinline__ bool ds_argmin_ahead(float a, int ia, float b, int ib) {
+    const bool na = a != a, nb = b != b;
+    if (na || nb) return na && (!nb || ia < ib);
+    return a < b || (a == b && ia < ib);
+}
+
 __global__ __launch_bounds__(256) void ds_vq_argmin_kernel(const float* __restrict__ z, const float* __restrict__ ze,
                                                            const float* __restrict__ ee, int64_t* __restrict__ idx,
                                                            float* __restrict__ dmin, int M, int C, int K) {
@@ -107,15 +117,15 @@ __global__ __launch_bounds__(256) void ds_vq_argmin_kernel(const float* __restri
     for (int o = 32; o > 0; o >>= 1) zz += __shfl_xor(zz, o);
     float best = INFINITY;
     int bi = 0x7fffffff;
-    for (int k = lane; k < K; k += 64) {   // ascending k within a lane keeps the first minimum
+    for (int k = lane; k < K; k += 64) {   // (+inf, sentinel) loses to every real entry; lane 0 always has k = 0 (K > 0)
         const float d = (zz + ee[k]) - 2.f * ze[(size_t)row * K + k];
-        if (d < best) { best = d; bi = k; }
+        if (ds_argmin_ahead(d, k, best, bi)) { best = d; bi = k; }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ob = __shfl_xor(best, o);
         const int oi = __shfl_xor(bi, o);
-        if (ob < best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        if (ds_argmin_ahead(ob, oi, best, bi)) { best = ob; bi = oi; }
     }
     if (lane == 0) {
         idx[row] = bi;
@@ -168,6 +178,7 @@ extern "C" int ds_codebook_gather(const int64_t* tokens, const float* codebook, 
                                   int C, int K, ds_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     DS_CHECK_ARG(tokens && codebook && out, "null pointer");
+    DS_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && K > 0, "sizes must be positive");
     DS_CHECK_ARG(C % 4 == 0, "C must be a multiple of 4");
     hipLaunchKernelGGL(ds_codebook_gather_kernel, dim3((B * H * W + 3) / 4), dim3(256), 0, stream, tokens, codebook,
                        out, B, H, W, C, K);
@@ -190,11 +201,11 @@ extern "C" int ds_softmax_rows(float* x, int rows, int n, int ld, float scale, d
 // thread keeps the 4 x 9 weights of its four output channels in registers and walks the row's pixels; the 32 threads of a pixel
 // write its 512 contiguous bytes (Cout = 128).  The GroupNorm that follows gets its statistics from this pass (per-segment partial sums), like from the 3x3 kernel.
 #define C1_WMAX 2046   // widest image row (three zero-padded input rows of it live in LDS: 24 KB)
+template <bool STATS>                             // STATS: gn_part is written (a compile-time flag: no branch in the pixel loop)
 __global__ __launch_bounds__(256) void ds_conv3x3_c1_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ bias, float* __restrict__ out, int H, int W,
                                                             int Cout, double* __restrict__ gn_part) {
-    __shared__ float xs[3][C1_WMAX + 2];              // input rows y-1, y, y+1 with the zero padding in place
-    __shared__ float red[2][256][4];
+    __shared__ __attribute__((aligned(16))) float xs[3][C1_WMAX + 2];   // input rows y-1, y, y+1 with the zero padding in place
     const int tpp = Cout >> 2;                        // threads per pixel (4 output channels each)
     const int cg = threadIdx.x % tpp, slot = threadIdx.x / tpp, slots = 256 / tpp;
     const int b = blockIdx.y, y = blockIdx.x;         // one image row of one sample per workgroup: no index divisions
@@ -203,32 +214,59 @@ __global__ __launch_bounds__(256) void ds_conv3x3_c1_kernel(const float* __restr
         const int r = i / (W + 2), c = i - r * (W + 2), sy = y + r - 1, sx = c - 1;
         xs[r][c] = (sy >= 0 && sy < H && sx >= 0 && sx < W) ? xb[(size_t)sy * W + sx] : 0.f;
     }
-    float wr[4][9];
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    f32x2 w01[9], w23[9];                             // the weights of channels (0, 1) and (2, 3) of the thread's four, per tap
 #pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int k = 0; k < 9; ++k) wr[c][k] = w[(size_t)(cg * 4 + c) * 9 + k];
+    for (int k = 0; k < 9; ++k) {
+        w01[k] = f32x2{w[(size_t)(cg * 4 + 0) * 9 + k], w[(size_t)(cg * 4 + 1) * 9 + k]};
+        w23[k] = f32x2{w[(size_t)(cg * 4 + 2) * 9 + k], w[(size_t)(cg * 4 + 3) * 9 + k]};
+    }
     const f32x4 bv = *(const f32x4*)(bias + cg * 4);
     float* ob = out + ((size_t)b * H + y) * W * Cout;
-    f32x4 s1 = f32x4{0.f, 0.f, 0.f, 0.f}, s2 = s1;
+    // the statistics are summed in double from the first value, like ds_conv3x3_f16x2's: fp32 sums over the row's W / slots
+    // pixels of a thread round the same way every time on a silent mel (constant output): measured, rstd and the shift term
+    // 27 x 2^-22 off on an all -1 mel of 80 x 848, 12 x where only the columns past 300 are silent
+    double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
     __syncthreads();
     for (int xx = slot; xx < W; xx += slots) {
-        f32x4 o = bv;
+        f32x2 o01 = f32x2{bv[0], bv[1]}, o23 = f32x2{bv[2], bv[3]};
+        {
+            // Taps in the conv's own order (ky major), every operation spelled out and nothing left to contract: the encoder's
+            // tokens hang on these bits, and which multiply-adds the compiler fuses changed with an unrelated edit of this
+            // kernel (a quarter of the outputs moved by an ulp).  What is written here is what the kernel has computed since it
+            // was added: channels 0 and 1 of a thread's four in fused multiply-adds throughout; channels 2 and 3 fused at the
+            // first tap, then a rounded product and a rounded sum per tap.
+#pragma clang fp contract(off)
 #pragma unroll
-        for (int ky = 0; ky < 3; ++ky)                // taps in the conv's own order (ky major): an fp32 multiply-add chain
+            for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const float t = xs[ky][xx + kx];      // (the threads of a pixel read the same word: an LDS broadcast)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) o[c] += wr[c][ky * 3 + kx] * t;
-            }
+                for (int kx = 0; kx < 3; ++kx) {
+                    const int k = ky * 3 + kx;
+                    const float t1 = xs[ky][xx + kx];     // (the threads of a pixel read the same word: an LDS broadcast)
+                    const f32x2 t = f32x2{t1, t1};
+                    o01 = __builtin_elementwise_fma(w01[k], t, o01);
+                    if (k == 0)
+                        o23 = __builtin_elementwise_fma(w23[k], t, o23);
+                    else
+                        o23 = o23 + w23[k] * t;           // (pairs of channels: the packed two-lane instructions)
+                }
+        }
+        const f32x4 o = f32x4{o01[0], o01[1], o23[0], o23[1]};
         *(f32x4*)(ob + (size_t)xx * Cout + cg * 4) = o;
-        s1 += o;
-        s2 += o * o;
+        if (STATS) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const double d = (double)o[c];
+                s1[c] += d;
+                s2[c] = __builtin_fma(d, d, s2[c]);
+            }
+        }
     }
-    if (gn_part) {
+    if (STATS) {
         // GroupNorm statistics of the OUTPUT (the next op is a GroupNorm): per-channel sum and sum of squares of this row,
         // slots added in a fixed order -> part[b][row][2][Cout] doubles (the format ds_groupnorm_finish reads)
+        __syncthreads();                                  // every thread has read its last pixel: the input rows' LDS is free
+        double (*red)[256][4] = (double (*)[256][4])&xs[0][0];   // [2][256][4] doubles = 16 KB of the rows' 24 KB
 #pragma unroll
         for (int c = 0; c < 4; ++c) { red[0][threadIdx.x][c] = s1[c]; red[1][threadIdx.x][c] = s2[c]; }
         __syncthreads();
@@ -237,7 +275,7 @@ __global__ __launch_bounds__(256) void ds_conv3x3_c1_kernel(const float* __restr
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 double a1 = 0.0, a2 = 0.0;
-                for (int sl = 0; sl < slots; ++sl) { a1 += (double)red[0][sl * tpp + cg][c]; a2 += (double)red[1][sl * tpp + cg][c]; }
+                for (int sl = 0; sl < slots; ++sl) { a1 += red[0][sl * tpp + cg][c]; a2 += red[1][sl * tpp + cg][c]; }
                 pp[c] = a1;
                 pp[Cout + c] = a2;
             }
@@ -256,7 +294,10 @@ extern "C" int ds_conv3x3_c1(const float* x, const float* w, const float* bias, 
     DS_CHECK_ARG(Cout % 4 == 0 && Cout >= 4 && Cout <= 1024 && 1024 % Cout == 0, "Cout: a multiple of 4 that divides 1024");
     DS_CHECK_ARG((((uintptr_t)bias | (uintptr_t)out) & 15) == 0, "bias / out must be 16-byte aligned");
     DS_CHECK_ARG(W <= C1_WMAX && B <= 65535, "rows of at most 2046 pixels, at most 65535 samples");
-    hipLaunchKernelGGL(ds_conv3x3_c1_kernel, dim3(H, B), dim3(256), 0, (hipStream_t)stream_, x, w, bias, out, H, W, Cout, gn_part);
+    if (gn_part)
+        hipLaunchKernelGGL(ds_conv3x3_c1_kernel<true>, dim3(H, B), dim3(256), 0, (hipStream_t)stream_, x, w, bias, out, H, W, Cout, gn_part);
+    else
+        hipLaunchKernelGGL(ds_conv3x3_c1_kernel<false>, dim3(H, B), dim3(256), 0, (hipStream_t)stream_, x, w, bias, out, H, W, Cout, gn_part);
     DS_CHECK_LAUNCH();
     return 0;
 }
@@ -264,7 +305,7 @@ extern "C" int ds_conv3x3_c1(const float* x, const float* w, const float* bias, 
 extern "C" int ds_stencil9(const float* taps, int ldt, float bias, float* out, int B, int H, int W,
                            ds_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    DS_CHECK_ARG(taps && out && ldt >= 9, "bad arguments");
+    DS_CHECK_ARG(taps && out && ldt >= 9 && B > 0 && H > 0 && W > 0, "bad arguments");
     hipLaunchKernelGGL(ds_stencil9_kernel, dim3((B * H * W + 255) / 256), dim3(256), 0, stream, taps, ldt, bias, out,
                        B, H, W);
     DS_CHECK_LAUNCH();
@@ -274,7 +315,8 @@ extern "C" int ds_stencil9(const float* taps, int ldt, float bias, float* out, i
 extern "C" int ds_stencil7_tanh(const float* taps, int ldt, float bias, float* out, int B, int N,
                                 ds_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    DS_CHECK_ARG(taps && out && ldt >= 7, "bad arguments");
+    DS_CHECK_ARG(taps && out && ldt >= 7 && B > 0, "bad arguments");
+    DS_CHECK_ARG(N >= 4, "N must be at least 4 (ReflectionPad1d(3) reflects once)");
     hipLaunchKernelGGL(ds_stencil7_tanh_kernel, dim3((B * N + 255) / 256), dim3(256), 0, stream, taps, ldt, bias, out,
                        B, N);
     DS_CHECK_LAUNCH();
@@ -284,7 +326,7 @@ extern "C" int ds_stencil7_tanh(const float* taps, int ldt, float bias, float* o
 extern "C" int ds_mel_to_cl(const float* mel, float* out, int B, int C, int T, int Cpad, float a, float b,
                             ds_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    DS_CHECK_ARG(mel && out && Cpad >= C, "bad arguments");
+    DS_CHECK_ARG(mel && out && B > 0 && C > 0 && T > 0 && Cpad >= C, "bad arguments");
     hipLaunchKernelGGL(ds_mel_to_cl_kernel, dim3((B * T * Cpad + 255) / 256), dim3(256), 0, stream, mel, out, B, C, T,
                        Cpad, a, b);
     DS_CHECK_LAUNCH();

@@ -127,8 +127,12 @@ __global__ __launch_bounds__(256) void ds_layernorm_kernel(const float* __restri
 // A block reduces GN_PCHUNK pixels x C channels: thread = (pixel lane, 4 consecutive channels as one float4); the pixel lanes
 // of a channel quad are added up through LDS.  (The first version gave a thread ONE channel and walked the 256 pixels in a
 // dependent load -> double-add chain: 126-260 us per call on tensors that take 1-2 us to read.)  C % 4 == 0, C <= 1024.
+// The sums are of x - pivot, pivot = the sample's first pixel in the first channel of the channel's group (cpg channels per
+// group): E[x^2] - mean^2 loses (mean / std)^2 of the sums' relative error, and sums of 4e8-sized squares carry enough of it,
+// even in double, to put rstd 1.7 x 2^-22 off (measured) at means of 0.7e4 .. 1.4e4 standard deviations (C = 1024: 256
+// sequential adds per thread).  The variance does not see the pivot; ds_gn_finish_kernel adds it back to the mean.
 __global__ __launch_bounds__(256) void ds_gn_partial_kernel(const float* __restrict__ x, double* __restrict__ part,
-                                                            int P, int C) {
+                                                            int P, int C, int cpg) {
     // part[b][chunk][2][C]
     __shared__ double red[256][8];
     const int b = blockIdx.y, chunk = blockIdx.x, nchunk = gridDim.x;
@@ -143,11 +147,14 @@ __global__ __launch_bounds__(256) void ds_gn_partial_kernel(const float* __restr
         const int pl = (int)threadIdx.x / (quads < 256 ? quads : 256);
         double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
         if (qd < quads && pl < lanes) {
+            double pv[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pv[e] = (double)xb[(qd * 4 + e) / cpg * cpg];
             for (int p = p0 + pl; p < p1; p += lanes) {
                 const f32x4 v = *(const f32x4*)(xb + (size_t)p * C + qd * 4);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const double d = (double)v[e];
+                    const double d = (double)v[e] - pv[e];
                     s[e] += d;
                     q[e] += d * d;
                 }
@@ -173,10 +180,12 @@ __global__ __launch_bounds__(256) void ds_gn_partial_kernel(const float* __restr
 // grid (groups, B): one block per (sample, group) adds that group's partial sums over the chunks (fixed order: thread t
 // takes items t, t + 256, ..., then a tree over the block) and writes the group's channels.  (Rounds 1-3 ran ONE block per
 // sample over all groups -- 48 us per call once ds_conv3x3_f16x2 hands over 540 tile partials per sample.)
+// pivot_x: the tensor whose sums of x - pivot ds_gn_partial_kernel took, or null for plain sums (the convolutions' partials).
 __global__ __launch_bounds__(256) void ds_gn_finish_kernel(const double* __restrict__ part, int nchunk, int P, int C,
                                                            int groups, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, float eps,
-                                                           float* __restrict__ scale, float* __restrict__ shift) {
+                                                           float* __restrict__ scale, float* __restrict__ shift,
+                                                           const float* __restrict__ pivot_x) {
     __shared__ double rs[256], rq[256];
     const int g = blockIdx.x, b = blockIdx.y;
     const int cpg = C / groups;
@@ -198,9 +207,10 @@ __global__ __launch_bounds__(256) void ds_gn_finish_kernel(const double* __restr
         __syncthreads();
     }
     const double n = (double)P * cpg;
-    const double mean = rs[0] / n;
-    double var = rq[0] / n - mean * mean;
+    const double ms = rs[0] / n;                    // mean of x - pivot
+    double var = rq[0] / n - ms * ms;
     if (var < 0.0) var = 0.0;
+    const double mean = pivot_x ? (double)pivot_x[(size_t)b * P * C + g * cpg] + ms : ms;
     const double rstd = 1.0 / sqrt(var + (double)eps);
     for (int c = g * cpg + threadIdx.x; c < (g + 1) * cpg; c += 256) {
         const double ga = gamma[c], be = beta[c];
@@ -260,13 +270,14 @@ extern "C" int ds_groupnorm_stats(const float* x, int B, int P, int C, int group
                                   ds_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     DS_CHECK_ARG(x && gamma && beta && work && scale && shift, "null pointer");
+    DS_CHECK_ARG(B > 0 && P > 0 && C > 0, "sizes must be positive");
     DS_CHECK_ARG(groups > 0 && groups <= 64 && C % groups == 0, "bad group count");
     DS_CHECK_ARG(C % 4 == 0 && C <= 1024 && ((uintptr_t)x & 15) == 0, "C % 4 == 0, C <= 1024, 16-byte aligned x");
     const int nchunk = (P + GN_PCHUNK - 1) / GN_PCHUNK;
-    hipLaunchKernelGGL(ds_gn_partial_kernel, dim3(nchunk, B), dim3(256), 0, stream, x, work, P, C);
+    hipLaunchKernelGGL(ds_gn_partial_kernel, dim3(nchunk, B), dim3(256), 0, stream, x, work, P, C, C / groups);
     DS_CHECK_LAUNCH();
     hipLaunchKernelGGL(ds_gn_finish_kernel, dim3(groups, B), dim3(256), 0, stream, work, nchunk, P, C, groups, gamma, beta,
-                       eps, scale, shift);
+                       eps, scale, shift, x);
     DS_CHECK_LAUNCH();
     return 0;
 }
@@ -277,9 +288,9 @@ extern "C" int ds_groupnorm_finish(const double* part, int B, int nchunk, int P,
                                    const float* beta, float eps, float* scale, float* shift, ds_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     DS_CHECK_ARG(part && gamma && beta && scale && shift, "null pointer");
-    DS_CHECK_ARG(B > 0 && nchunk > 0 && P > 0 && groups > 0 && groups <= 64 && C % groups == 0, "bad shape / group count");
+    DS_CHECK_ARG(B > 0 && nchunk > 0 && P > 0 && C > 0 && groups > 0 && groups <= 64 && C % groups == 0, "bad shape / group count");
     hipLaunchKernelGGL(ds_gn_finish_kernel, dim3(groups, B), dim3(256), 0, stream, part, nchunk, P, C, groups, gamma, beta, eps,
-                       scale, shift);
+                       scale, shift, (const float*)nullptr);
     DS_CHECK_LAUNCH();
     return 0;
 }
