@@ -831,6 +831,44 @@ int ds_level_gain(const double* seg, int n_seg_max, int B, int T, const int32_t*
                   const double* target_dev, int target_n, double ceiling_db, const void* scratch, int64_t scratch_bytes,
                   double* lufs, float* peaks, double* mean_sq, int32_t* counts, float* gain, ds_stream_t stream);
 int ds_level_apply(const float* x, const float* gain, float* out, int B, int T, const int32_t* lengths, ds_stream_t stream);
+/* A look-ahead true-peak limiter behind the levelling gain (csrc/limiter.hip): where gain[b] = g0 would lift the x4 true peak of
+ * row b above c = 10^(ceiling_db/20), a gain curve takes the row down around its peaks and leaves the rest at g0 -- instead of
+ * the static cut of ds_level_gain, which turns the whole row down.  x, lengths, T and taps as for ds_level_true_peak; gain f32[B]
+ * on the device (never read on the host).  L = the look-ahead in samples, 1 <= L <= ds_limit_block() = N; a in [0, 1) the release
+ * coefficient per sample, exp(-1000 / (release_ms fs)); w f64[L + 1] on the device, non-negative, sum 1 (audio.limit_plan: a
+ * Hann shape).  Per row, n = len_b, y4 the x4 signal ds_level_true_peak forms (same taps, fp32 fma over j ascending):
+ *   e[i] = max(|x[i]|, |y4[4i + p]|, p = 0..3)                                  fp32
+ *   d[i] = max(0, 1 - fl32(c) / (|g0| e[i])),  0 where g0 e[i] = 0, for i < 0 and for i >= n     fp32
+ *   m[i] = max d[i .. i + L],  -L <= i < n                                      the hold: a peak is seen L samples ahead
+ *   h[i] = max(m[i], a h[i-1]),  h[-L-1] = 0                                    float64: exponential release
+ *   s[i] = sum_{k = 0..L} w[k] h[i-k]                                           float64 fma over k ascending; s[i] >= d[i]
+ *   g[i] = fl32(1 - s[i]),   out[b][i] = fl32(fl32(g0 g[i]) x[b][i]) for i < n, 0 for n <= i < T;   curve[b][i] = g[i], 1 past n
+ * h is evaluated as max(H[i], max d[i+1 .. i+L]) with H[i] = max(d[i], a H[i-1]); a stretch of n' samples acts on H as
+ * H -> max(a^n' H, M), so ds_limit_envelope leaves d and M of every block of N samples (cut at k N - L), ds_limit_carry walks
+ * H over a row's blocks with one wave (a^N by squaring), and ds_limit_apply runs each block again from its true start state.
+ * curve (may be NULL) f32[B][T].  ds_limit_apply also leaves each block's minimum of g in the scratch buffer.  The entries run in
+ * this order on one stream, with the same B, T, L, a and scratch (ds_limit_scratch_bytes(B, T, L) bytes, 8-byte aligned; it
+ * holds d f32[B][T]).  A time-varying gain does not commute with the x4 interpolation, so `out` is then measured again
+ * (ds_level_segments, ds_level_true_peak, ds_level_gain with DS_LEVEL_MEASURE: lufs_in f64[B], peaks f32[B][2]) and
+ * ds_limit_finish forms, per row,  tp = peaks[b][1],  trim t = 1 where tp <= c, else fl32((c / tp)(1 - 2^-15)), one fp32 step
+ * further down where the rounding lifted t tp above c (1 - 2^-15);  lufs = lufs_in + 20 log10 t;  true_peak = t tp rounded
+ * towards zero;  max_reduction = 1 - min_i g[i].  ds_level_apply(out, trim, out) then applies t in place.  The margin 2^-15
+ * covers what rounding the scaled samples and their 69 fmas can add to an x4 output (csrc/limiter.hip), so the x4 true peak
+ * of the stored row, measured by ds_level_true_peak, is <= c.  No entry allocates or synchronises; 16-byte accesses where
+ * T % 4 == 0 and x, out and curve are 16-byte aligned; a row's every result is bit-identical whatever the batch, its position in
+ * it, T and the launch.  Bad arguments (a null pointer, L outside 1..N, a outside [0, 1), a ceiling that is not finite, a
+ * scratch that is too small) return -1 and launch nothing. */
+int ds_limit_block(void);
+int64_t ds_limit_scratch_bytes(int B, int T, int L);
+int ds_limit_envelope(const float* x, int B, int T, const int32_t* lengths, const float* taps, const float* gain,
+                      double ceiling_db, int L, double a, void* scratch, int64_t scratch_bytes, ds_stream_t stream);
+int ds_limit_carry(int B, int T, const int32_t* lengths, int L, double a, void* scratch, int64_t scratch_bytes,
+                   ds_stream_t stream);
+int ds_limit_apply(const float* x, int B, int T, const int32_t* lengths, const float* gain, int L, double a, const double* w,
+                   float* out, float* curve, void* scratch, int64_t scratch_bytes, ds_stream_t stream);
+int ds_limit_finish(int B, int T, int L, double ceiling_db, const double* lufs_in, const float* peaks, const void* scratch,
+                    int64_t scratch_bytes, float* trim, double* lufs, float* true_peak, float* max_reduction,
+                    ds_stream_t stream);
 /* Pasting a recording back over a rendering of it (csrc/paste.hip): outside the regenerated columns the recording's own values
  * replace the rendering's, cross-faded inside the regenerated columns, with one gain per clip on the rendering.
  * ren / out f32[B C][T] (rows of clip b: b C .. b C + C - 1; C = 1 for waveforms, the mel channels for mel images), rec f32[B C][Tr];

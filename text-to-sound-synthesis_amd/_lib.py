@@ -198,6 +198,12 @@ _PROTOS = {
     "ds_level_gain": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_double, _vp, C.c_int, C.c_double,
                                 _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ds_level_apply": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "ds_limit_block": (C.c_int, []),
+    "ds_limit_scratch_bytes": (_i64, [C.c_int, C.c_int, C.c_int]),
+    "ds_limit_envelope": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, C.c_int, C.c_double, _vp, _i64, _vp]),
+    "ds_limit_carry": (C.c_int, [C.c_int, C.c_int, _vp, C.c_int, C.c_double, _vp, _i64, _vp]),
+    "ds_limit_apply": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ds_limit_finish": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ds_paste_scratch_bytes": (_i64, [C.c_int, C.c_int]),
     "ds_paste_sums": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _i64, _i64, _vp, _i64, _vp, _vp]),
     "ds_paste": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _i64, _i64, C.c_double,

@@ -3,6 +3,7 @@ launcher of the kernel (csrc/stft_mel.hip) that `modeling.vocoder.Audio2Mel` and
 polyphase table of `ds_resample` (csrc/resample.hip) and its launcher: audio at any integer sample rate in and out; the
 cross-fade table of `ds_mel_stitch` (csrc/misc.hip) and its launcher: window mels joined into one long mel; the K-weighting
 coefficients and segment plan of the `ds_level_*` entries (csrc/loudness.hip) and their launchers: loudness, true peak, gain;
+the plan and the launchers of the `ds_limit_*` entries (csrc/limiter.hip): a look-ahead true-peak limiter behind that gain;
 the launchers of `ds_paste_sums` / `ds_paste` (csrc/paste.hip): a recording pasted back over a rendering of it.
 
 The reference extracts mels with librosa on the host (Diffsound/vocoder/mel2wav/extract_mel_spectrogram.py:15-38,141-187)
@@ -305,7 +306,7 @@ def _level_run(wave, rate, lengths, strategy, target, target_dev, ceiling_db, co
                                _lib.ptr(scratch), nbytes, _lib.ptr(lufs), _lib.ptr(peaks), _lib.ptr(mean_sq), _lib.ptr(cnt),
                                _lib.ptr(gain), st))
     out = {"lufs": lufs, "sample_peak": peaks[:, 0], "true_peak": peaks[:, 1], "rms": mean_sq.sqrt(), "gain": gain,
-           "seg": seg[:, :n_seg_max]}
+           "seg": seg[:, :n_seg_max], "peaks": peaks}
     if counts:
         out["gate_counts"] = cnt
     return out
@@ -327,7 +328,7 @@ def measure_level(wave, rate, lengths=None, segments=False):
     return {k: r[k] for k in keys}
 
 
-def level(wave, rate, strategy, target=None, ceiling_db=-1.0, lengths=None, reference=None):
+def level(wave, rate, strategy, target=None, ceiling_db=-1.0, lengths=None, reference=None, limit=None):
     """Bring wave f32[B, T] (device, `rate` Hz; lengths as in measure_level) to a level -> (out f32[B, T], gain f32[B]):
     one gain per row, out = gain x in fp32, exact zeros past a row's length.  strategy "peak": the sample peak to `target`
     dBFS (default -1); "rms": the root mean square to `target` dBFS (-20); "loudness": the integrated loudness to `target`
@@ -336,8 +337,14 @@ def level(wave, rate, strategy, target=None, ceiling_db=-1.0, lengths=None, refe
     Then the ceiling: a gain that would lift the x4 true peak above ceiling_db dBFS is cut to reach exactly that -- a static
     cut of the whole row, its shape untouched.  A silent row, and under "loudness" / "match" a row shorter than 0.4 s, has
     nothing to scale by and keeps gain 1; where the lengths are known on the host such a short row raises ValueError instead.
-    Everything stays on the device and nothing synchronises."""
+    limit=True, or a dict {lookahead_ms, release_ms}: the strategy's gain is NOT cut; it goes to the look-ahead limiter
+    (`limit`, same ceiling_db), which takes the row down around the peaks that would cross the ceiling and leaves the rest at
+    the gain asked for.  The returned gain is then that uncut gain g0.  Limiting lowers loudness, so a limited clip lands under
+    its target by what was limited; `limit` reports the loudness reached, and nothing iterates towards the target.
+    limit=None: the static cut, the launches and the bits of before.  Everything stays on the device and nothing synchronises."""
     rate = _level_rate(rate)
+    limit = _limit_spec(limit)
+    plan = None if limit is None else limit_plan(rate, **limit)     # raises on a look-ahead or a release this rate cannot take
     if strategy not in LEVEL_STRATEGIES:
         raise ValueError("strategy must be one of %s, got %r" % (", ".join(sorted(LEVEL_STRATEGIES)), strategy))
     if (strategy == "match") != (reference is not None):
@@ -374,11 +381,130 @@ def level(wave, rate, strategy, target=None, ceiling_db=-1.0, lengths=None, refe
         if target_dev.numel() not in (1, wave.shape[0]):
             raise ValueError("the reference holds %d rows for %d clips" % (target_dev.numel(), wave.shape[0]))
     code = {"peak": _lib.LEVEL_PEAK, "rms": _lib.LEVEL_RMS, "loudness": _lib.LEVEL_LOUDNESS, "match": _lib.LEVEL_LOUDNESS}[strategy]
+    if plan is not None:                                 # the gain as the strategy gives it: no ceiling is in its way
+        r = _level_run(wave, rate, lengths, code, 0.0 if target is None else target, target_dev, _NO_CEILING_DB)
+        out, _ = _limit_run(wave, rate, lengths, r["gain"], ceiling_db, plan, False)
+        return out, r["gain"]
     r = _level_run(wave, rate, lengths, code, 0.0 if target is None else target, target_dev, ceiling_db)
     out = torch.empty_like(wave)
     _lib.check(_lib.lib().ds_level_apply(_lib.ptr(wave), _lib.ptr(r["gain"]), _lib.ptr(out), wave.shape[0], wave.shape[1],
                                          _lib.ptr(lengths), _lib.stream()))
     return out, r["gain"]
+
+
+# ---- the look-ahead true-peak limiter behind a levelling gain (csrc/limiter.hip) ---------------------------------------------
+LIMIT_LOOKAHEAD_MS = 1.5
+LIMIT_RELEASE_MS = 50.0
+LIMIT_BLOCK = 1024             # = ds_limit_block(), checked where the library is used: the look-ahead may not exceed it
+_NO_CEILING_DB = 1000.0        # a ceiling no fp32 gain times an fp32 peak reaches: ds_level_gain then returns the strategy's own gain
+
+
+def limit_plan(rate, lookahead_ms=LIMIT_LOOKAHEAD_MS, release_ms=LIMIT_RELEASE_MS):
+    """{"L": look-ahead in samples = round(lookahead_ms rate / 1000), 1 <= L <= 0.01 rate; "a": the release coefficient per
+    sample exp(-1000 / (release_ms rate)), float64; "w": f64[L + 1], the smoothing weights -- a Hann shape without its zero
+    ends (np.hanning(L + 3)[1:-1]), normalised to sum 1} (include/diffsound_hip.h: ds_limit_envelope).  The kernels' block
+    holds ds_limit_block() = 1024 samples and L may not exceed it: up to 10 ms at 102 400 Hz."""
+    rate = _level_rate(rate)
+    lookahead_ms, release_ms = float(lookahead_ms), float(release_ms)
+    if not (math.isfinite(lookahead_ms) and lookahead_ms > 0.0):
+        raise ValueError("lookahead_ms must be positive and finite, got %r" % (lookahead_ms,))
+    if not (math.isfinite(release_ms) and release_ms > 0.0):
+        raise ValueError("release_ms must be positive and finite, got %r" % (release_ms,))
+    L = int(math.floor(lookahead_ms * rate / 1000.0 + 0.5))
+    if L < 1 or L > 0.01 * rate:
+        raise ValueError("the look-ahead of %g ms is %d samples at %d Hz; it must be 1 .. %d" % (lookahead_ms, L, rate, int(0.01 * rate)))
+    if L > LIMIT_BLOCK:
+        raise ValueError("the look-ahead of %d samples exceeds the limiter's block of %d" % (L, LIMIT_BLOCK))
+    a = math.exp(-1000.0 / (release_ms * rate))
+    if not a < 1.0:
+        raise ValueError("release_ms = %g does not release at %d Hz" % (release_ms, rate))
+    w = np.hanning(L + 3)[1:-1].astype(np.float64)
+    return {"L": L, "a": a, "w": w / w.sum()}
+
+
+_LIMIT_TABLES = {}
+
+
+def _limit_spec(limit):
+    """level's `limit` keyword -> None or the keyword arguments of limit_plan"""
+    if limit is None or limit is False:
+        return None
+    if limit is True:
+        return {}
+    if not isinstance(limit, dict) or set(limit) - {"lookahead_ms", "release_ms"}:
+        raise ValueError("limit is None, True or a dict {lookahead_ms, release_ms}, got %r" % (limit,))
+    return {k: float(v) for k, v in limit.items()}
+
+
+def _limit_run(wave, rate, lengths, gain, ceiling_db, plan, return_curve):
+    """the limiter's launches on rows already checked -> (out, info)"""
+    B, T = wave.shape
+    dev = wave.device
+    lib = _lib.lib()
+    if int(lib.ds_limit_block()) != LIMIT_BLOCK:
+        raise RuntimeError("libdiffsound_hip's limiter block is %d, audio.LIMIT_BLOCK is %d" % (lib.ds_limit_block(), LIMIT_BLOCK))
+    S, kw, taps = _level_tables(rate, dev)
+    L, a = plan["L"], plan["a"]
+    key = (rate, L, dev.type, dev.index)
+    if key not in _LIMIT_TABLES:
+        _LIMIT_TABLES[key] = torch.from_numpy(np.ascontiguousarray(plan["w"])).to(dev)
+    w = _LIMIT_TABLES[key]
+    nbytes = int(lib.ds_limit_scratch_bytes(B, T, L))
+    scratch = torch.empty(nbytes // 8 + 1, device=dev, dtype=torch.float64)
+    out = torch.empty_like(wave)
+    curve = torch.empty_like(wave) if return_curve else None
+    st = _lib.stream()
+    _lib.check(lib.ds_limit_envelope(_lib.ptr(wave), B, T, _lib.ptr(lengths), _lib.ptr(taps), _lib.ptr(gain), ceiling_db, L, a,
+                                     _lib.ptr(scratch), nbytes, st))
+    _lib.check(lib.ds_limit_carry(B, T, _lib.ptr(lengths), L, a, _lib.ptr(scratch), nbytes, st))
+    _lib.check(lib.ds_limit_apply(_lib.ptr(wave), B, T, _lib.ptr(lengths), _lib.ptr(gain), L, a, _lib.ptr(w), _lib.ptr(out),
+                                  _lib.ptr(curve), _lib.ptr(scratch), nbytes, st))
+    m = _level_run(out, rate, lengths, _lib.LEVEL_MEASURE, 0.0, None, 0.0)          # a varying gain moves the x4 peaks: measure again
+    trim = torch.empty(B, device=dev, dtype=torch.float32)
+    true_peak, max_red = torch.empty_like(trim), torch.empty_like(trim)
+    lufs = torch.empty(B, device=dev, dtype=torch.float64)
+    _lib.check(lib.ds_limit_finish(B, T, L, ceiling_db, _lib.ptr(m["lufs"]), _lib.ptr(m["peaks"]), _lib.ptr(scratch), nbytes,
+                                   _lib.ptr(trim), _lib.ptr(lufs), _lib.ptr(true_peak), _lib.ptr(max_red), st))
+    _lib.check(lib.ds_level_apply(_lib.ptr(out), _lib.ptr(trim), _lib.ptr(out), B, T, _lib.ptr(lengths), st))
+    info = {"gain": gain, "trim": trim, "max_reduction": max_red, "lufs": lufs, "true_peak": true_peak}
+    if return_curve:
+        info["curve"] = curve
+    return out, info
+
+
+def limit(wave, rate, ceiling_db=-1.0, gain=None, lookahead_ms=LIMIT_LOOKAHEAD_MS, release_ms=LIMIT_RELEASE_MS, lengths=None,
+          return_curve=False):
+    """A look-ahead true-peak limiter on wave f32[B, T] (device, `rate` Hz; lengths as in measure_level) -> (out f32[B, T], info).
+    gain: f32[B] on the device, the gain g0 each row is to get (None: 1).  Where g0 would lift the x4 true peak above
+    ceiling_db dBFS, a gain curve g <= 1 -- the reduction every peak asks for, seen lookahead_ms ahead, held, released
+    exponentially over release_ms and smoothed by a Hann shape over the look-ahead -- takes the row down around those peaks:
+    out = (g0 g) x in fp32, exact zeros past a row's length (include/diffsound_hip.h: ds_limit_envelope has the formulas).
+    `out` is then measured again and cut statically by `trim` <= 1 (1 where nothing is left above the ceiling), so its x4 true
+    peak and its sample peak are at or under the ceiling.  info holds device tensors: 'gain' f32[B] = g0, 'trim' f32[B],
+    'max_reduction' f32[B] = 1 - min g, 'lufs' f64[B] and 'true_peak' f32[B] of `out` as returned, and with return_curve
+    'curve' f32[B, T] = g (1 past a row's length).  Limiting lowers loudness: a row limited after a loudness gain lands under
+    that target by what was limited -- 'lufs' reports where, nothing iterates.  Eight entries, no host synchronisation; a row
+    that needs no limiting comes out as ds_level_apply would give it, bit for bit.  A host tensor raises."""
+    rate = _level_rate(rate)
+    ceiling_db = float(ceiling_db)
+    if not math.isfinite(ceiling_db):
+        raise ValueError("ceiling_db must be finite")
+    plan = limit_plan(rate, lookahead_ms, release_ms)
+    wave, lengths, _ = _level_rows(wave, lengths)
+    B, T = wave.shape
+    if B == 0 or T == 0:
+        raise ValueError("wave holds no rows or no samples")
+    if gain is None:
+        gain = torch.ones(B, device=wave.device, dtype=torch.float32)
+    else:
+        if not torch.is_tensor(gain):
+            raise ValueError("gain must be a tensor f32[B] on the device")
+        if not gain.is_cuda:
+            raise _lib.DiffsoundHipError("gain is not on a GPU: the HIP path has no CPU fallback")
+        gain = gain.float().reshape(-1).contiguous()
+        if gain.shape != (B,):
+            raise ValueError("gain must hold one value per row")
+    return _limit_run(wave, rate, lengths, gain, ceiling_db, plan, bool(return_curve))
 
 
 def fade_table(V):

@@ -211,14 +211,16 @@ def purity_sample_type(sample_type, purity_steps, purity_weight=0.0):
 
 def level_spec(level, takes_recording):
     """The drivers' `level` keyword -> None or {"strategy", "target", "ceiling_db"}: a strategy name of audio.level ("peak",
-    "rms", "loudness", "match") or a dict {strategy[, target][, ceiling_db]}.  "match" -- the result takes the loudness of the
-    recording the driver was given -- only where there is one (takes_recording).  Anything else raises ValueError."""
+    "rms", "loudness", "match") or a dict {strategy[, target][, ceiling_db][, limit]}.  "match" -- the result takes the loudness
+    of the recording the driver was given -- only where there is one (takes_recording).  limit (True, or a dict {lookahead_ms,
+    release_ms}; audio.level) puts the look-ahead limiter in place of the static cut under the ceiling; the returned dict
+    carries the key only where the caller gave it.  Anything else raises ValueError."""
     from . import audio
     if level is None:
         return None
     spec = {"strategy": level} if isinstance(level, str) else level
-    if not isinstance(spec, dict) or "strategy" not in spec or set(spec) - {"strategy", "target", "ceiling_db"}:
-        raise ValueError("level is a strategy name or a dict {strategy, target, ceiling_db}, got %r" % (level,))
+    if not isinstance(spec, dict) or "strategy" not in spec or set(spec) - {"strategy", "target", "ceiling_db", "limit"}:
+        raise ValueError("level is a strategy name or a dict {strategy, target, ceiling_db, limit}, got %r" % (level,))
     strategy, target = spec["strategy"], spec.get("target")
     if strategy not in audio.LEVEL_STRATEGIES:
         raise ValueError("level: strategy must be one of %s, got %r" % (", ".join(sorted(audio.LEVEL_STRATEGIES)), strategy))
@@ -226,8 +228,12 @@ def level_spec(level, takes_recording):
         raise ValueError('level="match" needs a recording to match: this driver takes none')
     if strategy == "match" and target is not None:
         raise ValueError('level="match" takes its target from the recording')
-    return {"strategy": strategy, "target": None if target is None else float(target),
-            "ceiling_db": float(spec.get("ceiling_db", -1.0))}
+    out = {"strategy": strategy, "target": None if target is None else float(target),
+           "ceiling_db": float(spec.get("ceiling_db", -1.0))}
+    if "limit" in spec:
+        audio._limit_spec(spec["limit"])                 # its form is checked here, before anything runs
+        out["limit"] = spec["limit"]
+    return out
 
 
 def recording_loudness(item, rate=None, device="cuda"):
@@ -461,9 +467,10 @@ class Diffsound:
         sharpening weight; None: today's path, untouched.  Not together with fast.  Its effect on audio quality is unmeasured.
         level= (keyword-only, on this and every driver that returns or writes a waveform; _levelled, level_spec): bring every
         clip to a level on the device, at the output rate -- "peak" (-1 dBFS), "rms" (-20 dBFS), "loudness" (-23 LUFS, BS.1770-4)
-        or a dict {strategy, target, ceiling_db}, under a true-peak ceiling of -1 dBFS (audio.level); the drivers that take a
-        recording also accept "match": the recording's own loudness.  None: the vocoder's own level, no launch.  Mel and tokens
-        are never affected; generate_best_of levels the winners only."""
+        or a dict {strategy, target, ceiling_db, limit}, under a true-peak ceiling of -1 dBFS (audio.level: a static cut, or
+        with limit=True the look-ahead limiter); the drivers that take a recording also accept "match": the recording's own
+        loudness.  None: the vocoder's own level, no launch.  Mel and tokens are never affected; generate_best_of levels the
+        winners only."""
         if isinstance(cond, (list, tuple, str)):
             batch = {"text": [cond] if isinstance(cond, str) else list(cond)}
         elif cond.dtype == torch.long:
@@ -540,7 +547,7 @@ class Diffsound:
         rate = VOCODER_RATE if sample_rate is None else int(sample_rate)
         ref = recording_loudness(recording[0], recording[1], wave.device) if spec["strategy"] == "match" else None
         out, _ = audio.level(wave[:, 0], rate, spec["strategy"], target=spec["target"], ceiling_db=spec["ceiling_db"],
-                             reference=ref)
+                             reference=ref, limit=spec.get("limit"))
         return out[:, None]
 
     @_levelled(True)
