@@ -247,6 +247,7 @@ extern "C" int ds_adaln(const float* x, float* y, int M, int L, int D, const flo
     hipStream_t stream = (hipStream_t)stream_;
     DS_CHECK_ARG(x && y && table && t, "null pointer");
     DS_CHECK_ARG(D == 1024, "only D = 1024 is built");
+    DS_CHECK_ARG(M > 0 && L > 0, "M and L must be positive");
     hipLaunchKernelGGL((ds_layernorm_kernel<1024>), dim3((M + 3) / 4), dim3(256), 0, stream, x, y, M, L, 0, table,
                        t, (const float*)nullptr, (const float*)nullptr, 1e-5f, 0);
     DS_CHECK_LAUNCH();
@@ -258,6 +259,7 @@ extern "C" int ds_layernorm(const float* x, float* y, int M, int D, const float*
     hipStream_t stream = (hipStream_t)stream_;
     DS_CHECK_ARG(x && y && gamma && beta, "null pointer");
     DS_CHECK_ARG(D == 1024, "only D = 1024 is built");
+    DS_CHECK_ARG(M > 0, "M must be positive");
     hipLaunchKernelGGL((ds_layernorm_kernel<1024>), dim3((M + 3) / 4), dim3(256), 0, stream, x, y, M, 1, 1,
                        (const float*)nullptr, (const int64_t*)nullptr, gamma, beta, 1e-5f, 0);
     DS_CHECK_LAUNCH();
@@ -353,6 +355,7 @@ extern "C" int ds_adaln_split(const float* x, void* yh, int M, int L, int D, con
     hipStream_t stream = (hipStream_t)stream_;
     DS_CHECK_ARG(x && yh && table && t, "null pointer");
     DS_CHECK_ARG(D == 1024, "only D = 1024 is built");
+    DS_CHECK_ARG(M > 0 && L > 0, "M and L must be positive");
     hipLaunchKernelGGL((ds_layernorm_kernel<1024>), dim3((M + 3) / 4), dim3(256), 0, stream, x, (float*)yh, M, L, 0,
                        table, t, (const float*)nullptr, (const float*)nullptr, 1e-5f, 2);
     DS_CHECK_LAUNCH();
@@ -364,6 +367,7 @@ extern "C" int ds_layernorm_split(const float* x, void* yh, int M, int D, const 
     hipStream_t stream = (hipStream_t)stream_;
     DS_CHECK_ARG(x && yh && gamma && beta, "null pointer");
     DS_CHECK_ARG(D == 1024, "only D = 1024 is built");
+    DS_CHECK_ARG(M > 0, "M must be positive");
     hipLaunchKernelGGL((ds_layernorm_kernel<1024>), dim3((M + 3) / 4), dim3(256), 0, stream, x, (float*)yh, M, 1, 1,
                        (const float*)nullptr, (const int64_t*)nullptr, gamma, beta, 1e-5f, 2);
     DS_CHECK_LAUNCH();
