@@ -246,6 +246,39 @@ int ds_sample_tail_guided_rng(const float* logits_c, const float* logits_u, cons
                               int64_t* out_tokens, int B, int L, int K, int T, int initial, float trunc_r, int trunc_k,
                               float scale, const unsigned char* keep, const int64_t* known, int mode, ds_stream_t stream);
 
+/* Joint-window sampling in the tail: the W windows of a long clip live on one token CANVAS and a position that two windows
+ * cover is drawn once, from the fusion of their predictions (the discrete counterpart of MultiDiffusion, Bar-Tal et al. 2023).
+ * Geometry: R = 5 grid rows, G = 53 grid columns, n = overlap_cols in 1 .. 26, hop h = G - n; the canvas has C columns --
+ * line (ring == 0): C = G + (W - 1) h, W >= 1; ring: C = W h, W >= 2, window w covering columns (w h + o) mod C -- and
+ * Lc = R C positions q = R c + r, time-major.  For column c the later window is w1 = min(c / h, W - 1) (ring: c / h) at offset
+ * o1 = c - w1 h; if o1 < n and (w1 >= 1 or ring) the earlier window w0 = (w1 - 1) mod W covers it too, at offset o1 + h.
+ *   logits / logits_u  f32[B W lrows][K], row (b W + w) lrows + R o + r for offset o of window w; lrows >= R G;
+ *                      logits_u NULL: unguided, else the null condition's rows and `scale` as in ds_sample_tail_guided
+ *   canvas / out_canvas / keep / known  [B][Lc];  t i64[B];  u f32[B][K+1][Lc], or gids i64[B] (Philox position q)
+ *   fade               f32[n] on the device: the later window's weight at overlap offset o1, in (0, 1)
+ * One wave per canvas position.  Under one window it is the plain (or guided) tail on that window's row.  Under two, l0 / l1 =
+ * the log_pred the plain (or guided) tail gives rows w0 / w1 (rounded to f32, clamped), and in float64
+ *     g = l0 + fade[o1] (l1 - l0),   g <- g - logsumexp(g)   (max-shifted),
+ * the guided expression with (lu, lc, scale) = (l0, l1, fade[o1]), rounded to f32 and clamped to [-70, 0], is the log_pred that
+ * truncation, posterior and Gumbel-argmax consume unchanged; the dbg_* dumps are f32[B][K+1][Lc].  keep / known: clamp mode
+ * only (mode 0), keep == NULL: unheld.  Rejected (-1, nothing launched): null pointers (fade included), W < 1, n outside
+ * 1 .. 26, a ring with W < 2, Lc >= 65536, lrows < R G, mode != 0, keep without known, both truncations, a non-finite scale
+ * with logits_u. */
+int ds_sample_tail_joint(const float* logits, const float* logits_u, const int64_t* canvas, const int64_t* t, const float* u,
+                         const float* sched, int64_t* out_canvas, float* dbg_log_pred, float* dbg_trunc, float* dbg_post,
+                         int B, int W, int overlap_cols, int ring, const float* fade, int lrows, int K, int T, int initial,
+                         float trunc_r, int trunc_k, float scale, const unsigned char* keep, const int64_t* known, int mode,
+                         ds_stream_t stream);
+int ds_sample_tail_joint_rng(const float* logits, const float* logits_u, const int64_t* canvas, const int64_t* t,
+                             const int64_t* gids, unsigned long long seed, int call, const float* sched, int64_t* out_canvas,
+                             float* dbg_log_pred, float* dbg_trunc, float* dbg_post, int B, int W, int overlap_cols, int ring,
+                             const float* fade, int lrows, int K, int T, int initial, float trunc_r, int trunc_k, float scale,
+                             const unsigned char* keep, const int64_t* known, int mode, ds_stream_t stream);
+/* The window rows of a canvas, as the denoiser reads them: win[(k B W + b W + w)][R o + r] = canvas[b][R ((w h + o) mod C) + r]
+ * for k < copies (1 or 2), condition-major.  canvas i64[B][Lc], win i64[copies B W][265].  The geometry rules above. */
+int ds_joint_gather(const int64_t* canvas, int64_t* win, int B, int W, int overlap_cols, int ring, int copies,
+                    ds_stream_t stream);
+
 /* Caption tracks in the tail: several captions per clip, each weighted per grid position (the conjunction of Liu et al.,
  * "Compositional Visual Generation with Composable Diffusion Models", 2022, with weights that vary over the token grid;
  * guidance is its one-track, constant-weight case).  C = n_tracks, 1 <= C <= DS_MAX_TRACKS.
@@ -582,6 +615,31 @@ int ds_denoiser_sample_guided_rng(const ds_denoiser* h, int64_t* tokens, int64_t
                                   int n_calls, const float* kv, const int64_t* gids, unsigned long long seed, int call0,
                                   int B, int initial, float trunc_r, int trunc_k, float scale, const unsigned char* keep,
                                   const int64_t* known, int mode, int64_t* tokens2, void* workspace, ds_stream_t stream);
+
+/* Joint forms (see ds_sample_tail_joint) of the three guided entries: per step ds_joint_gather into tokensN, ONE forward at
+ * batch n_cond B W (n_cond 1: unguided, 2: guided at `scale`), the joint tail onto the canvas.
+ *   canvas_in / canvas_out / canvas / canvas_tmp / keep / known   [B][Lc]
+ *   tokensN    i64[n_cond B W][265] scratch
+ *   kv, workspace   at batch n_cond B W; kv: each clip's caption embedding W times (row b W + w), then the B W null ones
+ *   t, t_post  i64[n_cond B W], one entry per forward row; the posterior reads entry b W of its vector
+ *   t_steps    i64[n_calls][2][n_cond B W]
+ *   fade       f32[overlap_cols] on the device
+ * Every call is checked before the first is enqueued; the handle's seq_len must be 265. */
+int ds_denoiser_step_joint(const ds_denoiser* h, const int64_t* canvas_in, const int64_t* t, const int64_t* t_post,
+                           const float* kv, const float* u, int B, int W, int overlap_cols, int ring, int n_cond,
+                           const float* fade, int initial, float trunc_r, int trunc_k, float scale, const unsigned char* keep,
+                           const int64_t* known, int mode, int64_t* tokensN, void* workspace, int64_t* canvas_out,
+                           ds_stream_t stream);
+int ds_denoiser_step_joint_rng(const ds_denoiser* h, const int64_t* canvas_in, const int64_t* t, const int64_t* t_post,
+                               const float* kv, const int64_t* gids, unsigned long long seed, int call, int B, int W,
+                               int overlap_cols, int ring, int n_cond, const float* fade, int initial, float trunc_r,
+                               int trunc_k, float scale, const unsigned char* keep, const int64_t* known, int mode,
+                               int64_t* tokensN, void* workspace, int64_t* canvas_out, ds_stream_t stream);
+int ds_denoiser_sample_joint_rng(const ds_denoiser* h, int64_t* canvas, int64_t* canvas_tmp, const int64_t* t_steps,
+                                 int n_calls, const float* kv, const int64_t* gids, unsigned long long seed, int call0, int B,
+                                 int W, int overlap_cols, int ring, int n_cond, const float* fade, int initial, float trunc_r,
+                                 int trunc_k, float scale, const unsigned char* keep, const int64_t* known, int mode,
+                                 int64_t* tokensN, void* workspace, ds_stream_t stream);
 
 /* Composed forms (caption tracks, see ds_sample_tail_composed) of the three guided entries: one forward at batch (C+1)B,
  * C = n_tracks, and the composed tail on the C + 1 slabs of its logits.

@@ -225,7 +225,24 @@ _PROTOS_COMPOSED = {
     "ds_denoiser_sample_composed_rng": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_uint64, C.c_int, C.c_int, C.c_int,
                                                   _f, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
 }
-EXPORTED = tuple(_PROTOS) + tuple(_PROTOS_COMPOSED)
+# joint-window sampling (csrc/sampler.hip SampleJoint): the window gather, the joint tails and the joint step / chain entries
+_PROTOS_JOINT = {
+    "ds_joint_gather": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "ds_sample_tail_joint": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp,
+                                       C.c_int, C.c_int, C.c_int, C.c_int, _f, C.c_int, _f, _vp, _vp, C.c_int, _vp]),
+    "ds_sample_tail_joint_rng": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                                           C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _f, C.c_int, _f,
+                                           _vp, _vp, C.c_int, _vp]),
+    "ds_denoiser_step_joint": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int,
+                                         _f, C.c_int, _f, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "ds_denoiser_step_joint_rng": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_int, _vp, C.c_int, _f, C.c_int, _f, _vp, _vp, C.c_int, _vp, _vp, _vp,
+                                             _vp]),
+    "ds_denoiser_sample_joint_rng": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_uint64, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, C.c_int, C.c_int, _vp, C.c_int, _f, C.c_int, _f, _vp, _vp, C.c_int, _vp,
+                                               _vp, _vp]),
+}
+EXPORTED = tuple(_PROTOS) + tuple(_PROTOS_COMPOSED) + tuple(_PROTOS_JOINT)
 
 _lib = None
 
@@ -239,7 +256,7 @@ def lib():
                 "libdiffsound_hip.so is missing (%s). Build it with `python __graft_entry__.py` -- "
                 "there is no CPU or PyTorch fallback for the Diffsound HIP path." % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_PROTOS.items()) + list(_PROTOS_COMPOSED.items()):
+        for name, (res, args) in list(_PROTOS.items()) + list(_PROTOS_COMPOSED.items()) + list(_PROTOS_JOINT.items()):
             fn = getattr(L, name)   # AttributeError here == header/library mismatch
             fn.restype = res
             fn.argtypes = args

@@ -445,6 +445,9 @@ struct StepCall {
     // conditions per clip with tokens2: 2 guided; n_tracks + 1 composed (sampler.hip SampleCompose: tokens2 is
     // i64[n_cond B][seq_len], kv is track-major with the null condition last, and the tail reads n_cond slabs of the logits)
     int n_cond = 2;
+    // joint-window sampling (tail.joint; sampler.hip SampleJoint): tokens_in / tokens_out are canvases i64[B][tail.L], tokens2 is
+    // the gather's target i64[n_cond B W][seq_len] -- always given, n_cond 1 (unguided) or 2 -- the forward runs at batch
+    // n_cond B W, and the posterior reads entry b W of its timestep vector (one per window row, like the network's)
     bool zero_kv_pad = true;           // forward_impl: false in the later steps of a chain
 };
 
@@ -457,12 +460,14 @@ static int step_error(const StepCall& s, int rc, const char* what, const char* d
 // only.  The purity tail reads no timestep and no schedule table: t, sched and T stay zero.  Returns the rows per sample.
 static int aim_tail(const ds_denoiser* h, StepCall& s, Carve* w) {
     TailCall& c = s.tail;
-    const int Bf = s.tokens2 ? s.n_cond * c.B : c.B, Lp = rows_per_sample(h, Bf);
+    const int Bw = c.joint ? c.B * c.windows : c.B;      // rows of one condition
+    const int Bf = s.tokens2 ? s.n_cond * Bw : Bw, Lp = rows_per_sample(h, Bf);
     carve(h, Bf, s.workspace, w, Lp);
-    c.L = h->d.seq_len; c.K = h->d.n_codes;
+    if (!c.joint) c.L = h->d.seq_len;                    // (joint: the canvas length, set by the entry)
+    c.K = h->d.n_codes;
     c.logits = w->logits; c.logits_rows = Lp;
     const bool composed = c.weights != nullptr;
-    c.logits_u = s.tokens2 && !composed ? w->logits + (size_t)c.B * Lp * c.K : nullptr;
+    c.logits_u = s.tokens2 && !composed && !(c.joint && s.n_cond == 1) ? w->logits + (size_t)Bw * Lp * c.K : nullptr;
     c.track_stride = composed ? (size_t)c.B * Lp * c.K : 0;
     c.xt = s.tokens_in; c.out_tokens = s.tokens_out;
     if (c.kind == DS_TAIL_POSTERIOR) {
@@ -483,14 +488,19 @@ static int step_check(const ds_denoiser* h, StepCall s) {
 static int run_step(const ds_denoiser* h, StepCall& s) {
     hipStream_t stream = (hipStream_t)s.tail.stream;
     const size_t n_tok = (size_t)s.tail.B * h->d.seq_len;
-    for (int half = 0; s.tokens2 && half < s.n_cond; ++half) {
+    const bool joint = s.tail.joint;
+    if (joint)
+        TRY(ds_joint_gather_launch(s.tail.who, s.tokens_in, s.tokens2, s.tail.B, s.tail.windows, s.tail.overlap_cols, s.tail.ring,
+                                   s.n_cond, s.tail.stream));
+    for (int half = 0; !joint && s.tokens2 && half < s.n_cond; ++half) {
         hipError_t e = hipMemcpyAsync(s.tokens2 + half * n_tok, s.tokens_in, n_tok * sizeof(int64_t), hipMemcpyDeviceToDevice,
                                       stream);
         if (e != hipSuccess) return step_error(s, -2, "hipMemcpyAsync: ", hipGetErrorString(e));
     }
     Carve w;
     const int Lp = aim_tail(h, s, &w);
-    TRY(forward_impl(h, s.tokens2 ? s.tokens2 : s.tokens_in, s.t, s.kv, s.tokens2 ? s.n_cond * s.tail.B : s.tail.B, w, w.logits, 0,
+    const int Bw = joint ? s.tail.B * s.tail.windows : s.tail.B;
+    TRY(forward_impl(h, s.tokens2 ? s.tokens2 : s.tokens_in, s.t, s.kv, s.tokens2 ? s.n_cond * Bw : Bw, w, w.logits, 0,
                      stream, Lp, s.zero_kv_pad));
     return ds_sample_tail_launch(s.tail);
 }
@@ -538,7 +548,7 @@ static int run_chain(const ds_denoiser* h, const StepCall& first, const ChainCal
         int64_t* sw = cur; cur = nxt; nxt = sw;
     }
     if (cur != ch.tokens) {
-        hipError_t e = hipMemcpyAsync(ch.tokens, cur, (size_t)s.tail.B * h->d.seq_len * sizeof(int64_t), hipMemcpyDeviceToDevice,
+        hipError_t e = hipMemcpyAsync(ch.tokens, cur, (size_t)s.tail.B * s.tail.L * sizeof(int64_t), hipMemcpyDeviceToDevice,
                                       (hipStream_t)s.tail.stream);
         if (e != hipSuccess) return step_error(s, -2, "hipMemcpyAsync: ", hipGetErrorString(e));
     }
@@ -742,6 +752,74 @@ extern "C" int ds_denoiser_sample_composed_rng(const ds_denoiser* h, int64_t* to
     return run_chain(h, s, ChainCall{tokens, tokens_tmp, t_steps, n_calls, 2 * Bf, Bf, nullptr});
 }
 #undef DS_COMPOSED_ARGS
+
+// ---- joint-window sampling (sampler.hip SampleJoint): every step gathers the W window rows of each clip's canvas into tokensN
+// (ds_joint_gather, n_cond copies), runs ONE forward at batch n_cond B W and the joint tail onto the canvas.  n_cond 1: unguided,
+// 2: guided at `scale`.  What sizes the forward -- B, W, overlap_cols, ring, n_cond, the handle's grid -- is the entries' own
+// test; the tail's checker states the geometry again for the tail entries.
+static int joint_args(const ds_denoiser* h, StepCall& s, const void* noise, int B, int W, int n, int ring, int n_cond,
+                      const float* fade, float scale, const unsigned char* keep, const int64_t* known, int mode,
+                      int64_t* tokensN) {
+    const char* msg = !(h && noise && tokensN && fade) ? "bad arguments (null handle, noise source, tokensN or fade)"
+                      : h->d.seq_len != DS_GRID_ROWS * DS_GRID_COLS ? "joint sampling is built for the 5 x 53 grid (seq_len 265)"
+                      : !(B > 0)                        ? "B must be positive"
+                      : W < 1                           ? "windows must be at least 1"
+                      : !(n >= 1 && n <= DS_GRID_COLS / 2) ? "overlap_cols must be in 1 .. 26"
+                      : (ring && W < 2)                 ? "a ring needs at least 2 windows"
+                      : !(n_cond == 1 || n_cond == 2)   ? "n_cond is 1 (unguided) or 2 (guided)"
+                      : ds_joint_canvas_len(W, n, ring) >= 65536 ? "the canvas must be shorter than 65536 positions"
+                                                        : nullptr;
+    if (msg) return step_error(s, -1, msg, "");
+    TailCall& c = s.tail;
+    c.joint = true; c.windows = W; c.overlap_cols = n; c.ring = ring != 0; c.fade = fade; c.t_stride = W;
+    c.B = B; c.L = (int)ds_joint_canvas_len(W, n, ring);
+    c.scale = scale; c.keep = keep; c.known = known; c.mode = mode;
+    s.tokens2 = tokensN; s.n_cond = n_cond;
+    return 0;
+}
+
+extern "C" int ds_denoiser_step_joint(const ds_denoiser* h, const int64_t* canvas_in, const int64_t* t, const int64_t* t_post,
+                                      const float* kv, const float* u, int B, int W, int overlap_cols, int ring, int n_cond,
+                                      const float* fade, int initial, float trunc_r, int trunc_k, float scale,
+                                      const unsigned char* keep, const int64_t* known, int mode, int64_t* tokensN,
+                                      void* workspace, int64_t* canvas_out, ds_stream_t stream) {
+    StepCall s{{__func__, DS_TAIL_POSTERIOR, stream}};
+    TRY(joint_args(h, s, u, B, W, overlap_cols, ring, n_cond, fade, scale, keep, known, mode, tokensN));
+    TailCall& c = s.tail;
+    c.u = u; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    s.tokens_in = canvas_in; s.tokens_out = canvas_out; s.t = t; s.t_post = t_post; s.kv = kv; s.workspace = workspace;
+    return step(h, s);
+}
+
+extern "C" int ds_denoiser_step_joint_rng(const ds_denoiser* h, const int64_t* canvas_in, const int64_t* t,
+                                          const int64_t* t_post, const float* kv, const int64_t* gids, unsigned long long seed,
+                                          int call, int B, int W, int overlap_cols, int ring, int n_cond, const float* fade,
+                                          int initial, float trunc_r, int trunc_k, float scale, const unsigned char* keep,
+                                          const int64_t* known, int mode, int64_t* tokensN, void* workspace,
+                                          int64_t* canvas_out, ds_stream_t stream) {
+    StepCall s{{__func__, DS_TAIL_POSTERIOR, stream}};
+    TRY(joint_args(h, s, gids, B, W, overlap_cols, ring, n_cond, fade, scale, keep, known, mode, tokensN));
+    TailCall& c = s.tail;
+    c.gids = gids; c.seed = seed; c.call = call; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    s.tokens_in = canvas_in; s.tokens_out = canvas_out; s.t = t; s.t_post = t_post; s.kv = kv; s.workspace = workspace;
+    return step(h, s);
+}
+
+// the whole joint chain: canvas / canvas_tmp i64[B][Lc] are the two ends of the ping-pong, t_steps is i64[n_calls][2][n_cond B W]
+extern "C" int ds_denoiser_sample_joint_rng(const ds_denoiser* h, int64_t* canvas, int64_t* canvas_tmp, const int64_t* t_steps,
+                                            int n_calls, const float* kv, const int64_t* gids, unsigned long long seed,
+                                            int call0, int B, int W, int overlap_cols, int ring, int n_cond, const float* fade,
+                                            int initial, float trunc_r, int trunc_k, float scale, const unsigned char* keep,
+                                            const int64_t* known, int mode, int64_t* tokensN, void* workspace,
+                                            ds_stream_t stream) {
+    StepCall s{{__func__, DS_TAIL_POSTERIOR, stream}};
+    TRY(joint_args(h, s, gids, B, W, overlap_cols, ring, n_cond, fade, scale, keep, known, mode, tokensN));
+    TailCall& c = s.tail;
+    c.gids = gids; c.seed = seed; c.call = call0; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    s.kv = kv; s.workspace = workspace;
+    const size_t Bf = (size_t)n_cond * B * W;
+    return run_chain(h, s, ChainCall{canvas, canvas_tmp, t_steps, n_calls, 2 * Bf, Bf, nullptr});
+}
 
 // ---- purity-prior sampling (sampler.hip SamplePurity): forward + purity tail.  tokens2 == NULL: the forward at batch B; else
 // the guided forward at batch 2B, the tail mixing the two halves of the logits.  scratch: ds_purity_scratch_bytes, a pointer

@@ -35,6 +35,11 @@ struct TailCall {
     const float* weights = nullptr;          // non-null: composed (caption tracks); f32[B][n_tracks][L] track weights, and
     int n_tracks = 0;                        //   logits holds n_tracks + 1 slabs (tracks, then the null condition),
     size_t track_stride = 0;                 //   track_stride floats apart.  Not with logits_u, not with DS_TAIL_PURITY.
+    bool joint = false;                      // true: joint-window sampling (sampler.hip SampleJoint) -- B counts clips, L is the
+    int windows = 0, overlap_cols = 0;       //   canvas length, logits (and logits_u) hold one slab of logits_rows rows per
+    int ring = 0;                            //   window, xt / out_tokens / keep / known / u are the canvas's
+    const float* fade = nullptr;             //   f32[overlap_cols], the later window's weight per overlap column (device)
+    int t_stride = 1;                        //   the posterior reads t[b t_stride]
     int remain = 0;                          // purity only, from here on
     float weight = 0.f;
     void* scratch = nullptr;                 // ds_purity_scratch_bytes
@@ -45,6 +50,14 @@ struct TailCall {
 
 // (The VALUES of weights live on the device: checking that they are finite would take a synchronisation, so it is the
 // caller's job -- the Python layer does it, DiffusionTransformer._tracks.  A non-finite weight gives a non-finite prediction.)
+// the token grid of one window, and the canvas of W windows sharing n columns (line or ring): its positions, 0 if none exists
+#define DS_GRID_ROWS 5
+#define DS_GRID_COLS 53
+long long ds_joint_canvas_len(int W, int n, int ring);
+int ds_joint_gather_check(const char* who, const int64_t* canvas, const int64_t* win, int B, int W, int n, int ring, int copies);
+int ds_joint_gather_launch(const char* who, const int64_t* canvas, int64_t* win, int B, int W, int n, int ring, int copies,
+                           ds_stream_t stream);
+
 int ds_sample_tail_check(const TailCall& c);    // every argument rule, once: -1 and a message naming c.who, no HIP call
 int ds_sample_tail_launch(const TailCall& c);   // a checked call: fills the kernel arguments, selects the kernel
 

@@ -160,6 +160,26 @@ struct SampleCompose {
     int n_tracks;                // 1 .. DS_MAX_TRACKS
 };
 
+// JOINT form (joint-window sampling of a long clip: the *_joint entries; geometry: DESIGN.md section 4).  All W windows of a
+// clip live on one token canvas of C columns -- line: C = G + (W - 1) h, ring: C = W h, hop h = G - n, n overlap columns --
+// and one wave handles one CANVAS position q = R c + r: p.L is the canvas length R C, p.xt / p.out_tokens / keep / known / the
+// uniforms and the Philox position are the canvas's, p.B counts clips.  p.logits holds one slab of lrows rows per WINDOW, row
+// ((b W + w) lrows + R o + r) for offset o of window w.  The later window of column c is w1 = min(c / h, W - 1) (ring: c / h)
+// at offset o1 = c - w1 h; with o1 < n and (w1 >= 1 or ring) the earlier window w0 = (w1 - 1) mod W covers the column too, at
+// offset o1 + h.  A position under one window gets that row's log_pred -- the plain tail's, or with gd.logits_u (here a
+// run-time test, one wave-uniform branch) the guided tail's.  A position under two windows: l0, l1 = those log_preds (each
+// rounded to f32 and clamped), then the GUIDED expression with (lu, lc, scale) = (l0, l1, fade[o1]) -- the same macro, the
+// same f64 operations in the same order -- and its renormalisation give the log_pred that truncation, posterior and
+// Gumbel-argmax consume unchanged.  The posterior's timestep is p.t[b t_stride]: 1 for the tail entries (t i64[B]), W where
+// the step driver hands over the network's vector (one entry per window row).  A separate kernel argument and ONE separate
+// __global__ wrapper per (K, noise source), keep == nullptr meaning unheld: the other kernels keep their arguments,
+// registers and code.
+struct SampleJoint {
+    const float* fade;           // f32[n]: the later window's weight at overlap offset o (audio.fade_table(n))
+    int W, n, ring;
+    int t_stride;
+};
+
 __device__ __forceinline__ double wmaxd(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
@@ -196,11 +216,28 @@ __device__ __forceinline__ double wmaxd(double v) {
         }                                                                                \
     }
 
-template <int NPL, bool RNG, bool HOLD, bool GUIDED = false, bool PURITY = false, bool COMPOSED = false>
+// The guided mix of two predictions, gv = lu + s (lc - lu) in float64, and the renormalisation of a mix, lp = f32(gv - logsumexp(gv))
+// (max-shifted) clamped to [-70, 0]: macros for the reason above, expanded by the guided, the composed and the joint form.
+#define DS_GUIDE_MIX(gv_, lu_, lc_, s_) \
+    _Pragma("unroll") for (int j = 0; j < NPL; ++j) gv_[j] = (double)lu_[j] + s_ * ((double)lc_[j] - (double)lu_[j]);
+#define DS_GUIDE_RENORM(gv_, lp_)                                                        \
+    {                                                                                    \
+        double gm = gv_[0];                                                              \
+        _Pragma("unroll") for (int j = 1; j < NPL; ++j) gm = fmax(gm, gv_[j]);           \
+        gm = wmaxd(gm);                                                                  \
+        double gs = 0.0;                                                                 \
+        _Pragma("unroll") for (int j = 0; j < NPL; ++j) gs += exp(gv_[j] - gm);          \
+        const double glse = log(wsumd(gs));                                              \
+        _Pragma("unroll") for (int j = 0; j < NPL; ++j)                                  \
+            lp_[j] = fminf(fmaxf((float)((gv_[j] - gm) - glse), -70.f), 0.f);            \
+    }
+
+template <int NPL, bool RNG, bool HOLD, bool GUIDED = false, bool PURITY = false, bool COMPOSED = false, bool JOINT = false>
 __device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const SampleRng& g, const SampleHold& h,
                                                     const SampleGuide& gd = SampleGuide{nullptr, 1.f},
                                                     const SamplePurity& pu = SamplePurity{nullptr, nullptr, nullptr, 0.f},
-                                                    const SampleCompose& cp = SampleCompose{nullptr, 0, 0}) {
+                                                    const SampleCompose& cp = SampleCompose{nullptr, 0, 0},
+                                                    const SampleJoint& jt = SampleJoint{nullptr, 1, 1, 0, 1}) {
     constexpr int K = NPL * 64;
     __shared__ float s_lp[4][K];
     __shared__ __attribute__((aligned(16))) float s_pr[4][K];
@@ -211,7 +248,7 @@ __device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const
     if (!live) col = p.B * p.L - 1;
     const int b = col / p.L, pos = col - b * p.L;
     if constexpr (HOLD) {
-        if ((!(GUIDED || COMPOSED) || h.keep) && h.keep[col]) {       // wave-uniform: the whole wave leaves (no block-wide barrier below in this form)
+        if ((!(GUIDED || COMPOSED || JOINT) || h.keep) && h.keep[col]) {       // wave-uniform: the whole wave leaves (no block-wide barrier below in this form)
             int tok = (int)h.known[col];
             if constexpr (RNG) {
                 const int tp = (int)p.t[b];
@@ -226,7 +263,44 @@ __device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const
 
     // ---- predict_start: float64 log-softmax over the K real classes ----
     float lp[NPL];
-    if constexpr (COMPOSED) {    // the null condition's row (the last slab) first: lp is lu until the mix below replaces it
+    if constexpr (JOINT) {
+        // ---- joint windows (see SampleJoint): the later window's log_pred in lp, the earlier one's -- if there is one -- in l0 ----
+        const int hop = DS_GRID_COLS - jt.n;
+        const int cc = pos / DS_GRID_ROWS, rr = pos - cc * DS_GRID_ROWS;
+        int w1 = cc / hop;
+        if (!jt.ring && w1 > jt.W - 1) w1 = jt.W - 1;
+        const int o1 = cc - w1 * hop;
+        const bool two = o1 < jt.n && (w1 >= 1 || jt.ring);
+        const int w0 = w1 >= 1 ? w1 - 1 : jt.W - 1;
+        float l0[NPL];
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) l0[j] = 0.f;
+        for (int k = two ? 0 : 1; k < 2; ++k) {
+            const size_t row = k ? ((size_t)b * jt.W + w1) * p.lrows + DS_GRID_ROWS * o1 + rr
+                                 : ((size_t)b * jt.W + w0) * p.lrows + DS_GRID_ROWS * (o1 + hop) + rr;
+            float lw[NPL];
+            DS_PREDICT_START_ROW(p.logits + row * K, lw)
+            if (gd.logits_u) {
+                float lu[NPL];
+                DS_PREDICT_START_ROW(gd.logits_u + row * K, lu)
+                const double s = (double)gd.scale;
+                double gv[NPL];
+                DS_GUIDE_MIX(gv, lu, lw, s)
+                DS_GUIDE_RENORM(gv, lw)
+            }
+#pragma unroll
+            for (int j = 0; j < NPL; ++j) {
+                if (k == 0) l0[j] = lw[j];
+                lp[j] = lw[j];
+            }
+        }
+        if (two) {
+            const double s = (double)jt.fade[o1];
+            double gv[NPL];
+            DS_GUIDE_MIX(gv, l0, lp, s)
+            DS_GUIDE_RENORM(gv, lp)
+        }
+    } else if constexpr (COMPOSED) {    // the null condition's row (the last slab) first: lp is lu until the mix below replaces it
         DS_PREDICT_START_ROW(p.logits + (size_t)cp.n_tracks * cp.track_stride + ((size_t)b * p.lrows + pos) * K, lp)
     } else {
     DS_PREDICT_START_ROW(p.logits + ((size_t)b * p.lrows + pos) * K, lp)
@@ -255,19 +329,9 @@ __device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const
             float lu[NPL];
             DS_PREDICT_START_ROW(gd.logits_u + ((size_t)b * p.lrows + pos) * K, lu)
             const double s = (double)gd.scale;
-#pragma unroll
-            for (int j = 0; j < NPL; ++j) gv[j] = (double)lu[j] + s * ((double)lp[j] - (double)lu[j]);
+            DS_GUIDE_MIX(gv, lu, lp, s)
         }
-        double gm = gv[0];
-#pragma unroll
-        for (int j = 1; j < NPL; ++j) gm = fmax(gm, gv[j]);
-        gm = wmaxd(gm);
-        double gs = 0.0;
-#pragma unroll
-        for (int j = 0; j < NPL; ++j) gs += exp(gv[j] - gm);
-        const double glse = log(wsumd(gs));
-#pragma unroll
-        for (int j = 0; j < NPL; ++j) lp[j] = fminf(fmaxf((float)((gv[j] - gm) - glse), -70.f), 0.f);
+        DS_GUIDE_RENORM(gv, lp)
     }
     const size_t dbg_base = (size_t)b * (K + 1) * p.L + pos;
     if (p.dbg_log_pred && live) {
@@ -420,7 +484,7 @@ __device__ __forceinline__ void ds_sample_tail_body(const SampleParams& p, const
     } else {
     // ---- q_posterior ----
     const int T1 = p.T + 1;
-    const int t = (int)p.t[b];
+    const int t = (int)p.t[JOINT ? b * jt.t_stride : b];
     const int tm1 = (t - 1 + T1) % T1;
     const float* S = p.sched;
     const float lat = S[0 * T1 + t], lbt = S[1 * T1 + t], lct = S[2 * T1 + t];
@@ -524,6 +588,8 @@ __global__ __launch_bounds__(256) void ds_sample_tail_hold_kernel(const SamplePa
 }
 
 #undef DS_PREDICT_START_ROW
+#undef DS_GUIDE_MIX
+#undef DS_GUIDE_RENORM
 
 template <int NPL, bool RNG>
 __global__ __launch_bounds__(256) void ds_sample_tail_guided_kernel(const SampleParams p, const SampleRng g, const SampleHold h,
@@ -544,6 +610,29 @@ __global__ __launch_bounds__(256) void ds_sample_tail_composed_kernel(const Samp
                                                                       const SampleCompose cp) {
     ds_sample_tail_body<NPL, RNG, true, false, false, true>(p, g, h, SampleGuide{nullptr, 1.f},
                                                             SamplePurity{nullptr, nullptr, nullptr, 0.f}, cp);
+}
+
+// the joint tail (see SampleJoint): one wave per canvas position; guided iff gd.logits_u
+template <int NPL, bool RNG>
+__global__ __launch_bounds__(256) void ds_sample_tail_joint_kernel(const SampleParams p, const SampleRng g, const SampleHold h,
+                                                                   const SampleGuide gd, const SampleJoint jt) {
+    ds_sample_tail_body<NPL, RNG, true, false, false, false, true>(p, g, h, gd, SamplePurity{nullptr, nullptr, nullptr, 0.f},
+                                                                   SampleCompose{nullptr, 0, 0}, jt);
+}
+
+// The window rows of a canvas (see SampleJoint), as the denoiser reads them: win[(k B W + b W + w)][R o + r] =
+// canvas[b][R ((w h + o) mod C) + r] for k < copies -- condition-major, the layout of StepCall::tokens2.  One thread per
+// token of one copy: a whole int64 loaded once and stored `copies` times.
+__global__ __launch_bounds__(256) void ds_joint_gather_kernel(const int64_t* __restrict__ canvas, int64_t* __restrict__ win,
+                                                              int B, int W, int hop, int C, int copies) {
+    constexpr int L = DS_GRID_ROWS * DS_GRID_COLS;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x, n = (long long)B * W * L;
+    if (i >= n) return;
+    const int e = (int)(i % L), bw = (int)(i / L);
+    const int b = bw / W, w = bw - b * W;
+    const int o = e / DS_GRID_ROWS, r = e - o * DS_GRID_ROWS;
+    const int64_t v = canvas[(size_t)b * DS_GRID_ROWS * C + (size_t)DS_GRID_ROWS * ((w * hop + o) % C) + r];
+    for (int k = 0; k < copies; ++k) win[(size_t)k * n + i] = v;
 }
 
 // step 6: one workgroup per sample.  m = its [MASK] positions, n = max(0, m - remain); the n masked positions of largest key
@@ -931,9 +1020,17 @@ extern "C" int ds_philox_uniforms(const int64_t* gids, unsigned long long seed, 
 
 // ---- the tails' host side: one description of a call (sampler.h TailCall), one checker, one launcher ----------------------
 // Every rule of every tail, stated once.  A field a form does not have stays zero in the TailCall and passes its rule.
+// positions of the canvas of W windows sharing n columns (see SampleJoint), 0 where the geometry does not exist
+long long ds_joint_canvas_len(int W, int n, int ring) {
+    if (W < 1 || n < 1 || n > DS_GRID_COLS / 2 || (ring && W < 2)) return 0;
+    const long long hop = DS_GRID_COLS - n;
+    return DS_GRID_ROWS * (ring ? W * hop : DS_GRID_COLS + (W - 1) * hop);
+}
+
 int ds_sample_tail_check(const TailCall& c) {
     const bool purity = c.kind == DS_TAIL_PURITY, guided = c.logits_u != nullptr;
     const bool composed = c.weights != nullptr || c.n_tracks != 0;        // a composed entry; its rules are the guided form's plus:
+    const bool joint = c.joint;                                           // a joint entry: c.L is the canvas length, 0 if it has none
     const char* msg =
         (composed && !c.weights)                                          ? "null pointer (weights: the track weights)"
         : (composed && !(c.n_tracks >= 1 && c.n_tracks <= DS_MAX_TRACKS)) ? "n_tracks must be in 1 .. 4"
@@ -941,11 +1038,18 @@ int ds_sample_tail_check(const TailCall& c) {
         : (composed && purity)                                            ? "caption tracks have no purity form"
         : !(c.logits && c.xt && (c.u || c.gids) && c.out_tokens && (purity ? c.scratch && c.B > 0 : c.t && c.sched))
                                                                          ? "null pointer"
+        : (joint && !c.fade)                                              ? "null pointer (fade: the overlap's column weights)"
+        : (joint && c.windows < 1)                                        ? "windows must be at least 1"
+        : (joint && !(c.overlap_cols >= 1 && c.overlap_cols <= DS_GRID_COLS / 2)) ? "overlap_cols must be in 1 .. 26"
+        : (joint && c.ring && c.windows < 2)                              ? "a ring needs at least 2 windows"
+        : (joint && ds_joint_canvas_len(c.windows, c.overlap_cols, c.ring) >= 65536)
+                                                                          ? "the canvas must be shorter than 65536 positions"
+        : (joint && c.mode != 0)                   ? "joint sampling holds positions clean (mode 0): it has no renoise mode"
         // (the unguided posterior tails never tested these three, and which calls are accepted is part of the ABI)
-        : (!purity && (guided || composed) && !(c.B > 0 && c.L > 0 && c.T > 0)) ? "B, L and T must be positive"
+        : (!purity && (guided || composed || joint) && !(c.B > 0 && c.L > 0 && c.T > 0)) ? "B, L and T must be positive"
         : !(c.K == 256 || c.K == 512)                                     ? "codebook size must be 256 or 512"
         : (purity && !(c.L > 0 && c.L <= DS_PURITY_MAX_L))                ? "L must be in 1 .. 288"
-        : !(c.logits_rows >= c.L && c.L < 65536)                          ? "logits rows per sample"
+        : !(c.logits_rows >= (joint ? DS_GRID_ROWS * DS_GRID_COLS : c.L) && c.L < 65536) ? "logits rows per sample"
         : (composed && c.track_stride < (size_t)c.B * c.logits_rows * c.K) ? "track_stride is smaller than one slab of logits"
         : (purity && c.remain < 0)                                        ? "remain must be >= 0"
         : (purity && !(c.weight >= 0.f && c.weight - c.weight == 0.f))    ? "the purity weight must be finite and >= 0"
@@ -976,6 +1080,8 @@ int ds_sample_tail_check(const TailCall& c) {
     hipLaunchKernelGGL((ds_sample_tail_guided_kernel<NPL_, RNG_>), grid, block, 0, stream, p, g, h, gd)
 #define DS_TAIL_COMPOSED(NPL_, RNG_) \
     hipLaunchKernelGGL((ds_sample_tail_composed_kernel<NPL_, RNG_>), grid, block, 0, stream, p, g, h, cp)
+#define DS_TAIL_JOINT(NPL_, RNG_) \
+    hipLaunchKernelGGL((ds_sample_tail_joint_kernel<NPL_, RNG_>), grid, block, 0, stream, p, g, h, gd, jt)
 #define DS_TAIL_PURITY(NPL_, RNG_)                                                                                           \
     do {                                                                                                                     \
         if (guided) hipLaunchKernelGGL((ds_sample_purity_rows_kernel<NPL_, RNG_, true>), grid, block, 0, stream, p, g, gd, pu); \
@@ -985,6 +1091,7 @@ int ds_sample_tail_check(const TailCall& c) {
 int ds_sample_tail_launch(const TailCall& c) {
     hipStream_t stream = (hipStream_t)c.stream;
     const bool purity = c.kind == DS_TAIL_PURITY, guided = c.logits_u != nullptr, composed = c.weights != nullptr;
+    const bool joint = c.joint;
     const long long cols = (long long)c.B * c.L;
     int* cand = (int*)c.scratch;                             // purity: the rows kernel leaves (candidate, key) per grid position
     float* key = purity ? (float*)(cand + cols) : nullptr;   //   here, and the select kernel writes the tokens
@@ -995,12 +1102,14 @@ int ds_sample_tail_launch(const TailCall& c) {
     const SampleGuide gd{c.logits_u, c.scale};
     const SamplePurity pu{cand, key, c.dbg_sharp, c.weight};
     const SampleCompose cp{c.weights, c.track_stride, c.n_tracks};
+    const SampleJoint jt{c.fade, c.windows, c.overlap_cols, c.ring, c.t_stride};
     const dim3 grid((unsigned)((cols + 3) / 4)), block(256);
-    if (!purity && !guided && !composed && c.keep) DS_TAIL_LADDER(DS_TAIL_HOLD);
-    else if (!purity && !guided && !composed) DS_TAIL_LADDER(DS_TAIL_PLAIN);
-    else if (!purity && !composed) DS_TAIL_LADDER(DS_TAIL_GUIDED);
-    else if (purity) DS_TAIL_LADDER(DS_TAIL_PURITY);
-    else DS_TAIL_LADDER(DS_TAIL_COMPOSED);
+    if (!joint && !purity && !guided && !composed && c.keep) DS_TAIL_LADDER(DS_TAIL_HOLD);
+    else if (!joint && !purity && !guided && !composed) DS_TAIL_LADDER(DS_TAIL_PLAIN);
+    else if (!joint && !purity && !composed) DS_TAIL_LADDER(DS_TAIL_GUIDED);
+    else if (!joint && purity) DS_TAIL_LADDER(DS_TAIL_PURITY);
+    else if (!joint) DS_TAIL_LADDER(DS_TAIL_COMPOSED);
+    else DS_TAIL_LADDER(DS_TAIL_JOINT);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && purity) {
         hipLaunchKernelGGL(ds_sample_purity_select_kernel, dim3(c.B), dim3(256), 0, stream, c.xt, (const int*)cand,
@@ -1025,6 +1134,7 @@ int ds_sample_tail_launch(const TailCall& c) {
 #undef DS_TAIL_GUIDED
 #undef DS_TAIL_PURITY
 #undef DS_TAIL_COMPOSED
+#undef DS_TAIL_JOINT
 
 static int tail_run(const TailCall& c) {
     const int rc = ds_sample_tail_check(c);
@@ -1154,6 +1264,82 @@ extern "C" int ds_sample_tail_composed_rng(const float* logits, const int64_t* x
     c.B = B; c.L = L; c.K = K; c.T = T; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
     c.keep = keep; c.known = known; c.mode = mode;
     return tail_run(c);
+}
+
+// the joint tails (see SampleJoint): logits (and logits_u, NULL: unguided) f32[B W lrows][K], one slab of lrows >= 265 rows per
+// window; everything else on the canvas of ds_joint_canvas_len(W, n, ring) positions; keep == nullptr: unheld
+static void joint_fields(TailCall& c, int B, int W, int n, int ring, const float* fade, int lrows) {
+    c.joint = true; c.windows = W; c.overlap_cols = n; c.ring = ring != 0; c.fade = fade; c.t_stride = 1;
+    c.B = B; c.logits_rows = lrows;
+    const long long Lc = ds_joint_canvas_len(W, n, ring);
+    c.L = Lc < 65536 ? (int)Lc : 0;       // (the checker refuses a canvas that does not exist or is too long before it reads L)
+}
+
+extern "C" int ds_sample_tail_joint(const float* logits, const float* logits_u, const int64_t* canvas, const int64_t* t,
+                                    const float* u, const float* sched, int64_t* out_canvas, float* dbg_log_pred,
+                                    float* dbg_trunc, float* dbg_post, int B, int W, int overlap_cols, int ring,
+                                    const float* fade, int lrows, int K, int T, int initial, float trunc_r, int trunc_k,
+                                    float scale, const unsigned char* keep, const int64_t* known, int mode,
+                                    ds_stream_t stream) {
+    DS_CHECK_ARG(u, "null pointer");
+    TailCall c{__func__, DS_TAIL_POSTERIOR, stream};
+    joint_fields(c, B, W, overlap_cols, ring, fade, lrows);
+    c.logits = logits; c.logits_u = logits_u; c.scale = scale;
+    c.xt = canvas; c.t = t; c.u = u; c.sched = sched; c.out_tokens = out_canvas;
+    c.dbg_log_pred = dbg_log_pred; c.dbg_trunc = dbg_trunc; c.dbg_post = dbg_post;
+    c.K = K; c.T = T; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    c.keep = keep; c.known = known; c.mode = mode;
+    return tail_run(c);
+}
+
+extern "C" int ds_sample_tail_joint_rng(const float* logits, const float* logits_u, const int64_t* canvas, const int64_t* t,
+                                        const int64_t* gids, unsigned long long seed, int call, const float* sched,
+                                        int64_t* out_canvas, float* dbg_log_pred, float* dbg_trunc, float* dbg_post, int B,
+                                        int W, int overlap_cols, int ring, const float* fade, int lrows, int K, int T,
+                                        int initial, float trunc_r, int trunc_k, float scale, const unsigned char* keep,
+                                        const int64_t* known, int mode, ds_stream_t stream) {
+    DS_CHECK_ARG(gids, "null pointer");
+    TailCall c{__func__, DS_TAIL_POSTERIOR, stream};
+    joint_fields(c, B, W, overlap_cols, ring, fade, lrows);
+    c.logits = logits; c.logits_u = logits_u; c.scale = scale;
+    c.xt = canvas; c.t = t; c.sched = sched; c.out_tokens = out_canvas;
+    c.gids = gids; c.seed = seed; c.call = call;
+    c.dbg_log_pred = dbg_log_pred; c.dbg_trunc = dbg_trunc; c.dbg_post = dbg_post;
+    c.K = K; c.T = T; c.initial = initial; c.trunc_r = trunc_r; c.trunc_k = trunc_k;
+    c.keep = keep; c.known = known; c.mode = mode;
+    return tail_run(c);
+}
+
+// the window rows of a canvas (ds_joint_gather_kernel): every rule checked before the launch
+int ds_joint_gather_check(const char* who, const int64_t* canvas, const int64_t* win, int B, int W, int n, int ring, int copies) {
+    const char* msg = !(canvas && win)                                    ? "null pointer"
+                      : !(B > 0)                                          ? "B must be positive"
+                      : W < 1                                             ? "windows must be at least 1"
+                      : !(n >= 1 && n <= DS_GRID_COLS / 2)                ? "overlap_cols must be in 1 .. 26"
+                      : (ring && W < 2)                                   ? "a ring needs at least 2 windows"
+                      : !(copies >= 1 && copies <= 2)                     ? "copies is 1 or 2"
+                                                                          : nullptr;
+    if (!msg) return 0;
+    ds_set_error("%s: %s", who, msg);
+    return -1;
+}
+int ds_joint_gather_launch(const char* who, const int64_t* canvas, int64_t* win, int B, int W, int n, int ring, int copies,
+                           ds_stream_t stream) {
+    const int hop = DS_GRID_COLS - n, C = (int)(ds_joint_canvas_len(W, n, ring) / DS_GRID_ROWS);
+    const long long total = (long long)B * W * DS_GRID_ROWS * DS_GRID_COLS;
+    hipLaunchKernelGGL(ds_joint_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, canvas,
+                       win, B, W, hop, C, copies);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        ds_set_error("%s: launch failed: %s", who, hipGetErrorString(e));
+        return -2;
+    }
+    return 0;
+}
+extern "C" int ds_joint_gather(const int64_t* canvas, int64_t* win, int B, int W, int overlap_cols, int ring, int copies,
+                               ds_stream_t stream) {
+    const int rc = ds_joint_gather_check(__func__, canvas, win, B, W, overlap_cols, ring, copies);
+    return rc ? rc : ds_joint_gather_launch(__func__, canvas, win, B, W, overlap_cols, ring, copies, stream);
 }
 
 // ---- purity-prior tails (see SamplePurity)

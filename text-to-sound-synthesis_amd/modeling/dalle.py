@@ -341,8 +341,59 @@ class DALLE(nn.Module):
         return {"content": content, "content_token": tokens}
 
     @torch.no_grad()
+    def _joint_long_content(self, batch, windows, n, ring, keep_mode, sample_type, guidance_scale, start_token, tracks):
+        """generate_long_content(joint=True): the token stage as ONE joint chain (DiffusionTransformer.sample_joint)."""
+        from ..pipeline import GRID_COLS, GRID_ROWS, joint_canvas_cols, joint_window_positions
+        if tracks is not None:
+            raise ValueError("caption tracks are not built for joint sampling (joint=True)")
+        if keep_mode != "clamp":
+            raise ValueError("joint sampling holds positions clean: keep_mode=%r is not built for it (joint=True)" % (keep_mode,))
+        if self._purity_part(sample_type, keep_mode) is not None:
+            raise ValueError("a purity part is not built for joint sampling (joint=True): sample type %r" % (sample_type,))
+        parts = sample_type.split(",")
+        skip = 0
+        for q in parts[1:]:
+            if q[:4] != "fast":
+                raise ValueError("joint sampling takes 'top{r}r' / 'top{k}p' and ',fast{n}': %r is not built for it" % (q,))
+            skip = int(q[4:])
+        Lc = GRID_ROWS * joint_canvas_cols(windows, n, ring)
+        self.eval()
+        condition = self.prepare_condition(batch=batch)
+        tr = self.transformer
+        cond_emb = tr._cond(condition.get("condition_token"), condition.get("condition_embed_token"))
+        B = cond_emb.shape[0]
+        ids = batch.get("caption_ids")
+        ids = torch.arange(B) if ids is None else torch.as_tensor(ids, dtype=torch.long).reshape(-1)
+        if ids.numel() != B:
+            raise ValueError("%d caption ids for %d captions" % (ids.numel(), B))
+        kw = dict(self._guidance(batch, guidance_scale, 1), caption_ids=ids)
+        if batch.get("seed") is not None:
+            kw["seed"] = int(batch["seed"])
+        if start_token is not None:                           # the recording's grid: a held canvas head
+            head = torch.as_tensor(start_token).to(self.device).long().contiguous()
+            if tuple(head.shape) != (B, tr.content_seq_len):
+                raise ValueError("start_token must be i64[%d, %d], got %s" % (B, tr.content_seq_len, tuple(head.shape)))
+            known = torch.zeros(B, Lc, dtype=torch.long, device=self.device)
+            known[:, :GRID_ROWS * GRID_COLS] = head
+            keep = torch.zeros(B, Lc, dtype=torch.bool, device=self.device)
+            keep[:, :GRID_ROWS * GRID_COLS] = True
+            kw.update(keep_mask=keep, content_token=known)
+        saved = tr.truncation_r, tr.truncation_k, tr.repeat_rate, self.truncation_forward
+        self.truncation_forward = False                       # install THIS call's sample type
+        try:
+            self._install_sample_type(parts[0])
+            canvas = tr.sample_joint(cond_emb, windows, n, ring=ring, skip_step=skip, **kw)
+        finally:
+            tr.truncation_r, tr.truncation_k, tr.repeat_rate, self.truncation_forward = saved
+        tokens = canvas[:, joint_window_positions(windows, n, ring).to(canvas.device)].contiguous()       # [B, W, 265]
+        flat = tokens.view(B * windows, tokens.shape[2])
+        content = self.decode_to_img(flat, (flat.shape[0], 256, 5, 53))
+        self.train()
+        return {"content": content, "content_token": tokens, "canvas_token": canvas}
+
+    @torch.no_grad()
     def generate_long_content(self, *, batch, windows, overlap_cols, keep_mode="clamp", sample_type="top0.85r",
-                              guidance_scale=None, start_token=None, tracks=None):
+                              guidance_scale=None, start_token=None, tracks=None, joint=False, ring=False):
         """A clip longer than one token grid as `windows` overlapping 5 x 53 grids (not in the reference; the plan comes from
         pipeline.long_plan).  Window 0 is what generate_content(filter_ratio=0, content_ratio=1) generates with per-caption
         in-kernel noise (batch['caption_ids'], default 0 .. B-1; batch['seed']) -- or start_token (i64[B, 265], e.g. a
@@ -354,13 +405,25 @@ class DALLE(nn.Module):
         The model's truncation settings are this call's only: saved before and restored after.
         tracks: caption tracks as in generate_content with 'weight' f32[B, C, 5 total columns], total columns =
         53 + (W - 1)(53 - overlap_cols); window w runs under the slice over its own global columns (_window_tracks).
-        Returns {'content_token': i64[B, W, 265], 'content': mel image [B W, 1, 80, 848], clip-major (index b W + w)}."""
+        Returns {'content_token': i64[B, W, 265], 'content': mel image [B W, 1, 80, 848], clip-major (index b W + w)}.
+
+        joint=True: the token stage is ONE joint chain instead -- all windows on one token canvas, one denoiser forward per
+        step at batch B W, one token drawn per canvas position from the fusion of the windows that cover it
+        (DiffusionTransformer.sample_joint) under the clips' own caption ids; start_token becomes a held canvas head.  ring=True
+        (joint only, W >= 2) closes the canvas into a ring.  Also returns 'canvas_token' i64[B, 5 C]; content_token holds the
+        windows cut from the canvas, so two neighbours carry the SAME tokens in the columns they share.  tracks, a purity part
+        and keep_mode "renoise" are not built for joint sampling and raise ValueError.  joint=False: today's path."""
         from ..pipeline import GRID_COLS, MAX_WINDOWS, continuation_tokens, window_caption_ids
         windows, n = int(windows), int(overlap_cols)
         if not 1 <= windows <= MAX_WINDOWS:
             raise ValueError("windows must be in 1 .. %d, got %r" % (MAX_WINDOWS, windows))
         if not 1 <= n <= GRID_COLS // 2:
             raise ValueError("overlap_cols must be in 1 .. %d, got %r" % (GRID_COLS // 2, overlap_cols))
+        if ring and not joint:
+            raise ValueError("a ring exists under joint sampling only: pass joint=True with ring=True")
+        if joint:
+            return self._joint_long_content(batch, windows, n, bool(ring), keep_mode, sample_type, guidance_scale, start_token,
+                                            tracks)
         trk = self._track_keywords(batch, tracks, 1, sample_type, GRID_COLS + (windows - 1) * (GRID_COLS - n))
         self.eval()
         condition = self.prepare_condition(batch=batch) if trk is None else {}

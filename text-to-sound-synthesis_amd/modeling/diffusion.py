@@ -697,6 +697,108 @@ class DiffusionTransformer(nn.Module):
         finally:
             self.repeat_rate = keep
 
+    # ---- joint-window sampling (csrc/sampler.hip SampleJoint) ----------------------------------------------
+    JOINT_MAX_ROWS = 128      # the largest forward of a joint step: the largest batch the project has measured
+
+    def _joint_once(self, cond_emb, geometry, calls, noise_fn, gids, seed, hold, guide):
+        """One joint chain on a chunk of clips -> canvas i64[B, Lc].  calls: [(t, t_post)]; noise_fn None: the one-call chain
+        with in-kernel noise (ds_denoiser_sample_joint_rng), else the stepped entry per call (ds_denoiser_step_joint)."""
+        from ..audio import _fade_table
+        W, n, ring, Lc = geometry
+        device = self.device
+        B, K1, L = cond_emb.shape[0], self.num_classes, self.content_seq_len
+        sched = self._schedule_table()
+        tr = self.transformer
+        p = tr.packed(sched)
+        lib = _lib.lib()
+        r, k = self._truncation()
+        n_cond = 1 if guide is None else 2
+        Bf = n_cond * B * W
+        emb = cond_emb.to(device).float().repeat_interleave(W, 0)               # row b W + w: clip b's caption
+        scale = 1.0
+        if guide is not None:
+            emb, scale = torch.cat((emb, guide[0].repeat_interleave(W, 0)), 0), guide[1]
+        kv = tr.condition_kv(emb.contiguous(), sched)
+        fade = _fade_table(n, device)
+        keep, known = (None, None) if hold is None else hold
+        x = torch.full((B, Lc), K1 - 1, device=device, dtype=torch.long) if hold is None \
+            else torch.where(keep != 0, known, torch.full_like(known, K1 - 1))
+        tmp = torch.empty_like(x)
+        tokens_n = torch.empty(Bf, L, device=device, dtype=torch.long)
+        ws = tr.workspace(Bf, sched, 0)
+        geo = [B, W, n, int(bool(ring)), n_cond, _lib.ptr(fade)]
+        tail = [r, k, float(scale), _lib.ptr(keep), _lib.ptr(known), 0, _lib.ptr(tokens_n), _lib.ptr(ws)]
+        if noise_fn is None:
+            t_steps = torch.tensor(calls, dtype=torch.long, device=device).view(-1, 2, 1).expand(-1, 2, Bf).contiguous()
+            _lib.check(lib.ds_denoiser_sample_joint_rng(p["handle"], _lib.ptr(x), _lib.ptr(tmp), _lib.ptr(t_steps), len(calls),
+                                                        _lib.ptr(kv), _lib.ptr(gids), self._seed(seed), 0, *geo,
+                                                        int(hold is None), *tail, _lib.stream()))
+            return x
+        for i, (step, step_post) in enumerate(calls):
+            u = noise_fn(step, (B, K1, Lc)).to(device).float().contiguous()
+            t = torch.full((Bf,), step, device=device, dtype=torch.long)
+            tp = None if step_post == step else torch.full((Bf,), step_post, device=device, dtype=torch.long)
+            _lib.check(lib.ds_denoiser_step_joint(p["handle"], _lib.ptr(x), _lib.ptr(t), _lib.ptr(tp), _lib.ptr(kv), _lib.ptr(u),
+                                                  *geo, int(hold is None and i == 0), *tail, _lib.ptr(tmp), _lib.stream()))
+            x, tmp = tmp, x
+        return x
+
+    @torch.no_grad()
+    def sample_joint(self, condition_embed, windows, overlap_cols, ring=False, skip_step=0, caption_ids=None, seed=None,
+                     keep_mask=None, content_token=None, guidance_scale=None, null_condition_embed=None, noise_fn=None):
+        """Joint-window sampling (not in the reference; the discrete-diffusion counterpart of MultiDiffusion, Bar-Tal et al.
+        2023): all `windows` = W overlapping 5 x 53 windows of a long clip live on one token canvas of
+        C = pipeline.joint_canvas_cols(W, overlap_cols, ring) columns, every diffusion step runs the denoiser ONCE on all
+        windows at batch B W (2 B W with guidance) and the joint tail draws one token per canvas position -- from the fusion
+        of the two windows' predictions where two windows cover it (csrc/sampler.hip SampleJoint).  ring=True closes the
+        canvas into a ring (W >= 2): the last window flows into the first.  -> canvas tokens i64[B, 5 C], time-major.
+
+        condition_embed f32[B, 77, 512].  skip_step: the skip-step plan of sample_fast (0: all T steps).  Noise: in-kernel
+        Philox per clip (caption_ids, default 0 .. B-1; seed) at the canvas position, the whole chain one C call -- or
+        noise_fn(t, (B', K+1, 5 C)), the stepped entry.  keep_mask bool[B, 5 C] / content_token i64[B, 5 C]: held canvas
+        positions (clean: there is no renoise mode).  guidance_scale / null_condition_embed as in sample().  Clips are
+        independent; the batch is cut into chunks whose forward has at most JOINT_MAX_ROWS rows (noise_fn is then called
+        per chunk, with the chunk's B').  How joint clips sound is unmeasured: no trained checkpoint has been available."""
+        from ..pipeline import GRID_ROWS, joint_canvas_cols
+        W, n = int(windows), int(overlap_cols)
+        Lc = GRID_ROWS * joint_canvas_cols(W, n, ring)
+        if self.content_seq_len != 265:
+            raise ValueError("joint sampling is built for the 5 x 53 grid, this model's is %d tokens" % self.content_seq_len)
+        if self.repeat_rate is not None:
+            raise ValueError("the repeat sampler (',q{rate}') is not built for joint sampling")
+        cond_emb = self._cond(None, condition_embed)
+        guide = self._guide(guidance_scale, null_condition_embed, cond_emb)
+        device, B, T = self.device, cond_emb.shape[0], self.num_timesteps
+        skip = int(skip_step)
+        lst = list(range(T - 1, -1, -1 - skip))
+        if lst[-1] != 0:
+            lst.append(0)
+        calls = [(s_, s_ - skip if s_ > skip else s_) for s_ in lst]
+        hold = None
+        if keep_mask is not None:
+            if content_token is None:
+                raise ValueError("keep_mask holds canvas positions of given content: pass content_token i64[B, %d]" % Lc)
+            known = torch.as_tensor(content_token).to(device).long().contiguous()
+            keep = torch.as_tensor(keep_mask).to(device)
+            if tuple(known.shape) != (B, Lc) or tuple(keep.shape) != (B, Lc):
+                raise ValueError("keep_mask and content_token of joint sampling are on the canvas, [%d, %d]: got %s and %s"
+                                 % (B, Lc, tuple(keep.shape), tuple(known.shape)))
+            hold = ((keep != 0).to(torch.uint8).contiguous(), known)
+        gids = None if noise_fn is not None else self._caption_ids(caption_ids, B, device)
+        n_cond = 1 if guide is None else 2
+        if n_cond * W > self.JOINT_MAX_ROWS:
+            raise ValueError("%d windows%s exceed the largest forward of joint sampling (%d rows)"
+                             % (W, " with guidance" if guide is not None else "", self.JOINT_MAX_ROWS))
+        chunk = max(1, self.JOINT_MAX_ROWS // (n_cond * W))
+        out = []
+        for a in range(0, B, chunk):
+            sl = slice(a, min(B, a + chunk))
+            out.append(self._guarded(self._joint_once, cond_emb[sl], (W, n, bool(ring), Lc), calls, noise_fn,
+                                     None if gids is None else gids[sl].contiguous(), seed,
+                                     None if hold is None else (hold[0][sl].contiguous(), hold[1][sl].contiguous()),
+                                     None if guide is None else (guide[0][sl], guide[1])))
+        return out[0] if len(out) == 1 else torch.cat(out, 0)
+
     # ---- purity-prior sampling (csrc/sampler.hip SamplePurity; DESIGN.md section 4) ---------------------------------------------
     def _purity_check(self, steps, purity_weight, keep_mode, filter_ratio):
         """The argument rules of sample_purity, before anything is enqueued -> (S, weight)."""

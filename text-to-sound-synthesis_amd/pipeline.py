@@ -138,6 +138,99 @@ def long_plan(seconds, overlap_seconds=2.4):
     return windows, n, GRID_COLS + (windows - 1) * hop, samples
 
 
+def joint_canvas_cols(windows, overlap_cols, ring=False):
+    """Columns C of the token canvas of joint-window sampling: `windows` = W grids of 53 columns, neighbours sharing n =
+    overlap_cols of them (hop h = 53 - n).  line: C = 53 + (W - 1) h, W >= 1; ring: C = W h, W >= 2 (window w covers columns
+    (w h + o) mod C).  1 <= n <= 26, so n <= h and at most two windows cover a column.  Anything else raises ValueError."""
+    W, n = int(windows), int(overlap_cols)
+    if not 1 <= n <= GRID_COLS // 2:
+        raise ValueError("overlap_cols must be in 1 .. %d, got %r" % (GRID_COLS // 2, overlap_cols))
+    if W < (2 if ring else 1):
+        raise ValueError("%s needs at least %d window%s, got %r" % ((("a ring", 2, "s") if ring else ("a canvas", 1, "")) + (windows,)))
+    h = GRID_COLS - n
+    return W * h if ring else GRID_COLS + (W - 1) * h
+
+
+def joint_map(windows, overlap_cols, ring=False):
+    """The host mirror of the joint tail's geometry (csrc/sampler.hip SampleJoint): for every canvas column c
+    -> dict of numpy arrays of length C = joint_canvas_cols(...):
+        'later' / 'later_offset'      w1 = min(c // h, W - 1) (ring: c // h) and o1 = c - w1 h
+        'earlier' / 'earlier_offset'  w0 = (w1 - 1) mod W and o1 + h where o1 < n and (w1 >= 1 or ring); -1 elsewhere
+        'weight'                      f32: the later window's weight -- audio.fade_table(n)[o1] under two windows (sin^2, in
+                                      (0, 1); the earlier window's is 1 - weight), 1 under one
+    and 'columns' = C.  Canvas positions are time-major, q = 5 c + r, as in content_token."""
+    import numpy as np
+    from .audio import fade_table
+    W, n = int(windows), int(overlap_cols)
+    C = joint_canvas_cols(W, n, ring)
+    h = GRID_COLS - n
+    c = np.arange(C)
+    w1 = c // h if ring else np.minimum(c // h, W - 1)
+    o1 = c - w1 * h
+    two = (o1 < n) & ((w1 >= 1) | bool(ring))
+    fade = fade_table(n).numpy()
+    return {"columns": C, "later": w1, "later_offset": o1, "earlier": np.where(two, (w1 - 1) % W, -1),
+            "earlier_offset": np.where(two, o1 + h, -1),
+            "weight": np.where(two, fade[np.minimum(o1, n - 1)], np.float32(1.0)).astype(np.float32)}
+
+
+def joint_window_positions(windows, overlap_cols, ring=False):
+    """i64[W, 265]: the canvas position of every token of every window (window w, offset o, row r -> 5 ((w h + o) mod C) + r):
+    canvas[:, joint_window_positions(...)] cuts the windows from a canvas, as ds_joint_gather does on the device."""
+    W, n = int(windows), int(overlap_cols)
+    C = joint_canvas_cols(W, n, ring)
+    h = GRID_COLS - n
+    col = (torch.arange(W)[:, None] * h + torch.arange(GRID_COLS)[None, :]) % C                 # [W, 53]
+    return (GRID_ROWS * col[:, :, None] + torch.arange(GRID_ROWS)[None, None, :]).reshape(W, GRID_ROWS * GRID_COLS)
+
+
+def loop_plan(seconds, overlap_seconds=2.4):
+    """The window plan of a seamless loop (Diffsound.generate_loop): -> (windows W, overlap columns n, ring columns C, samples).
+    n as in long_plan; W is the smallest W >= 2 with W h >= ceil(round(seconds 22050) / 4096), h = 53 - n, and the loop that
+    is made is C = W h WHOLE columns -- a loop's length snaps UP to a multiple of h columns -- of samples = 4096 C samples:
+    the length made, not the one asked for.  A ring under 54 columns (10.03 s) would need a window that overlaps itself and is
+    not built: a length that fits one window (<= 53 columns) raises ValueError, and so do more than 16 windows."""
+    import math
+    asked = int(round(_seconds_to_samples(seconds)))
+    if asked < 1:
+        raise ValueError("seconds must cover at least one sample, got %r" % (seconds,))
+    n = int(math.ceil(_seconds_to_samples(overlap_seconds) / COLUMN_SAMPLES))
+    if not 1 <= n <= GRID_COLS // 2:
+        raise ValueError("overlap_seconds must cover 1 .. %d columns of %d samples, got %r (%d columns)"
+                         % (GRID_COLS // 2, COLUMN_SAMPLES, overlap_seconds, n))
+    hop = GRID_COLS - n
+    needed = -(-asked // COLUMN_SAMPLES)
+    if needed <= GRID_COLS:
+        raise ValueError("a loop of %r s fits one window (%d columns): the shortest ring is two windows, %d columns (%.2f s)"
+                         % (seconds, needed, GRID_COLS + 1, (GRID_COLS * COLUMN_SAMPLES + 1) / VOCODER_RATE))
+    windows = max(2, -(-needed // hop))
+    if windows > MAX_WINDOWS:
+        raise ValueError("a loop of %r s needs %d windows at an overlap of %d columns: at most %d (%.1f s)"
+                         % (seconds, windows, n, MAX_WINDOWS, MAX_WINDOWS * hop * COLUMN_SAMPLES / VOCODER_RATE))
+    return windows, n, windows * hop, windows * hop * COLUMN_SAMPLES
+
+
+LOOP_LEAD_HOPS = 2            # hops of the ring's own content rendered ahead of the loop that is cut out (generate_loop)
+
+
+def loop_cut(columns, hop_cols, sample_rate=None):
+    """Where generate_loop cuts the loop out of its rendering, at the output rate -> (offset, period) in whole samples.  At
+    22 050 Hz the rendering starts LOOP_LEAD_HOPS hops ahead of the ring (offset = 2 hop_cols 4096) and the period is 4096
+    columns samples; at another rate both are multiplied by sample_rate / 22 050 and must stay WHOLE: a loop point is exact or
+    it is not emitted.  44 100 and 11 025 Hz always work; 48 000 Hz needs 147 to divide both column counts.  Otherwise
+    ValueError, naming the period."""
+    rate = VOCODER_RATE if sample_rate is None else int(sample_rate)
+    if rate <= 0:
+        raise ValueError("sample_rate must be positive, got %r" % (sample_rate,))
+    off, period = LOOP_LEAD_HOPS * int(hop_cols) * COLUMN_SAMPLES, int(columns) * COLUMN_SAMPLES
+    if (off * rate) % VOCODER_RATE or (period * rate) % VOCODER_RATE:
+        raise ValueError("a loop of %d columns has a period of %d samples at %d Hz = %s samples at %d Hz (offset %s): not whole, "
+                         "and no approximate loop point is emitted -- use 44100, 11025 or 22050 Hz"
+                         % (columns, period, VOCODER_RATE, "%d/%d" % (period * rate, VOCODER_RATE), rate,
+                            "%d/%d" % (off * rate, VOCODER_RATE)))
+    return off * rate // VOCODER_RATE, period * rate // VOCODER_RATE
+
+
 def window_caption_ids(caption_ids, window):
     """The caption ids window `window` of a long clip draws its noise under: ids + window 2^20 (i64 tensor).  Ids must be in
     0 .. 2^20 - 1, which keeps the windows apart from each other and from the replicate stride 2^24; else ValueError."""
@@ -377,15 +470,17 @@ def recording_at_rate(item, rate, out_rate, device="cuda"):
 
 _LEVEL = threading.local()        # the (spec, recording) of the driver call this thread is inside, read by Diffsound._finish
 _PASTE = threading.local()        # the keep_original request of the driver call this thread is inside (Diffsound._paste_plan)
+_JOINT = threading.local()        # the joint= request of the long-form driver call this thread is inside (Diffsound._long_tokens)
 
 
-def _levelled(takes_recording, pastes=False):
+def _levelled(takes_recording, pastes=False, joint=False):
     """Gives a driver the keyword `level=None` (level_spec; keyword-only, behind everything the driver declares) and, with
     pastes=True, `keep_original=None`, `fade_seconds` and `match_gain` (paste_plan).  It is a decorator because levelling
     and pasting are steps of the tail the drivers share (Diffsound._finish), not of any driver: the call's checked spec
     -- and, for "match" and for pasting, the `audio` / `audio_rate` the driver was given -- is held for the duration of the call
     and the tail applies it; a driver's own parameters stay what they were.  level=None and keep_original=None call the
-    driver as it is."""
+    driver as it is.  joint=True (the long-form drivers) adds the keyword `joint=False` the same way: the token stage of the call
+    is joint-window sampling (Diffsound._long_tokens reads the request); False calls the driver as it is."""
     def deco(fn):
         sig = inspect.signature(fn)
 
@@ -414,6 +509,20 @@ def _levelled(takes_recording, pastes=False):
             extra += [inspect.Parameter("keep_original", inspect.Parameter.KEYWORD_ONLY, default=None),
                       inspect.Parameter("fade_seconds", inspect.Parameter.KEYWORD_ONLY, default=FADE_SECONDS),
                       inspect.Parameter("match_gain", inspect.Parameter.KEYWORD_ONLY, default=True)]
+        if joint:
+            levelled = driver
+
+            @functools.wraps(fn)
+            def driver(self, *args, joint=False, **kwargs):
+                if not joint:
+                    return levelled(self, *args, **kwargs)
+                outer = getattr(_JOINT, "request", False)
+                _JOINT.request = True
+                try:
+                    return levelled(self, *args, **kwargs)
+                finally:
+                    _JOINT.request = outer
+            extra.insert(0, inspect.Parameter("joint", inspect.Parameter.KEYWORD_ONLY, default=False))
         driver.__signature__ = sig.replace(parameters=list(sig.parameters.values()) + extra)
         return driver
     return deco
@@ -538,7 +647,11 @@ class Diffsound:
         """The tail every driver shares: the vocoder's f32[B,1,T] -> at `sample_rate` (_at_rate) -> the recording's samples
         pasted over it (paste = a paste_plan of mode "audio") -> brought to the level the driver call asked for (`level=`,
         _levelled), at that rate, on the device (audio.level).  No plan and no `level`: no launch, the waveform as it is."""
-        wave = Diffsound._paste_audio(Diffsound._at_rate(wave, sample_rate), paste)
+        return Diffsound._level(Diffsound._paste_audio(Diffsound._at_rate(wave, sample_rate), paste), sample_rate)
+
+    @staticmethod
+    def _level(wave, sample_rate):
+        """_finish's last step on a waveform that is already at `sample_rate`"""
         request = getattr(_LEVEL, "request", None)
         if wave is None or request is None:
             return wave
@@ -704,7 +817,7 @@ class Diffsound:
 
     def _long_tokens(self, text, windows, overlap_cols, keep_mode, truncation_rate, caption_ids, seed,
                      guidance_scale, negative_text, start_token=None, purity_steps=None, purity_weight=0.0, tracks=None,
-                     sample_type=None):
+                     sample_type=None, joint=False, ring=False):
         """DALLE.generate_long_content under this call's caption / noise keywords (the truncation rate is the call's: the
         facade saves and restores the model's own)."""
         batch = {} if tracks is not None and text is None else dict(self._caption_batch(text))
@@ -717,6 +830,8 @@ class Diffsound:
         if sample_type is None:
             sample_type = purity_sample_type("top" + str(truncation_rate) + "r", purity_steps, purity_weight)
         kw = {} if tracks is None else {"tracks": tracks}       # (without tracks: the call as it always was)
+        if joint:
+            kw.update(joint=True, ring=ring)                    # (likewise)
         return self.model.generate_long_content(batch=batch, windows=windows, overlap_cols=overlap_cols, keep_mode=keep_mode,
                                                 sample_type=sample_type, guidance_scale=guidance_scale, start_token=start_token,
                                                 **kw)
@@ -750,7 +865,7 @@ class Diffsound:
                     write_wav_pcm24(path + ".wav", w_[i], VOCODER_RATE if sample_rate is None else int(sample_rate))
         return mel01, wave, out["content_token"]
 
-    @_levelled(False)
+    @_levelled(False, joint=True)
     @torch.no_grad()
     def generate_long(self, text, seconds, overlap_seconds=2.4, truncation_rate=0.85, keep_mode="clamp", caption_ids=None,
                       seed=None, sample_rate=None, guidance_scale=None, negative_text=None, save_root=None, purity_steps=None,
@@ -767,11 +882,81 @@ class Diffsound:
         in the other drivers; purity_steps / purity_weight: every window's chain is a purity-prior chain
         (generate_sample_with_condition; keep_mode "clamp" only).  seconds up to one grid (217 088 samples): W = 1, the same path without a held chain.
 
-        The overlap is a design choice whose audible quality is unmeasured (long_plan)."""
+        joint=True (keyword-only, given by _levelled like level=) switches the TOKEN stage to joint-window sampling
+        (DALLE.generate_long_content: one chain at batch B W on a shared canvas instead of W chains at batch B, every window
+        seeing both neighbours); the rendering is unchanged.  purity_steps and keep_mode "renoise" are not built for it.
+
+        The overlap is a design choice whose audible quality is unmeasured (long_plan); so is how joint clips sound."""
         windows, n, _, samples = long_plan(seconds, overlap_seconds)
         out = self._long_tokens(text, windows, n, keep_mode, truncation_rate, caption_ids, seed, guidance_scale, negative_text,
-                                purity_steps=purity_steps, purity_weight=purity_weight)
+                                purity_steps=purity_steps, purity_weight=purity_weight, joint=getattr(_JOINT, "request", False))
         return self._render_long(out, windows, n, samples, save_root, sample_rate)
+
+    def _loop_rendering(self, win, windows, overlap_cols, sample_rate=None):
+        """The UNCUT rendering of a ring: the decoded windows win f32[B W, 1, 80, 848] (clip-major) stitched as
+        [w_{W-2}, w_{W-1}, w_0 .. w_{W-1}, w_0, w_1] (indices mod W; audio.stitch_mel at hop 16 h frames) -> (mel f32[B, 80,
+        848 + (W + 3) 16 h] in the codec's [-1, 1], wave f32[B, 1, .] at sample_rate -- the vocoder over the whole stitched mel,
+        resampled as a whole -- or None without a vocoder).  The ring's frame f is stitched frame 2 16 h + f; the stitched mel
+        is the ring's periodic continuation from frame 16 n (the first window's head has no predecessor to blend with) to frame
+        (W + 4) 16 h (the last window's tail has no successor)."""
+        from . import audio
+        B = win.shape[0] // windows
+        order = [(w - LOOP_LEAD_HOPS) % windows for w in range(windows + 2 * LOOP_LEAD_HOPS)]
+        mel = audio.stitch_mel(win.reshape(B, windows, win.shape[2], win.shape[3])[:, order].contiguous(),
+                               (GRID_COLS - overlap_cols) * COLUMN_FRAMES)
+        wave = None
+        if self.vocoder is not None:
+            step = max(1, self.VOCODER_CHUNK_FRAMES // mel.shape[2])
+            wave = torch.cat([self.vocoder(mel[i:i + step], scale=0.5, shift=0.5) for i in range(0, B, step)], 0)
+            wave = self._at_rate(wave, sample_rate)
+        return mel, wave
+
+    @_levelled(False)
+    @torch.no_grad()
+    def generate_loop(self, text, seconds, overlap_seconds=2.4, truncation_rate=0.85, fast=False, caption_ids=None, seed=None,
+                      guidance_scale=None, negative_text=None, sample_rate=None, save_root=None):
+        """Captions -> seamless loops of about `seconds` (ambiences, engines, room tone): (mel01 f32[B, 80, 16 C], wave
+        f32[B, 1, 4096 C rate / 22050] -- None without a vocoder --, tokens i64[B, W, 265], seconds_made).  loop_plan picks
+        W >= 2 windows and the ring of C = W h whole columns (the length snaps UP to a multiple of the hop h = 53 - n columns;
+        seconds_made = 4096 C / 22050 says what was made).  The tokens are ONE joint chain on the canvas closed into a ring
+        (DALLE.generate_long_content(joint=True, ring=True)): window W - 1 flows into window 0 as every window flows into
+        the next.  Rendering: the W decoded windows are stitched as [w_{W-2}, w_{W-1}, w_0 .. w_{W-1}, w_0, w_1] (indices
+        mod W; audio.stitch_mel, hop 16 h frames), so the ring's frame f is stitched frame 2 16 h + f and the frames ahead of
+        and behind the ring are the ring's own content, one hop of it fully blended on either side; the vocoder renders the
+        WHOLE stitched mel and the waveform is cut to the ring's samples.  A convolutional vocoder on a periodic mel gives a
+        periodic waveform wherever its receptive field stays inside the periodic part (DESIGN.md section 4 derives the field),
+        so the loop's last sample flows into its first as any sample flows into the next: no cross-fade in the audio domain.
+        sample_rate: the uncut rendering is resampled and cut at the converted offsets, which must be whole samples
+        (loop_cut: 44 100 and 11 025 always are; otherwise ValueError -- no approximate loop point is emitted).
+        level=: the static strategies measure and scale the one period; with limit it raises (a periodic gain curve is not
+        built).  fast / caption_ids / seed / guidance_scale / negative_text / save_root as in the other drivers.
+
+        How loops SOUND is unmeasured: no trained checkpoint has been available to this project."""
+        import numpy as np
+        request = getattr(_LEVEL, "request", None)
+        if request is not None and request[0].get("limit"):
+            raise ValueError("generate_loop: level= with limit is not built for loops (the limiter's gain curve is not periodic)")
+        windows, n, cols, samples = loop_plan(seconds, overlap_seconds)
+        hop = GRID_COLS - n
+        off, period = loop_cut(cols, hop, sample_rate)                 # the rate rule, before anything runs
+        out = self._long_tokens(text, windows, n, "clamp", truncation_rate, caption_ids, seed, guidance_scale, negative_text,
+                                sample_type="top" + str(truncation_rate) + ("r,fast" + str(fast - 1) if fast else "r"),
+                                joint=True, ring=True)
+        mel, wave = self._loop_rendering(out["content"], windows, n, sample_rate)
+        B = mel.shape[0]
+        lead = LOOP_LEAD_HOPS * hop * COLUMN_FRAMES
+        if wave is not None:
+            wave = self._level(wave[:, :, off:off + period].contiguous(), sample_rate)
+        mel01 = ((mel + 1) / 2)[:, :, lead:lead + cols * COLUMN_FRAMES].contiguous()
+        if save_root is not None:
+            os.makedirs(save_root, exist_ok=True)
+            m_, w_ = mel01.cpu().numpy(), None if wave is None else wave[:, 0].cpu().numpy()
+            for i in range(B):
+                path = os.path.join(save_root, str(i).zfill(6))
+                np.save(path + ".npy", m_[i])
+                if w_ is not None:
+                    write_wav_pcm24(path + ".wav", w_[i], VOCODER_RATE if sample_rate is None else int(sample_rate))
+        return mel01, wave, out["content_token"], samples / VOCODER_RATE
 
     SCENE_SCALE = 3.0     # generate_scene's default track weight: the scale the guidance tests run at; a design choice
 
@@ -814,7 +999,7 @@ class Diffsound:
                                 sample_type="top" + str(truncation_rate) + ("r,fast" + str(fast - 1) if fast else "r"))
         return self._render_long(out, windows, n, samples, save_root, sample_rate)
 
-    @_levelled(True, pastes=True)
+    @_levelled(True, pastes=True, joint=True)
     @torch.no_grad()
     def extend_audio(self, audio, text, seconds, overlap_seconds=2.4, truncation_rate=0.85, keep_mode="clamp", caption_ids=None,
                      seed=None, sample_rate=None, guidance_scale=None, negative_text=None, save_root=None, audio_rate=None,
@@ -824,14 +1009,16 @@ class Diffsound:
         generated under `text` as in generate_long.  Returns what generate_long returns; tokens[:, 0] are the recording's.
         By default the head of the result is the codec's and the vocoder's rendering of the recording's tokens, not the
         input's samples; keep_original="mel" / "audio" (inpaint_audio) keeps columns 0 .. 52 of the long clip as the recording's
-        own mel / samples, with the cross-fade inside column 53."""
+        own mel / samples, with the cross-fade inside column 53.  joint=True (keyword-only, as on generate_long): the windows after the recording are ONE joint
+        chain with the recording's grid held as the canvas head (generate_long); tokens[:, 0] stay the recording's."""
         windows, n, _, samples = long_plan(seconds, overlap_seconds)
         if windows < 2:
             raise ValueError("extend_audio: seconds must exceed one grid (%d samples at %d Hz), got %r"
                              % (CLIP_SAMPLES, VOCODER_RATE, seconds))
         start = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})["content_token"]
         out = self._long_tokens(text, windows, n, keep_mode, truncation_rate, caption_ids, seed, guidance_scale, negative_text,
-                                start_token=start, purity_steps=purity_steps, purity_weight=purity_weight)
+                                start_token=start, purity_steps=purity_steps, purity_weight=purity_weight,
+                                joint=getattr(_JOINT, "request", False))
         return self._render_long(out, windows, n, samples, save_root, sample_rate,
                                  self._paste_plan("extend_audio", start.shape[0], seconds=seconds, sample_rate=sample_rate))
 
