@@ -137,12 +137,23 @@ EXISTING = {        # the drivers' keywords before purity_steps / purity_weight,
 }
 
 
+PASTES = ["keep_original", "fade_seconds", "match_gain"]
+KEYWORD_ONLY = {    # the drivers' keyword-only tails, written out in their def lines
+    "generate_sample_with_condition": ["level"], "inpaint_audio": ["level"] + PASTES, "continue_audio": ["level"] + PASTES,
+    "generate_long": ["joint", "level"], "extend_audio": ["joint", "level"] + PASTES,
+    "inference_generate_sample_with_condition": ["level"], "generate_sample": ["level"],
+}
+
+
 @pytest.mark.parametrize("name", sorted(EXISTING))
 def test_driver_keywords_come_after_the_existing_ones(name):
     fn = getattr(pipeline.Diffsound, name)
-    ps = list(inspect.signature(getattr(fn, "__wrapped__", fn)).parameters.values())[1:]
+    every = list(inspect.signature(getattr(fn, "__wrapped__", fn)).parameters.values())[1:]
+    ps = [p for p in every if p.kind is inspect.Parameter.POSITIONAL_OR_KEYWORD]
     assert [p.name for p in ps] == EXISTING[name] + ["purity_steps", "purity_weight"]
     assert ps[-2].default is None and ps[-1].default == 0.0
+    assert [p.name for p in every[len(ps):]] == KEYWORD_ONLY[name]
+    assert all(p.kind is inspect.Parameter.KEYWORD_ONLY for p in every[len(ps):])
 
 
 def test_signatures_json_is_still_satisfied():

@@ -7,10 +7,9 @@ vocoder is Generator(n_mel_channels, ngf, n_residual_layers) as `<ckpt_vocoder>/
 tensor-returning form of the reference's file-writing drivers: mel and waveform stay on the GPU and
 the vocoder runs on the whole batch.
 """
-import functools
-import inspect
+import contextlib
 import os
-import threading
+from collections import namedtuple
 
 import torch
 
@@ -468,64 +467,42 @@ def recording_at_rate(item, rate, out_rate, device="cuda"):
     return buf, torch.tensor(lens, dtype=torch.int32).to(device)
 
 
-_LEVEL = threading.local()        # the (spec, recording) of the driver call this thread is inside, read by Diffsound._finish
-_PASTE = threading.local()        # the keep_original request of the driver call this thread is inside (Diffsound._paste_plan)
-_JOINT = threading.local()        # the joint= request of the long-form driver call this thread is inside (Diffsound._long_tokens)
+_Request = namedtuple("_Request", "level recording paste")      # what one driver call asks of the tail the drivers share
 
 
-def _levelled(takes_recording, pastes=False, joint=False):
-    """Gives a driver the keyword `level=None` (level_spec; keyword-only, behind everything the driver declares) and, with
-    pastes=True, `keep_original=None`, `fade_seconds` and `match_gain` (paste_plan).  It is a decorator because levelling
-    and pasting are steps of the tail the drivers share (Diffsound._finish), not of any driver: the call's checked spec
-    -- and, for "match" and for pasting, the `audio` / `audio_rate` the driver was given -- is held for the duration of the call
-    and the tail applies it; a driver's own parameters stay what they were.  level=None and keep_original=None call the
-    driver as it is.  joint=True (the long-form drivers) adds the keyword `joint=False` the same way: the token stage of the call
-    is joint-window sampling (Diffsound._long_tokens reads the request); False calls the driver as it is."""
-    def deco(fn):
-        sig = inspect.signature(fn)
+def _request(self, level, recording=None, keep_original=None, fade_seconds=FADE_SECONDS, match_gain=True):
+    """A driver's `level` (level_spec) and `keep_original` / `fade_seconds` / `match_gain` (paste_plan) keywords, checked ->
+    the _Request its tail is given: (the level spec or None, the recording (audio, audio_rate) the driver takes or None, the
+    paste_plan keywords or None).  The first statement of every driver: a bad keyword raises ValueError before any work."""
+    spec = level_spec(level, recording is not None)
+    _check_keep_original(keep_original, fade_seconds, self.vocoder is not None)
+    paste = dict(keep_original=keep_original, fade_seconds=fade_seconds, match_gain=match_gain)
+    return _Request(spec, recording, None if keep_original is None else paste)
 
-        @functools.wraps(fn)
-        def driver(self, *args, level=None, keep_original=None, fade_seconds=FADE_SECONDS, match_gain=True, **kwargs):
-            if not pastes and (keep_original is not None or fade_seconds != FADE_SECONDS or match_gain is not True):
-                raise TypeError("%s() takes no keep_original / fade_seconds / match_gain: it holds no recording" % fn.__name__)
-            spec = level_spec(level, takes_recording)
-            _check_keep_original(keep_original, fade_seconds, getattr(self, "vocoder", None) is not None)
-            if spec is None and keep_original is None:
-                return fn(self, *args, **kwargs)
-            recording = None
-            if keep_original is not None or spec["strategy"] == "match":
-                given = sig.bind(self, *args, **kwargs).arguments
-                recording = (given["audio"], given.get("audio_rate"))
-            outer = getattr(_LEVEL, "request", None), getattr(_PASTE, "request", None)
-            _LEVEL.request = None if spec is None else (spec, recording)
-            _PASTE.request = None if keep_original is None else {
-                "keep_original": keep_original, "fade_seconds": fade_seconds, "match_gain": match_gain, "recording": recording}
-            try:
-                return fn(self, *args, **kwargs)
-            finally:
-                _LEVEL.request, _PASTE.request = outer
-        extra = [inspect.Parameter("level", inspect.Parameter.KEYWORD_ONLY, default=None)]
-        if pastes:
-            extra += [inspect.Parameter("keep_original", inspect.Parameter.KEYWORD_ONLY, default=None),
-                      inspect.Parameter("fade_seconds", inspect.Parameter.KEYWORD_ONLY, default=FADE_SECONDS),
-                      inspect.Parameter("match_gain", inspect.Parameter.KEYWORD_ONLY, default=True)]
-        if joint:
-            levelled = driver
 
-            @functools.wraps(fn)
-            def driver(self, *args, joint=False, **kwargs):
-                if not joint:
-                    return levelled(self, *args, **kwargs)
-                outer = getattr(_JOINT, "request", False)
-                _JOINT.request = True
-                try:
-                    return levelled(self, *args, **kwargs)
-                finally:
-                    _JOINT.request = outer
-            extra.insert(0, inspect.Parameter("joint", inspect.Parameter.KEYWORD_ONLY, default=False))
-        driver.__signature__ = sig.replace(parameters=list(sig.parameters.values()) + extra)
-        return driver
-    return deco
+def _sample_type(truncation_rate, fast=False, purity_steps=None, purity_weight=0.0):
+    """the drivers' truncation_rate / fast / purity_steps / purity_weight -> DALLE's sample_type "top{rate}r[,fast{n - 1}][,purity..]";
+    fast=n is skip_step n - 1, spelled like the reference's drivers"""
+    skip = ",fast" + str(fast - 1) if fast else ""
+    return purity_sample_type("top" + str(truncation_rate) + "r" + skip, purity_steps, purity_weight)
+
+
+def _numbered_stems(root, n):
+    """`root` (made where missing) -> the n path stems root/000000, root/000001, ..."""
+    os.makedirs(root, exist_ok=True)
+    return [os.path.join(root, str(i).zfill(6)) for i in range(n)]
+
+
+def _write_clips(mel01, wave, rate, stems):
+    """clip i of mel01 f32[B, 80, F] -> `{stems[i]}.npy` and, with a waveform f32[B, 1, T] at `rate` (None: 22 050 Hz), of wave ->
+    `{stems[i]}.wav` (PCM_24), clip by clip -> stems"""
+    import numpy as np
+    m_, w_ = mel01.cpu().numpy(), None if wave is None else wave[:, 0].cpu().numpy()
+    for i, stem in enumerate(stems):
+        np.save(stem + ".npy", m_[i])
+        if w_ is not None:
+            write_wav_pcm24(stem + ".wav", w_[i], VOCODER_RATE if rate is None else int(rate))
+    return stems
 
 
 class Diffsound:
@@ -556,11 +533,10 @@ class Diffsound:
             for p in self.vocoder.parameters():
                 p.requires_grad = False
 
-    @_levelled(False)
     @torch.no_grad()
     def generate_sample_with_condition(self, cond, truncation_rate=0.85, replicate=1, fast=False, caption_ids=None,
                                        seed=None, sample_rate=None, guidance_scale=None, negative_text=None, purity_steps=None,
-                                       purity_weight=0.0):
+                                       purity_weight=0.0, *, level=None):
         """Captions -> (mel01 f32[B,80,848], wave f32[B,1,217088] -- None without a vocoder --, tokens), everything left on the GPU.
         `cond` is a list of caption strings (needs the text stage: tokenizer + CLIP in the config),
         token ids i64[B,77], or caption embeddings f32[B,77,512].  fast=n selects the skip-step sampler with
@@ -574,32 +550,35 @@ class Diffsound:
         purity_steps = S: an S-step purity-prior chain instead of the reference's 100-step loop (DiffusionTransformer.
         sample_purity: 1 <= S <= 265 forwards, confident positions first, no [MASK] left at any S), purity_weight its
         sharpening weight; None: today's path, untouched.  Not together with fast.  Its effect on audio quality is unmeasured.
-        level= (keyword-only, on this and every driver that returns or writes a waveform; _levelled, level_spec): bring every
+        level= (keyword-only, on this and every driver that returns or writes a waveform; level_spec): bring every
         clip to a level on the device, at the output rate -- "peak" (-1 dBFS), "rms" (-20 dBFS), "loudness" (-23 LUFS, BS.1770-4)
         or a dict {strategy, target, ceiling_db, limit}, under a true-peak ceiling of -1 dBFS (audio.level: a static cut, or
         with limit=True the look-ahead limiter); the drivers that take a recording also accept "match": the recording's own
         loudness.  None: the vocoder's own level, no launch.  Mel and tokens are never affected; generate_best_of levels the
         winners only."""
-        if isinstance(cond, (list, tuple, str)):
-            batch = {"text": [cond] if isinstance(cond, str) else list(cond)}
-        elif cond.dtype == torch.long:
-            batch = {"condition_token": cond}
-        else:
-            batch = {"condition_embed_token": cond}
-        if caption_ids is not None:
-            batch["caption_ids"] = caption_ids
-        if seed is not None:
-            batch["seed"] = seed
-        if negative_text is not None:
-            batch["negative_text"] = negative_text
-        out = self.model.generate_content(batch=batch, filter_ratio=0, replicate=replicate, content_ratio=1,
-                                          return_att_weight=False, guidance_scale=guidance_scale,
-                                          sample_type=purity_sample_type(
-                                              "top" + str(truncation_rate) + ("r,fast" + str(fast - 1) if fast else "r"),
-                                              purity_steps, purity_weight))
+        request = _request(self, level)
+        out = self.model.generate_content(batch=self._batch(cond, caption_ids, seed, negative_text), filter_ratio=0,
+                                          replicate=replicate, content_ratio=1, return_att_weight=False,
+                                          guidance_scale=guidance_scale,
+                                          sample_type=_sample_type(truncation_rate, fast, purity_steps, purity_weight))
         mel = out["content"]                                   # [B,1,80,848] in ~[-1,1]
         wave = None if self.vocoder is None else self.vocoder(mel[:, 0], scale=0.5, shift=0.5)   # spec = (x+1)/2, :182
-        return (mel[:, 0] + 1) / 2, self._finish(wave, sample_rate), out["content_token"]
+        return (mel[:, 0] + 1) / 2, self._finish(wave, sample_rate, request), out["content_token"]
+
+    @staticmethod
+    def _batch(text, caption_ids=None, seed=None, negative_text=None):
+        """The batch dict of a model call: the caption(s) -- strings, token ids i64[B,77] or embeddings f32[B,77,512]; None: no
+        caption, the tracks of a scene carry them -- and those of the noise / guidance keywords that were given."""
+        if text is None:
+            batch = {}
+        elif isinstance(text, (list, tuple, str)):
+            batch = {"text": [text] if isinstance(text, str) else list(text)}
+        else:
+            batch = {"condition_token": text} if text.dtype == torch.long else {"condition_embed_token": text}
+        for key, value in (("caption_ids", caption_ids), ("seed", seed), ("negative_text", negative_text)):
+            if value is not None:
+                batch[key] = value
+        return batch
 
     @staticmethod
     def _at_rate(wave, sample_rate):
@@ -609,14 +588,12 @@ class Diffsound:
         from . import audio
         return audio.resample(wave[:, 0], VOCODER_RATE, sample_rate)[:, None]
 
-    def _paste_plan(self, driver, batch, **where):
-        """paste_plan for the driver call this thread is inside (None without keep_original) + the recording it was given"""
-        request = getattr(_PASTE, "request", None)
-        if request is None:
+    def _paste_plan(self, request, driver, batch, **where):
+        """paste_plan for the `keep_original` of a driver call's request (None without one) + the recording the driver was given"""
+        if request.paste is None:
             return None
-        plan = paste_plan(driver, request["keep_original"], batch=batch, fade_seconds=request["fade_seconds"],
-                          match_gain=request["match_gain"], has_vocoder=self.vocoder is not None, **where)
-        return dict(plan, recording=request["recording"])
+        plan = paste_plan(driver, batch=batch, has_vocoder=self.vocoder is not None, **request.paste, **where)
+        return dict(plan, recording=request.recording)
 
     @staticmethod
     def _paste_mel(mel, plan):
@@ -643,104 +620,87 @@ class Diffsound:
                            fade_len=p["fade_len"], curve="equal_power", rec_len=lens, match_gain=plan["match_gain"])[:, None]
 
     @staticmethod
-    def _finish(wave, sample_rate, paste=None):
+    def _finish(wave, sample_rate, request, paste=None):
         """The tail every driver shares: the vocoder's f32[B,1,T] -> at `sample_rate` (_at_rate) -> the recording's samples
-        pasted over it (paste = a paste_plan of mode "audio") -> brought to the level the driver call asked for (`level=`,
-        _levelled), at that rate, on the device (audio.level).  No plan and no `level`: no launch, the waveform as it is."""
-        return Diffsound._level(Diffsound._paste_audio(Diffsound._at_rate(wave, sample_rate), paste), sample_rate)
+        pasted over it (paste = a paste_plan of mode "audio") -> brought to the level the driver call asked for (request =
+        its _Request), at that rate, on the device (audio.level).  No plan and no `level`: no launch, the waveform as it is."""
+        return Diffsound._level(Diffsound._paste_audio(Diffsound._at_rate(wave, sample_rate), paste), sample_rate, request)
 
     @staticmethod
-    def _level(wave, sample_rate):
+    def _level(wave, sample_rate, request):
         """_finish's last step on a waveform that is already at `sample_rate`"""
-        request = getattr(_LEVEL, "request", None)
-        if wave is None or request is None:
+        spec, recording = request.level, request.recording
+        if wave is None or spec is None:
             return wave
         from . import audio
-        spec, recording = request
         rate = VOCODER_RATE if sample_rate is None else int(sample_rate)
         ref = recording_loudness(recording[0], recording[1], wave.device) if spec["strategy"] == "match" else None
         out, _ = audio.level(wave[:, 0], rate, spec["strategy"], target=spec["target"], ceiling_db=spec["ceiling_db"],
                              reference=ref, limit=spec.get("limit"))
         return out[:, None]
 
-    @_levelled(True)
     @torch.no_grad()
-    def generate_sample_from_audio(self, audio, text, filter_ratio=0.5, truncation_rate=0.85, save_root=None, audio_rate=None):
+    def generate_sample_from_audio(self, audio, text, filter_ratio=0.5, truncation_rate=0.85, save_root=None, audio_rate=None,
+                                   *, level=None):
         """Re-sample given recordings under new captions: audio (f32[B, T] on the device, or a list of `.wav` paths / host
         arrays; audio_rate = their sample rate, one or a list, None = 22 050 Hz / the files' own: another rate is resampled on
         the device first) -> mel (modeling/melspec.py, one HIP launch) -> VQ tokens -> diffused forward to
         t = int(T * filter_ratio) - 1 and denoised from there under `text` (a list of B captions, token ids or embeddings, as in
         generate_sample_with_condition) -> decode -> vocoder.  Returns (mel01 f32[B,80,848], wave f32[B,1,217088] or None,
         tokens); with save_root also writes `{i:06d}.npy` and, with a vocoder, `{i:06d}.wav` like the other drivers."""
+        request = _request(self, level, (audio, audio_rate))
         model = self.model
-        cond = model.prepare_condition(self._caption_batch(text))
+        cond = model.prepare_condition(self._batch(text))
         content = model.prepare_content({"audio": audio, "audio_rate": audio_rate})
-        tr = model.transformer
-        keep = tr.truncation_r, tr.truncation_k
-        tr.truncation_r, tr.truncation_k = float(truncation_rate), None
-        try:
-            out = tr.sample(condition_token=cond.get("condition_token"), condition_mask=cond.get("condition_mask"),
-                            condition_embed=cond.get("condition_embed_token"), content_token=content["content_token"],
-                            filter_ratio=filter_ratio, print_log=False)
-        finally:
-            tr.truncation_r, tr.truncation_k = keep
-        return self._render(out["content_token"], content["content_quant"].shape, save_root)
+        with self._truncation(truncation_rate):
+            out = model.transformer.sample(condition_token=cond.get("condition_token"), condition_mask=cond.get("condition_mask"),
+                                           condition_embed=cond.get("condition_embed_token"),
+                                           content_token=content["content_token"], filter_ratio=filter_ratio, print_log=False)
+        return self._render(request, out["content_token"], content["content_quant"].shape, save_root)
 
-    def _render(self, tokens, zshape, save_root=None, sample_rate=None, paste=None):
+    @contextlib.contextmanager
+    def _truncation(self, truncation_rate, forward=False):
+        """The model's truncation state at this call's rate inside the block (forward: with truncation_forward on, as a chain
+        through DALLE needs it) and what it was after it, also when the block raises: the facade installs a rate once and
+        keeps it."""
+        model, tr = self.model, self.model.transformer
+        saved = tr.truncation_r, tr.truncation_k, tr.repeat_rate, model.truncation_forward
+        tr.truncation_r, tr.truncation_k = float(truncation_rate), None
+        if forward:
+            model.truncation_forward = True
+        try:
+            yield
+        finally:
+            tr.truncation_r, tr.truncation_k, tr.repeat_rate, model.truncation_forward = saved
+
+    def _render(self, request, tokens, zshape, save_root=None, sample_rate=None, paste=None):
         """tokens -> decode (-> the recording's mel pasted: paste = a paste_plan) -> vocoder (-> sample_rate -> the recording's
-        samples pasted -> level: _finish): the tail the audio-in drivers share.  Returns (mel01, wave or None, tokens); with
-        save_root also writes `{i:06d}.npy` and, with a vocoder, `{i:06d}.wav`."""
-        import numpy as np
+        samples pasted -> level, as the driver call's request says: _finish): the tail the audio-in drivers share.  Returns
+        (mel01, wave or None, tokens); with save_root also writes `{i:06d}.npy` and, with a vocoder, `{i:06d}.wav`."""
         mel = self.model.decode_to_img(tokens, zshape)
         if paste is not None:
             mel = self._paste_mel(mel[:, 0], paste)[:, None]
         wave = None if self.vocoder is None else self.vocoder(mel[:, 0], scale=0.5, shift=0.5)
-        wave = self._finish(wave, sample_rate, paste)
+        wave = self._finish(wave, sample_rate, request, paste)
         mel01 = (mel[:, 0] + 1) / 2
         if save_root is not None:
-            os.makedirs(save_root, exist_ok=True)
-            m_, w_ = mel01.cpu().numpy(), None if wave is None else wave[:, 0].cpu().numpy()
-            for i in range(m_.shape[0]):
-                path = os.path.join(save_root, str(i).zfill(6))
-                np.save(path + ".npy", m_[i])
-                if w_ is not None:
-                    write_wav_pcm24(path + ".wav", w_[i], VOCODER_RATE if sample_rate is None else int(sample_rate))
+            _write_clips(mel01, wave, sample_rate, _numbered_stems(save_root, mel01.shape[0]))
         return mel01, wave, tokens
-
-    @staticmethod
-    def _caption_batch(text):
-        if isinstance(text, (list, tuple, str)):
-            return {"text": [text] if isinstance(text, str) else list(text)}
-        return {"condition_token": text} if text.dtype == torch.long else {"condition_embed_token": text}
 
     def _inpaint_tokens(self, tokens, keep, text, keep_mode, truncation_rate, caption_ids, seed, guidance_scale=None,
                         negative_text=None, purity_steps=None, purity_weight=0.0, tracks=None):
-        """DALLE.inpaint_content at this call's truncation rate (the facade installs a rate once and keeps it: set and
-        restored around the call, like generate_sample_from_audio does)."""
-        batch = dict({} if tracks is not None and text is None else self._caption_batch(text), content_token=tokens)
-        if caption_ids is not None:
-            batch["caption_ids"] = caption_ids
-        if seed is not None:
-            batch["seed"] = seed
-        if negative_text is not None:
-            batch["negative_text"] = negative_text
-        model, tr = self.model, self.model.transformer
-        saved = tr.truncation_r, tr.truncation_k, tr.repeat_rate, model.truncation_forward
-        tr.truncation_r, tr.truncation_k, model.truncation_forward = float(truncation_rate), None, True
-        try:
-            out = model.inpaint_content(batch=batch, keep_mask=keep, keep_mode=keep_mode, guidance_scale=guidance_scale,
-                                        **({} if tracks is None else {"tracks": tracks}),
-                                        sample_type=purity_sample_type("top" + str(truncation_rate) + "r", purity_steps,
-                                                                       purity_weight))
-        finally:
-            tr.truncation_r, tr.truncation_k, tr.repeat_rate, model.truncation_forward = saved
+        """DALLE.inpaint_content at this call's truncation rate (_truncation); text None: the captions are the tracks'."""
+        batch = dict(self._batch(text, caption_ids, seed, negative_text), content_token=tokens)
+        with self._truncation(truncation_rate, forward=True):
+            out = self.model.inpaint_content(batch=batch, keep_mask=keep, keep_mode=keep_mode, guidance_scale=guidance_scale,
+                                             **({} if tracks is None else {"tracks": tracks}),
+                                             sample_type=_sample_type(truncation_rate, False, purity_steps, purity_weight))
         return out["content_token"]
 
-    @_levelled(True, pastes=True)
     @torch.no_grad()
     def inpaint_audio(self, audio, text, spans, keep_mode="clamp", truncation_rate=0.85, save_root=None, audio_rate=None,
                       caption_ids=None, seed=None, sample_rate=None, guidance_scale=None, negative_text=None, purity_steps=None,
-                      purity_weight=0.0):
+                      purity_weight=0.0, *, level=None, keep_original=None, fade_seconds=FADE_SECONDS, match_gain=True):
         """Regenerate time spans of given recordings under a caption and keep the rest: audio / audio_rate / text as in
         generate_sample_from_audio; spans = the (t0, t1) seconds to regenerate, shared or one list per clip
         (spans_to_keep_mask: whole grid columns of 4096 samples at 22 050 Hz).  The recording is encoded to its 5 x 53 tokens,
@@ -769,38 +729,37 @@ class Diffsound:
         of the rendering to the recording and no limiter.
         level= as in generate_sample_with_condition; "match": the result is brought to the integrated loudness of the
         recording, measured at the recording's own rate and length."""
+        request = _request(self, level, (audio, audio_rate), keep_original, fade_seconds, match_gain)
         content = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})
         known = content["content_token"]
         keep = spans_to_keep_mask(spans, known.shape[0], known.device)
         tokens = self._inpaint_tokens(known, keep, text, keep_mode, truncation_rate, caption_ids, seed, guidance_scale,
                                       negative_text, purity_steps, purity_weight)
-        return self._render(tokens, content["content_quant"].shape, save_root, sample_rate,
-                            self._paste_plan("inpaint_audio", known.shape[0], spans=spans, sample_rate=sample_rate))
+        return self._render(request, tokens, content["content_quant"].shape, save_root, sample_rate,
+                            self._paste_plan(request, "inpaint_audio", known.shape[0], spans=spans, sample_rate=sample_rate))
 
-    @_levelled(True, pastes=True)
     @torch.no_grad()
     def inpaint_scene(self, audio, tracks, spans, scale=3.0, keep_mode="clamp", truncation_rate=0.85, save_root=None,
-                      audio_rate=None, caption_ids=None, seed=None, sample_rate=None, negative_text=None):
+                      audio_rate=None, caption_ids=None, seed=None, sample_rate=None, negative_text=None,
+                      *, level=None, keep_original=None, fade_seconds=FADE_SECONDS, match_gain=True):
         """inpaint_audio under a scene instead of one caption: the spans are regenerated under `tracks` -- caption tracks as
         in generate_scene, [(text, t0, t1[, scale]), ...] in the clip's own seconds, one scene or one per clip; a track that
         names no scale gets `scale` -- and the rest of the recording is kept, as tokens, exactly (keep_original= as in
         inpaint_audio: also as its own mel, or its own samples).  The other arguments and the return are inpaint_audio's.  (A method of its own: inpaint_audio's keywords are what they were.)"""
+        request = _request(self, level, (audio, audio_rate), keep_original, fade_seconds, match_gain)
         content = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})
         known = content["content_token"]
         keep = spans_to_keep_mask(spans, known.shape[0], known.device)
-        is_scenes = len(tracks) > 0 and isinstance(tracks[0], (list, tuple)) and len(tracks[0]) > 0 \
-            and isinstance(tracks[0][0], (list, tuple))
-        trk = self._scene(tracks, GRID_COLS, None if is_scenes else known.shape[0], scale)
         tokens = self._inpaint_tokens(known, keep, None, keep_mode, truncation_rate, caption_ids, seed, None, negative_text,
-                                      tracks=trk)
-        return self._render(tokens, content["content_quant"].shape, save_root, sample_rate,
-                            self._paste_plan("inpaint_scene", known.shape[0], spans=spans, sample_rate=sample_rate))
+                                      tracks=self._scene(tracks, GRID_COLS, known.shape[0], scale))
+        return self._render(request, tokens, content["content_quant"].shape, save_root, sample_rate,
+                            self._paste_plan(request, "inpaint_scene", known.shape[0], spans=spans, sample_rate=sample_rate))
 
-    @_levelled(True, pastes=True)
     @torch.no_grad()
     def continue_audio(self, audio, text, keep_seconds, keep_mode="clamp", truncation_rate=0.85, save_root=None,
                        audio_rate=None, caption_ids=None, seed=None, sample_rate=None, guidance_scale=None, negative_text=None,
-                       purity_steps=None, purity_weight=0.0):
+                       purity_steps=None, purity_weight=0.0, *, level=None, keep_original=None, fade_seconds=FADE_SECONDS,
+                       match_gain=True):
         """Generate the clip that follows given recordings: the last ceil(keep_seconds 22050 / 4096) token columns of the
         recording become the first columns of a new 10-s clip (a shift by 5 (53 - n) tokens), held, and the remaining columns
         are generated under `text`.  Arguments and return as inpaint_audio.  By default the new clip's head is the codec's
@@ -808,68 +767,57 @@ class Diffsound:
         it the recording's own mel frames from 16 (53 - n) on / its own samples from 4096 (53 - n) + RECORDING_OFFSET on (at
         22 050 Hz; scaled and rounded once at another output rate).  This returns the NEW clip only; extend_audio returns the
         recording and what follows it as one clip, joined in the mel domain."""
+        request = _request(self, level, (audio, audio_rate), keep_original, fade_seconds, match_gain)
         content = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})
         known, keep = continuation_tokens(content["content_token"], continuation_columns(keep_seconds))
         tokens = self._inpaint_tokens(known, keep, text, keep_mode, truncation_rate, caption_ids, seed, guidance_scale,
                                       negative_text, purity_steps, purity_weight)
-        return self._render(tokens, content["content_quant"].shape, save_root, sample_rate,
-                            self._paste_plan("continue_audio", known.shape[0], keep_seconds=keep_seconds, sample_rate=sample_rate))
+        return self._render(request, tokens, content["content_quant"].shape, save_root, sample_rate,
+                            self._paste_plan(request, "continue_audio", known.shape[0], keep_seconds=keep_seconds,
+                                             sample_rate=sample_rate))
 
-    def _long_tokens(self, text, windows, overlap_cols, keep_mode, truncation_rate, caption_ids, seed,
-                     guidance_scale, negative_text, start_token=None, purity_steps=None, purity_weight=0.0, tracks=None,
-                     sample_type=None, joint=False, ring=False):
-        """DALLE.generate_long_content under this call's caption / noise keywords (the truncation rate is the call's: the
-        facade saves and restores the model's own)."""
-        batch = {} if tracks is not None and text is None else dict(self._caption_batch(text))
-        if caption_ids is not None:
-            batch["caption_ids"] = caption_ids
-        if seed is not None:
-            batch["seed"] = seed
-        if negative_text is not None:
-            batch["negative_text"] = negative_text
-        if sample_type is None:
-            sample_type = purity_sample_type("top" + str(truncation_rate) + "r", purity_steps, purity_weight)
+    def _long_tokens(self, text, windows, overlap_cols, keep_mode, sample_type, caption_ids, seed, guidance_scale, negative_text,
+                     start_token=None, tracks=None, joint=False, ring=False):
+        """DALLE.generate_long_content under this call's caption / noise keywords and sample type (the model saves and restores
+        its own); text None: the captions are the tracks'."""
         kw = {} if tracks is None else {"tracks": tracks}       # (without tracks: the call as it always was)
         if joint:
             kw.update(joint=True, ring=ring)                    # (likewise)
-        return self.model.generate_long_content(batch=batch, windows=windows, overlap_cols=overlap_cols, keep_mode=keep_mode,
-                                                sample_type=sample_type, guidance_scale=guidance_scale, start_token=start_token,
-                                                **kw)
+        return self.model.generate_long_content(batch=self._batch(text, caption_ids, seed, negative_text), windows=windows,
+                                                overlap_cols=overlap_cols, keep_mode=keep_mode, sample_type=sample_type,
+                                                guidance_scale=guidance_scale, start_token=start_token, **kw)
 
     VOCODER_CHUNK_FRAMES = 64 * 848       # mel frames per vocoder call of a long clip: the largest call the benchmarks run
 
-    def _render_long(self, out, windows, overlap_cols, samples, save_root, sample_rate, paste=None):
+    def _vocode_long(self, mel):
+        """ONE vocoder pass per clip over its whole stitched mel f32[B, 80, F] -> f32[B, 1, 256 F] (None without a vocoder).
+        Clips go through the vocoder in batch chunks of at most VOCODER_CHUNK_FRAMES mel frames; a clip is never split."""
+        if self.vocoder is None:
+            return None
+        step = max(1, self.VOCODER_CHUNK_FRAMES // mel.shape[2])
+        return torch.cat([self.vocoder(mel[i:i + step], scale=0.5, shift=0.5) for i in range(0, mel.shape[0], step)], 0)
+
+    def _render_long(self, request, out, windows, overlap_cols, samples, save_root, sample_rate, paste=None):
         """window mels -> ds_mel_stitch (codec domain) (-> the recording's mel pasted: paste = a paste_plan; its samples
-        pasted in _finish) -> ONE vocoder pass per clip over its whole stitched mel -> both cut to
-        `samples` (the vocoder's reflection at the far end lies past the cut) -> sample_rate -> level (_finish), files.  Clips go through the
-        vocoder in batch chunks of at most VOCODER_CHUNK_FRAMES mel frames; a clip is never split."""
-        import numpy as np
+        pasted in _finish) -> the vocoder (_vocode_long) -> both cut to `samples` (the vocoder's reflection at the far end lies
+        past the cut) -> sample_rate -> paste -> level, as the driver call's request says (_finish), files."""
         from . import audio
         win = out["content"]                                          # [B W, 1, 80, 848], clip-major: index b W + w
         B = win.shape[0] // windows
         mel = audio.stitch_mel(win.reshape(B, windows, win.shape[2], win.shape[3]), (GRID_COLS - overlap_cols) * COLUMN_FRAMES)
         mel = self._paste_mel(mel, paste)
-        wave = None
-        if self.vocoder is not None:
-            step = max(1, self.VOCODER_CHUNK_FRAMES // mel.shape[2])
-            wave = torch.cat([self.vocoder(mel[i:i + step], scale=0.5, shift=0.5) for i in range(0, B, step)], 0)
-            wave = self._finish(wave[:, :, :samples].contiguous(), sample_rate, paste)
+        wave = self._vocode_long(mel)
+        if wave is not None:
+            wave = self._finish(wave[:, :, :samples].contiguous(), sample_rate, request, paste)
         mel01 = ((mel + 1) / 2)[:, :, :-(-samples // 256)].contiguous()
         if save_root is not None:
-            os.makedirs(save_root, exist_ok=True)
-            m_, w_ = mel01.cpu().numpy(), None if wave is None else wave[:, 0].cpu().numpy()
-            for i in range(B):
-                path = os.path.join(save_root, str(i).zfill(6))
-                np.save(path + ".npy", m_[i])
-                if w_ is not None:
-                    write_wav_pcm24(path + ".wav", w_[i], VOCODER_RATE if sample_rate is None else int(sample_rate))
+            _write_clips(mel01, wave, sample_rate, _numbered_stems(save_root, B))
         return mel01, wave, out["content_token"]
 
-    @_levelled(False, joint=True)
     @torch.no_grad()
     def generate_long(self, text, seconds, overlap_seconds=2.4, truncation_rate=0.85, keep_mode="clamp", caption_ids=None,
                       seed=None, sample_rate=None, guidance_scale=None, negative_text=None, save_root=None, purity_steps=None,
-                      purity_weight=0.0):
+                      purity_weight=0.0, *, joint=False, level=None):
         """Captions -> clips of `seconds` (up to 16 windows, about two minutes): (mel01 f32[B, 80, ceil(samples / 256)], wave
         f32[B, 1, samples] -- None without a vocoder --, tokens i64[B, W, 265]), samples = round(seconds 22050).  The clip is
         generated as W overlapping windows of one 5 x 53 grid each (long_plan): window 0 like generate_sample_with_condition
@@ -882,15 +830,16 @@ class Diffsound:
         in the other drivers; purity_steps / purity_weight: every window's chain is a purity-prior chain
         (generate_sample_with_condition; keep_mode "clamp" only).  seconds up to one grid (217 088 samples): W = 1, the same path without a held chain.
 
-        joint=True (keyword-only, given by _levelled like level=) switches the TOKEN stage to joint-window sampling
+        joint=True (keyword-only, like level=) switches the TOKEN stage to joint-window sampling
         (DALLE.generate_long_content: one chain at batch B W on a shared canvas instead of W chains at batch B, every window
         seeing both neighbours); the rendering is unchanged.  purity_steps and keep_mode "renoise" are not built for it.
 
         The overlap is a design choice whose audible quality is unmeasured (long_plan); so is how joint clips sound."""
+        request = _request(self, level)
         windows, n, _, samples = long_plan(seconds, overlap_seconds)
-        out = self._long_tokens(text, windows, n, keep_mode, truncation_rate, caption_ids, seed, guidance_scale, negative_text,
-                                purity_steps=purity_steps, purity_weight=purity_weight, joint=getattr(_JOINT, "request", False))
-        return self._render_long(out, windows, n, samples, save_root, sample_rate)
+        out = self._long_tokens(text, windows, n, keep_mode, _sample_type(truncation_rate, False, purity_steps, purity_weight),
+                                caption_ids, seed, guidance_scale, negative_text, joint=joint)
+        return self._render_long(request, out, windows, n, samples, save_root, sample_rate)
 
     def _loop_rendering(self, win, windows, overlap_cols, sample_rate=None):
         """The UNCUT rendering of a ring: the decoded windows win f32[B W, 1, 80, 848] (clip-major) stitched as
@@ -904,17 +853,11 @@ class Diffsound:
         order = [(w - LOOP_LEAD_HOPS) % windows for w in range(windows + 2 * LOOP_LEAD_HOPS)]
         mel = audio.stitch_mel(win.reshape(B, windows, win.shape[2], win.shape[3])[:, order].contiguous(),
                                (GRID_COLS - overlap_cols) * COLUMN_FRAMES)
-        wave = None
-        if self.vocoder is not None:
-            step = max(1, self.VOCODER_CHUNK_FRAMES // mel.shape[2])
-            wave = torch.cat([self.vocoder(mel[i:i + step], scale=0.5, shift=0.5) for i in range(0, B, step)], 0)
-            wave = self._at_rate(wave, sample_rate)
-        return mel, wave
+        return mel, self._at_rate(self._vocode_long(mel), sample_rate)
 
-    @_levelled(False)
     @torch.no_grad()
     def generate_loop(self, text, seconds, overlap_seconds=2.4, truncation_rate=0.85, fast=False, caption_ids=None, seed=None,
-                      guidance_scale=None, negative_text=None, sample_rate=None, save_root=None):
+                      guidance_scale=None, negative_text=None, sample_rate=None, save_root=None, *, level=None):
         """Captions -> seamless loops of about `seconds` (ambiences, engines, room tone): (mel01 f32[B, 80, 16 C], wave
         f32[B, 1, 4096 C rate / 22050] -- None without a vocoder --, tokens i64[B, W, 265], seconds_made).  loop_plan picks
         W >= 2 windows and the ring of C = W h whole columns (the length snaps UP to a multiple of the hop h = 53 - n columns;
@@ -932,51 +875,45 @@ class Diffsound:
         built).  fast / caption_ids / seed / guidance_scale / negative_text / save_root as in the other drivers.
 
         How loops SOUND is unmeasured: no trained checkpoint has been available to this project."""
-        import numpy as np
-        request = getattr(_LEVEL, "request", None)
-        if request is not None and request[0].get("limit"):
+        request = _request(self, level)
+        if request.level is not None and request.level.get("limit"):
             raise ValueError("generate_loop: level= with limit is not built for loops (the limiter's gain curve is not periodic)")
         windows, n, cols, samples = loop_plan(seconds, overlap_seconds)
         hop = GRID_COLS - n
         off, period = loop_cut(cols, hop, sample_rate)                 # the rate rule, before anything runs
-        out = self._long_tokens(text, windows, n, "clamp", truncation_rate, caption_ids, seed, guidance_scale, negative_text,
-                                sample_type="top" + str(truncation_rate) + ("r,fast" + str(fast - 1) if fast else "r"),
-                                joint=True, ring=True)
+        out = self._long_tokens(text, windows, n, "clamp", _sample_type(truncation_rate, fast), caption_ids, seed, guidance_scale,
+                                negative_text, joint=True, ring=True)
         mel, wave = self._loop_rendering(out["content"], windows, n, sample_rate)
-        B = mel.shape[0]
         lead = LOOP_LEAD_HOPS * hop * COLUMN_FRAMES
         if wave is not None:
-            wave = self._level(wave[:, :, off:off + period].contiguous(), sample_rate)
+            wave = self._level(wave[:, :, off:off + period].contiguous(), sample_rate, request)
         mel01 = ((mel + 1) / 2)[:, :, lead:lead + cols * COLUMN_FRAMES].contiguous()
         if save_root is not None:
-            os.makedirs(save_root, exist_ok=True)
-            m_, w_ = mel01.cpu().numpy(), None if wave is None else wave[:, 0].cpu().numpy()
-            for i in range(B):
-                path = os.path.join(save_root, str(i).zfill(6))
-                np.save(path + ".npy", m_[i])
-                if w_ is not None:
-                    write_wav_pcm24(path + ".wav", w_[i], VOCODER_RATE if sample_rate is None else int(sample_rate))
+            _write_clips(mel01, wave, sample_rate, _numbered_stems(save_root, mel01.shape[0]))
         return mel01, wave, out["content_token"], samples / VOCODER_RATE
 
     SCENE_SCALE = 3.0     # generate_scene's default track weight: the scale the guidance tests run at; a design choice
 
     @staticmethod
     def _scene(tracks, total_cols=GRID_COLS, batch=None, scale=None):
-        """tracks of generate_scene / inpaint_audio -> the dict DALLE's `tracks` keyword takes (None stays None); a track that
-        names no scale gets `scale` (default SCENE_SCALE)"""
+        """tracks of generate_scene / inpaint_scene -> the dict DALLE's `tracks` keyword takes (None stays None); a track that
+        names no scale gets `scale` (default SCENE_SCALE).  batch: the clips ONE scene is shared by; a list of scenes brings
+        its own count and batch is not looked at."""
         if tracks is None:
             return None
+        is_seq = lambda x: isinstance(x, (list, tuple))
+        if len(tracks) > 0 and is_seq(tracks[0]) and len(tracks[0]) > 0 and is_seq(tracks[0][0]):      # a list of scenes
+            batch = None
         scale = Diffsound.SCENE_SCALE if scale is None else float(scale)
-        fill = lambda t: tuple(t) + (scale,) if isinstance(t, (list, tuple)) and len(t) == 3 and isinstance(t[0], str) else t
-        tracks = [fill(t) if not (isinstance(t, (list, tuple)) and t and isinstance(t[0], (list, tuple))) else [fill(q) for q in t]
-                  for t in tracks]
+        fill = lambda t: tuple(t) + (scale,) if is_seq(t) and len(t) == 3 and isinstance(t[0], str) else t
+        tracks = [fill(t) if not (is_seq(t) and t and is_seq(t[0])) else [fill(q) for q in t] for t in tracks]
         text, weight = track_weights(tracks, total_cols, batch)
         return {"text": text, "weight": weight}
 
-    @_levelled(False)
     @torch.no_grad()
     def generate_scene(self, tracks, seconds=None, scale=3.0, overlap_seconds=2.4, truncation_rate=0.85, keep_mode="clamp",
-                       fast=False, caption_ids=None, seed=None, negative_text=None, sample_rate=None, save_root=None):
+                       fast=False, caption_ids=None, seed=None, negative_text=None, sample_rate=None, save_root=None,
+                       *, level=None):
         """A scene instead of one caption: tracks = [(text, t0, t1[, scale]), ...] in seconds (track_weights: t1 None = to the
         end; at most 4 tracks), one scene or a list of B scenes -> what generate_long returns: (mel01, wave or None, tokens
         i64[B, W, 265]).  Every sampler step evaluates the denoiser under each track's caption and under the null condition
@@ -991,19 +928,17 @@ class Diffsound:
 
         No trained checkpoint has been available to this project: what scenes SOUND like, and whether event order and
         placement improve over one caption, is unmeasured."""
+        request = _request(self, level)
         windows, n, total, samples = long_plan(CLIP_SAMPLES / VOCODER_RATE if seconds is None else seconds, overlap_seconds)
-        is_scenes = len(tracks) > 0 and isinstance(tracks[0], (list, tuple)) and len(tracks[0]) > 0 \
-            and isinstance(tracks[0][0], (list, tuple))
-        trk = self._scene(tracks, total, None if is_scenes else 1, scale)
-        out = self._long_tokens(None, windows, n, keep_mode, truncation_rate, caption_ids, seed, None, negative_text, tracks=trk,
-                                sample_type="top" + str(truncation_rate) + ("r,fast" + str(fast - 1) if fast else "r"))
-        return self._render_long(out, windows, n, samples, save_root, sample_rate)
+        out = self._long_tokens(None, windows, n, keep_mode, _sample_type(truncation_rate, fast), caption_ids, seed, None,
+                                negative_text, tracks=self._scene(tracks, total, 1, scale))
+        return self._render_long(request, out, windows, n, samples, save_root, sample_rate)
 
-    @_levelled(True, pastes=True, joint=True)
     @torch.no_grad()
     def extend_audio(self, audio, text, seconds, overlap_seconds=2.4, truncation_rate=0.85, keep_mode="clamp", caption_ids=None,
                      seed=None, sample_rate=None, guidance_scale=None, negative_text=None, save_root=None, audio_rate=None,
-                     purity_steps=None, purity_weight=0.0):
+                     purity_steps=None, purity_weight=0.0, *, joint=False, level=None, keep_original=None,
+                     fade_seconds=FADE_SECONDS, match_gain=True):
         """Extend given recordings to `seconds` in total (more than one grid, 217 088 / 22 050 s): audio / audio_rate as in
         continue_audio; the recording is encoded to its 5 x 53 tokens, which become window 0, and the windows after it are
         generated under `text` as in generate_long.  Returns what generate_long returns; tokens[:, 0] are the recording's.
@@ -1011,16 +946,16 @@ class Diffsound:
         input's samples; keep_original="mel" / "audio" (inpaint_audio) keeps columns 0 .. 52 of the long clip as the recording's
         own mel / samples, with the cross-fade inside column 53.  joint=True (keyword-only, as on generate_long): the windows after the recording are ONE joint
         chain with the recording's grid held as the canvas head (generate_long); tokens[:, 0] stay the recording's."""
+        request = _request(self, level, (audio, audio_rate), keep_original, fade_seconds, match_gain)
         windows, n, _, samples = long_plan(seconds, overlap_seconds)
         if windows < 2:
             raise ValueError("extend_audio: seconds must exceed one grid (%d samples at %d Hz), got %r"
                              % (CLIP_SAMPLES, VOCODER_RATE, seconds))
         start = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})["content_token"]
-        out = self._long_tokens(text, windows, n, keep_mode, truncation_rate, caption_ids, seed, guidance_scale, negative_text,
-                                start_token=start, purity_steps=purity_steps, purity_weight=purity_weight,
-                                joint=getattr(_JOINT, "request", False))
-        return self._render_long(out, windows, n, samples, save_root, sample_rate,
-                                 self._paste_plan("extend_audio", start.shape[0], seconds=seconds, sample_rate=sample_rate))
+        out = self._long_tokens(text, windows, n, keep_mode, _sample_type(truncation_rate, False, purity_steps, purity_weight),
+                                caption_ids, seed, guidance_scale, negative_text, start_token=start, joint=joint)
+        return self._render_long(request, out, windows, n, samples, save_root, sample_rate,
+                                 self._paste_plan(request, "extend_audio", start.shape[0], seconds=seconds, sample_rate=sample_rate))
 
     # ---- likelihood scoring (DiffusionTransformer.score_tokens, DESIGN.md section 4) -------------------------------------------
     @torch.no_grad()
@@ -1029,18 +964,13 @@ class Diffsound:
         tokens), text = one caption per recording (strings, token ids or embeddings).  Returns DALLE.score_content's
         {'nats' f64[B] -- the variational bound, lower = better fit --, 'bits_per_token', 'terms'}; timesteps / draws /
         caption_ids / seed as in DiffusionTransformer.score_tokens."""
-        batch = dict(self._caption_batch(text), audio=audio, audio_rate=audio_rate)
-        if caption_ids is not None:
-            batch["caption_ids"] = caption_ids
-        if seed is not None:
-            batch["seed"] = seed
+        batch = dict(self._batch(text, caption_ids, seed), audio=audio, audio_rate=audio_rate)
         return self.model.score_content(batch, timesteps=timesteps, draws=draws)
 
-    @_levelled(False)
     @torch.no_grad()
     def generate_best_of(self, cond, n, score_timesteps=None, truncation_rate=0.85, fast=False, caption_ids=None, seed=None,
                          sample_rate=None, guidance_scale=None, negative_text=None, purity_steps=None, purity_weight=0.0,
-                         score_draws=1):
+                         score_draws=1, *, level=None):
         """Best-of-n generation: n candidates per caption, the one that fits its caption best is rendered.  cond and the
         keywords as in generate_sample_with_condition, whose `replicate` is n here; the candidates are its tokens at
         replicate = n with per-caption in-kernel noise (caption_ids default 0 .. B-1; replicate r of caption i draws as id
@@ -1049,21 +979,16 @@ class Diffsound:
         with score_timesteps / score_draws as its timesteps / draws (None: the full bound, T forwards per candidate).  The
         lowest score wins, ties go to the lowest replicate; only the winners are decoded and vocoded.
         Returns (mel01 f32[B,80,848], wave or None, tokens i64[B,265], scores f64[B, n] in nats)."""
+        request = _request(self, level)
         n = int(n)
         if n < 1:
             raise ValueError("generate_best_of needs at least one candidate per caption, got n = %r" % (n,))
         model = self.model
-        batch = dict(self._caption_batch(cond))
-        condition = model.prepare_condition(batch=batch)
+        condition = model.prepare_condition(batch=self._batch(cond))
         B = next(v.shape[0] for v in condition.values() if torch.is_tensor(v))
         ids = torch.arange(B) if caption_ids is None else torch.as_tensor(caption_ids, dtype=torch.long).reshape(-1)
-        batch["caption_ids"] = ids
-        if seed is not None:
-            batch["seed"] = seed
-        if negative_text is not None:
-            batch["negative_text"] = negative_text
-        sample_type = purity_sample_type("top" + str(truncation_rate) + ("r,fast" + str(fast - 1) if fast else "r"),
-                                         purity_steps, purity_weight)
+        batch = self._batch(cond, ids, seed, negative_text)
+        sample_type = _sample_type(truncation_rate, fast, purity_steps, purity_weight)
         model.eval()
         replicated = {k: (torch.cat([v for _ in range(n)], dim=0) if torch.is_tensor(v) else v) for k, v in condition.items()}
         tokens = model._run_chain(batch, replicated, model._free_keywords(0, 1.0, False, sample_type), n, sample_type,
@@ -1077,35 +1002,26 @@ class Diffsound:
         import numpy as np
         best = torch.from_numpy(np.argmin(scores.cpu().numpy(), axis=1)).to(tokens.device)   # first minimum: the lowest replicate
         winners = tokens.view(n, B, -1)[best, torch.arange(B, device=tokens.device)].contiguous()
-        mel01, wave, winners = self._render(winners, (B, 256, 5, 53), None, sample_rate)
+        mel01, wave, winners = self._render(request, winners, (B, 256, 5, 53), None, sample_rate)
         return mel01, wave, winners, scores
 
-    @_levelled(False)
     @torch.no_grad()
     def inference_generate_sample_with_condition(self, text, truncation_rate, save_root, batch_size, fast=False,
-                                                 guidance_scale=None, negative_text=None, purity_steps=None, purity_weight=0.0):
+                                                 guidance_scale=None, negative_text=None, purity_steps=None, purity_weight=0.0,
+                                                 *, level=None):
         """The reference's single-caption driver, same signature and behaviour (generate_samples_batch.py:89-123):
         ONE caption `text`, sampled `replicate = 10` times (hard-coded there, :111; `batch_size` is accepted and
         unused, as in the reference), results written under `save_root/str(text)/` as `000000`, `000001`, ...
         The reference writes `.png` through an image-era uint8 cast that cannot represent a [-1,1] spectrogram
         (`Image.fromarray` rejects the [80,848,1] array); this drop-in writes what the batch driver writes instead:
         `{n:06d}.npy` (mel in [0,1], f32[80,848]) and, with a vocoder, `{n:06d}.wav` (22 050 Hz PCM_24).  Returns the paths."""
-        import numpy as np
-        os.makedirs(save_root, exist_ok=True)
-        save_root_ = os.path.join(save_root, str(text))
-        os.makedirs(save_root_, exist_ok=True)
-        mel01, wave, _ = self.generate_sample_with_condition([text], truncation_rate, replicate=10, fast=fast,
+        _request(self, level)                     # a bad level raises here, before a directory is made; the inner driver applies it
+        replicate = 10
+        stems = _numbered_stems(os.path.join(save_root, str(text)), replicate)
+        mel01, wave, _ = self.generate_sample_with_condition([text], truncation_rate, replicate=replicate, fast=fast,
                                                              guidance_scale=guidance_scale, negative_text=negative_text,
-                                                             purity_steps=purity_steps, purity_weight=purity_weight)
-        mel01, wave = mel01.cpu().numpy(), None if wave is None else wave[:, 0].cpu().numpy()
-        written = []
-        for b in range(mel01.shape[0]):
-            path = os.path.join(save_root_, str(b).zfill(6))
-            np.save(path + ".npy", mel01[b])
-            if wave is not None:
-                write_wav_pcm24(path + ".wav", wave[b], 22050)
-            written.append(path)
-        return written
+                                                             purity_steps=purity_steps, purity_weight=purity_weight, level=level)
+        return _write_clips(mel01, wave, None, stems)
 
     @staticmethod
     def read_tsv(val_path):
@@ -1117,35 +1033,28 @@ class Diffsound:
                 caps.setdefault(row["file_name"], []).append(row["caption"])
         return caps
 
-    @_levelled(False)
     @torch.no_grad()
     def generate_sample(self, val_path, truncation_rate, save_root, fast=False, replicate=2, sample_rate=None,
-                        guidance_scale=None, purity_steps=None, purity_weight=0.0):
+                        guidance_scale=None, purity_steps=None, purity_weight=0.0, *, level=None):
         """The reference's file-writing driver (generate_samples_batch.py:143-187): per audio file, all of
         its captions x `replicate` are sampled in one batch; every sample is written as
         `{base}_mel_sample_{i}.npy` (mel in [0,1], f32[80,848]) and -- if there is a vocoder (:183) --
         `{base}_mel_sample_{i}.wav` (22 050 Hz or `sample_rate`, PCM_24).  Unlike the reference the vocoder runs on the whole
         batch at once."""
-        import numpy as np
+        _request(self, level)                     # a bad level raises here, before a directory is made; the inner driver applies it
         os.makedirs(save_root, exist_ok=True)
         written = []
         n_seen = 0                       # running caption index over the whole table = the global caption id
         philox = self.model.transformer.rng_mode == "philox"
         for key, captions in self.read_tsv(val_path).items():
-            base = key.split(".")[0] + "_mel_sample_"
+            base = os.path.join(save_root, key.split(".")[0] + "_mel_sample_")
             ids = list(range(n_seen, n_seen + len(captions))) if philox else None
             n_seen += len(captions)
             mel01, wave, _ = self.generate_sample_with_condition(list(captions), truncation_rate, replicate, fast=fast,
                                                                  caption_ids=ids, sample_rate=sample_rate,
                                                                  guidance_scale=guidance_scale, purity_steps=purity_steps,
-                                                                 purity_weight=purity_weight)
-            mel01, wave = mel01.cpu().numpy(), None if wave is None else wave[:, 0].cpu().numpy()
-            for i in range(mel01.shape[0]):
-                path = os.path.join(save_root, base + str(i))
-                np.save(path + ".npy", mel01[i])
-                if wave is not None:
-                    write_wav_pcm24(path + ".wav", wave[i], VOCODER_RATE if sample_rate is None else int(sample_rate))
-                written.append(path)
+                                                                 purity_weight=purity_weight, level=level)
+            written += _write_clips(mel01, wave, sample_rate, [base + str(i) for i in range(mel01.shape[0])])
         return written
 
 
