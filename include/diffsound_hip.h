@@ -956,6 +956,54 @@ int ds_paste_sums(const float* ren, const float* rec, int B, int T, int Tr, cons
 int ds_paste(const float* ren, const float* rec, float* out, int B, int C, int T, int Tr, const int64_t* off,
              const int32_t* rec_len, const uint8_t* keep_cols, int n_cols, int64_t col_num, int64_t col_den, double fade_len,
              int curve, const double* sums, ds_stream_t stream);
+/* Two waveforms side by side (csrc/compare.hip): a the reference f32[B][Na], b the one under test f32[B][Nb], mono, same rate.
+ * A lag l pairs b[n] with a[n + l].  The region [s0, s1) of b is the same for every row (per-row lengths and regions are not
+ * built): 0 <= s0 < s1 <= Nb, s0 - max_lag >= 0, s1 + max_lag <= Na.  A sample of a outside [0, Na) -- reachable only through a
+ * lag given on the device -- is never loaded and counts as 0.  Every product and sum is float64 (the products of two fp32 values
+ * are exact); sums run over the region cut into tiles of 8192 samples, n ascending inside a tile, tiles added in order, nothing
+ * atomic: a row's bits do not depend on the batch around it or on its position in it.
+ * ds_compare_align, for |l - c| <= M = max_lag, 0 <= M <= ds_compare_max_lag() = 4096 (one token column: a design choice):
+ *   r(l) = sum_{n in region} b[n] a[n+l],   ea(l) = sum a[n+l]^2,   eb = sum b[n]^2
+ *   rho(l) = r / sqrt(ea(l) eb), exactly 0 where ea(l) or eb is 0
+ *   lag_out[b] = the l of largest rho (a NaN counts as -inf); among bit-equal rho the smallest |l - c| wins, then the smaller l;
+ *   rho[b] = rho(lag_out[b]);  sums[b] = { r, ea, eb } at that lag (f64[B][3]) -- these three once more in double-double over
+ *   lanes striding the region (a fixed order), so the reported rho is within a few roundings of its float64 value also where
+ *   it is within a few roundings of 1; the search itself compares the plain float64 sums.  Chosen on the device: no host
+ *   synchronisation.
+ *   The centre c is 0 for a search.  A given lag skips the search: max_lag == 0 and c = lag_dev[b] (i32[B] on the device) or,
+ *   with lag_dev NULL, a host integer lag != 0 (then s0 + lag >= 0 and s1 + lag <= Na); lag_out[b] = c and only the
+ *   double-double pass runs.  (max_lag == 0 with lag_dev NULL and lag == 0 is a search over the one lag 0: the same numbers.)
+ * ds_compare_residual, at lag[b] (i32[B] on the device) with sums[b] as ds_compare_align wrote them for that lag:
+ *   alpha = r / ea (0 where ea is 0),  e_res = sum (b[n] - alpha a[n+l])^2,  e_dif = sum (b[n] - a[n+l])^2 -- summed directly --
+ *   and ea again in this pass's own order of addition, which is the ea of the two ratios below.
+ * ds_compare_stft: three resolutions through the 1024-point double FFT of ds_wave_to_mel (`twiddle` as there): Hann windows
+ *   of w = 256, 512, 1024 samples zero-padded to 1024 (windows f32[3][1024] on the device: audio.hann_window(w), then zeros),
+ *   hops 64, 128, 256; frame f of b starts at s0 + f hop, f < F = (s1 - s0 - w) div hop + 1, the frame of a lag[b] later; no
+ *   reflection, so s1 - s0 >= 1024.  With A, B the magnitudes of a's and b's frames over bins 0..512, in double, it leaves
+ *   sum (A - B)^2, sum A^2 and sum |ln max(A, 1e-5) - ln max(B, 1e-5)| per workgroup of 16 frames.  Both transforms are the
+ *   same instructions: identical samples give identical magnitudes and exact zeros.
+ * ds_compare_finish adds the partials in order and writes, per row,
+ *   si_sdr_db = 10 log10(alpha^2 ea / e_res): +inf when e_res == 0, else -inf when alpha^2 ea == 0
+ *   snr_db    = 10 log10(ea / e_dif), by the same two rules
+ *   sc[b][i]     = sqrt(sum (A - B)^2) / sqrt(sum A^2): 0 when the numerator is 0, +inf when only the denominator is
+ *   logmag[b][i] = sum |ln max(A, 1e-5) - ln max(B, 1e-5)| / (513 F)              (f64[B][3] each, i = the resolution)
+ * The entries run in this order on one stream with the same B, s0, s1, max_lag and scratch (ds_compare_scratch_bytes(B,
+ * s1 - s0, max_lag) bytes, 8-byte aligned; -1 for sizes out of range).  ds_compare_l1: out[b] = sum |x[b][i] - y[b][i]| / n in
+ * float64 over fp32 rows of n values, i strided over 256 lanes, the lanes' sums added in a fixed order (the log-mel distance).
+ * No entry allocates or synchronises.  A null pointer, max_lag outside 0..4096, a region outside its rules, a region under 1024
+ * samples (ds_compare_stft, ds_compare_finish) or a scratch that is too small return -1 and launch nothing. */
+int ds_compare_max_lag(void);
+int64_t ds_compare_scratch_bytes(int B, int n_region, int max_lag);
+int ds_compare_align(const float* a, const float* b, int B, int Na, int Nb, int s0, int s1, int max_lag, const int32_t* lag_dev,
+                     int lag, void* scratch, int64_t scratch_bytes, int32_t* lag_out, double* rho, double* sums,
+                     ds_stream_t stream);
+int ds_compare_residual(const float* a, const float* b, int B, int Na, int Nb, int s0, int s1, int max_lag, const int32_t* lag,
+                        const double* sums, void* scratch, int64_t scratch_bytes, ds_stream_t stream);
+int ds_compare_stft(const float* a, const float* b, int B, int Na, int Nb, int s0, int s1, int max_lag, const int32_t* lag,
+                    const float* windows, const double* twiddle, void* scratch, int64_t scratch_bytes, ds_stream_t stream);
+int ds_compare_finish(int B, int s0, int s1, int max_lag, const double* sums, const void* scratch, int64_t scratch_bytes,
+                      double* si_sdr_db, double* snr_db, double* sc, double* logmag, ds_stream_t stream);
+int ds_compare_l1(const float* x, const float* y, int B, int64_t n, double* out, ds_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -208,6 +208,15 @@ _PROTOS = {
     "ds_paste_sums": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _i64, _i64, _vp, _i64, _vp, _vp]),
     "ds_paste": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _i64, _i64, C.c_double,
                            C.c_int, _vp, _vp]),
+    "ds_compare_max_lag": (C.c_int, []),
+    "ds_compare_scratch_bytes": (_i64, [C.c_int, C.c_int, C.c_int]),
+    "ds_compare_align": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _i64,
+                                   _vp, _vp, _vp, _vp]),
+    "ds_compare_residual": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _i64, _vp]),
+    "ds_compare_stft": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _i64,
+                                  _vp]),
+    "ds_compare_finish": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "ds_compare_l1": (C.c_int, [_vp, _vp, C.c_int, _i64, _vp, _vp]),
 }
 # The caption-track entries (csrc/sampler.hip SampleCompose), a table of their own: tests/test_driver_host.py walks the
 # sampling entries of _PROTOS against its closed list of their rejections; these entries' rejections are walked by

@@ -4,7 +4,9 @@ polyphase table of `ds_resample` (csrc/resample.hip) and its launcher: audio at 
 cross-fade table of `ds_mel_stitch` (csrc/misc.hip) and its launcher: window mels joined into one long mel; the K-weighting
 coefficients and segment plan of the `ds_level_*` entries (csrc/loudness.hip) and their launchers: loudness, true peak, gain;
 the plan and the launchers of the `ds_limit_*` entries (csrc/limiter.hip): a look-ahead true-peak limiter behind that gain;
-the launchers of `ds_paste_sums` / `ds_paste` (csrc/paste.hip): a recording pasted back over a rendering of it.
+the launchers of `ds_paste_sums` / `ds_paste` (csrc/paste.hip): a recording pasted back over a rendering of it; the region
+rules, window table and launchers of the `ds_compare_*` entries (csrc/compare.hip): two waveforms side by side -- lag, SI-SDR,
+multi-resolution STFT and log-mel distances.
 
 The reference extracts mels with librosa on the host (Diffsound/vocoder/mel2wav/extract_mel_spectrogram.py:15-38,141-187)
 and reads audio with `librosa.load(path, sr=None)` (:167); its data preparation resamples with `librosa.load(path, sr=22050)`
@@ -624,6 +626,179 @@ def paste(ren, rec, keep_cols, *, off=0, col_num, col_den=1, fade_len=0.0, curve
     _lib.check(_lib.lib().ds_paste(_lib.ptr(ren), _lib.ptr(rec), _lib.ptr(out), B, C, T, rec.shape[-1], _lib.ptr(off),
                                    _lib.ptr(rec_len), _lib.ptr(keep_cols), keep_cols.shape[1], int(col_num), int(col_den),
                                    float(fade_len), PASTE_CURVES[curve], _lib.ptr(sums), _lib.stream()))
+    return out
+
+
+# ---- two waveforms side by side: lag, SI-SDR / SNR, multi-resolution STFT and log-mel distances (csrc/compare.hip) --------------
+COMPARE_MAX_LAG = 4096          # = ds_compare_max_lag(): one token column.  A design choice, not a limit of the method
+# (window, hop) of the three STFT resolutions, all through the one 1024-point FFT the tree has (windows zero-padded to it).
+# Parallel WaveGAN's resolutions are FFT 512 / 1024 / 2048; these are this project's own and numbers are not comparable.
+COMPARE_RESOLUTIONS = ((256, 64), (512, 128), (1024, 256))
+COMPARE_MEL_RATE = 22050        # the one rate the log-mel distance is defined at (Audio2Mel's filterbank)
+
+_COMPARE_TABLES = {}
+
+
+def _compare_windows(device):
+    key = (device.type, device.index)
+    if key not in _COMPARE_TABLES:
+        win = torch.zeros(len(COMPARE_RESOLUTIONS), N_FFT)
+        for i, (w, _) in enumerate(COMPARE_RESOLUTIONS):
+            win[i, :w] = hann_window(w)
+        _COMPARE_TABLES[key] = win.to(device)
+    return _COMPARE_TABLES[key]
+
+
+def compare_region(n_a, n_b, max_lag=0, lag=None, region=None, min_len=1):
+    """The region [s0, s1) of b that align / compare work on, checked on the host -> (s0, s1).  Default: every sample of b whose
+    partner in a exists at every lag in question -- [max_lag, min(n_a, n_b) - max_lag) for a search, [max(0, -lag),
+    min(n_b, n_a - lag)) at a host integer lag, [0, min(n_a, n_b)) at a lag on the device.  A region must be non-empty (compare:
+    at least 1024 samples), inside b, and keep s0 - max_lag >= 0 and s1 + max_lag <= n_a (at an integer lag: s0 + lag >= 0 and
+    s1 + lag <= n_a); anything else raises ValueError.  The region is the same for every row: per-row lengths are not built."""
+    max_lag = _compare_max_lag(max_lag)
+    host_lag = lag if isinstance(lag, (int, np.integer)) and not isinstance(lag, bool) else None
+    if region is None:
+        if host_lag is not None:
+            s0, s1 = max(0, -int(host_lag)), min(n_b, n_a - int(host_lag))
+        else:
+            s0, s1 = max_lag, min(n_a, n_b) - max_lag
+    else:
+        try:
+            s0, s1 = region
+        except (TypeError, ValueError):
+            raise ValueError("region is a pair (s0, s1) of sample indices of b, got %r" % (region,))
+        for v in (s0, s1):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError("region is a pair of integers, got %r" % (region,))
+        s0, s1 = int(s0), int(s1)
+    if not (0 <= s0 < s1 <= n_b):
+        raise ValueError("the region [%d, %d) must be non-empty and inside b's %d samples" % (s0, s1, n_b))
+    if s1 - s0 < min_len:
+        raise ValueError("the region [%d, %d) holds %d samples; at least %d are needed" % (s0, s1, s1 - s0, min_len))
+    lo, hi = (s0 + int(host_lag), s1 + int(host_lag)) if host_lag is not None else (s0 - max_lag, s1 + max_lag)
+    if lo < 0 or hi > n_a:
+        raise ValueError("the region [%d, %d) reaches samples [%d, %d) of a, which holds %d" % (s0, s1, lo, hi, n_a))
+    return s0, s1
+
+
+def _compare_max_lag(max_lag):
+    if isinstance(max_lag, bool) or not isinstance(max_lag, (int, np.integer)) or not 0 <= max_lag <= COMPARE_MAX_LAG:
+        raise ValueError("max_lag must be an integer in 0..%d, got %r" % (COMPARE_MAX_LAG, max_lag))
+    return int(max_lag)
+
+
+def _compare_rows(a, b):
+    """the checks of the two inputs that need no device: ValueError; then the device check"""
+    for name, x in (("a", a), ("b", b)):
+        if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32:
+            raise ValueError("%s must be a tensor f32[B, N]" % name)
+        if not x.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+    if a.shape[0] != b.shape[0] or a.shape[0] < 1:
+        raise ValueError("a holds %d rows and b %d: one row of each per comparison, at least one" % (a.shape[0], b.shape[0]))
+    if a.shape[1] < 1 or b.shape[1] < 1:
+        raise ValueError("a and b must hold samples")
+
+
+def _compare_device(a, b):
+    if not a.is_cuda or not b.is_cuda:
+        raise _lib.DiffsoundHipError("a / b is not on a GPU: the HIP path has no CPU fallback")
+    if int(_lib.lib().ds_compare_max_lag()) != COMPARE_MAX_LAG:
+        raise RuntimeError("libdiffsound_hip's lag cap is %d, audio.COMPARE_MAX_LAG is %d" % (_lib.lib().ds_compare_max_lag(), COMPARE_MAX_LAG))
+
+
+def _compare_align(a, b, s0, s1, max_lag, lag):
+    """ds_compare_align -> (lag i32[B], rho f64[B], sums f64[B, 3], scratch, its bytes); lag: None (search), int, or i32[B]"""
+    B, dev = a.shape[0], a.device
+    L = _lib.lib()
+    nbytes = int(L.ds_compare_scratch_bytes(B, s1 - s0, max_lag))
+    scratch = torch.empty(nbytes // 8 + 1, device=dev, dtype=torch.float64)
+    lag_out = torch.empty(B, device=dev, dtype=torch.int32)
+    rho = torch.empty(B, device=dev, dtype=torch.float64)
+    sums = torch.empty(B, 3, device=dev, dtype=torch.float64)
+    lag_dev = lag if torch.is_tensor(lag) else None
+    _lib.check(L.ds_compare_align(_lib.ptr(a), _lib.ptr(b), B, a.shape[1], b.shape[1], s0, s1, max_lag, _lib.ptr(lag_dev),
+                                  0 if lag is None or lag_dev is not None else int(lag), _lib.ptr(scratch), nbytes,
+                                  _lib.ptr(lag_out), _lib.ptr(rho), _lib.ptr(sums), _lib.stream()))
+    return lag_out, rho, sums, scratch, nbytes
+
+
+def align(a, b, max_lag, region=None):
+    """The lag at which b f32[B, Nb] lines up with its reference a f32[B, Na] (device, contiguous, same rate) -> (lag i32[B],
+    rho f64[B]) on the device: lag l pairs b[n] with a[n + l]; over |l| <= max_lag <= 4096 the normalised correlation
+    rho(l) = sum b[n] a[n+l] / sqrt(sum a[n+l]^2 sum b[n]^2) over the region (compare_region) is formed in float64 and the l of
+    largest rho is chosen on the device -- among bit-equal rho the smallest |l|, then the negative one.  rho is exactly 0 where
+    either energy is 0.  Two launches, no host synchronisation; a row's bits do not depend on the batch around it.  The formulas
+    are in include/diffsound_hip.h (ds_compare_align).  A host tensor raises (there is no CPU path)."""
+    max_lag = _compare_max_lag(max_lag)
+    _compare_rows(a, b)
+    s0, s1 = compare_region(a.shape[1], b.shape[1], max_lag, None, region)
+    _compare_device(a, b)
+    lag, rho, _, _, _ = _compare_align(a, b, s0, s1, max_lag, None)
+    return lag, rho
+
+
+def compare(a, b, *, max_lag=0, lag=None, region=None, rate=22050):
+    """b f32[B, Nb], the waveform under test, against its reference a f32[B, Na] (device, contiguous, both at `rate` Hz) -> a
+    dict of device tensors:
+      'lag' i32[B], 'rho' f64[B]   align's search over |l| <= max_lag; or lag= an int or an i32[B] device tensor, which skips
+                                   the search (rho is then the correlation at that lag; samples a device lag reaches outside a
+                                   count as 0)
+      'si_sdr_db' f64[B]           10 log10(alpha^2 ea / sum (b - alpha a)^2), alpha = r / ea: +inf for a zero residual, else -inf
+                                   where alpha^2 ea is 0.  The residual is summed directly, sample by sample
+      'snr_db' f64[B]              10 log10(ea / sum (b - a)^2), same two rules
+      'sc', 'logmag' f64[B, 3]     per resolution of COMPARE_RESOLUTIONS: spectral convergence |A - B|_F / |A|_F and the mean of
+                                   |ln max(A, 1e-5) - ln max(B, 1e-5)| over the frames lying wholly inside the region (no
+                                   reflection) and bins 0..512 of a 1024-point FFT
+      'mel_l1' f64[B]              the mean |difference| of Audio2Mel's log10 mel (ds_wave_to_mel) of the two aligned cuts
+                                   a[s0 + l : s1 + l] and b[s0 : s1], reduced in float64 -- only at rate == 22050, the rate
+                                   that filterbank is defined at: at another rate the key is absent, not approximated.
+    region (compare_region) is the same for every row and holds at least 1024 samples.  Everything is float64 over fixed
+    partitions in a fixed order; nothing synchronises.  What these numbers say about a trained model is unmeasured.  The formulas
+    are in include/diffsound_hip.h (ds_compare_align).  A host tensor raises (there is no CPU path)."""
+    rate = _level_rate(rate)
+    max_lag = _compare_max_lag(max_lag)
+    _compare_rows(a, b)
+    B = a.shape[0]
+    if lag is not None:
+        if max_lag != 0:
+            raise ValueError("lag= skips the search: max_lag must be 0 with it")
+        if torch.is_tensor(lag):
+            if lag.dtype != torch.int32 or tuple(lag.shape) != (B,) or not lag.is_contiguous():
+                raise ValueError("a lag tensor must be i32[B], contiguous, on the device")
+        elif isinstance(lag, bool) or not isinstance(lag, (int, np.integer)):
+            raise ValueError("lag must be None, an int or an i32[B] device tensor, got %r" % (lag,))
+    s0, s1 = compare_region(a.shape[1], b.shape[1], max_lag, lag, region, min_len=N_FFT)
+    _compare_device(a, b)
+    if torch.is_tensor(lag) and not lag.is_cuda:
+        raise _lib.DiffsoundHipError("lag is not on a GPU: the HIP path has no CPU fallback")
+    dev = a.device
+    L = _lib.lib()
+    lag_out, rho, sums, scratch, nbytes = _compare_align(a, b, s0, s1, max_lag, lag)
+    st = _lib.stream()
+    Na, Nb = a.shape[1], b.shape[1]
+    _lib.check(L.ds_compare_residual(_lib.ptr(a), _lib.ptr(b), B, Na, Nb, s0, s1, max_lag, _lib.ptr(lag_out), _lib.ptr(sums),
+                                     _lib.ptr(scratch), nbytes, st))
+    _lib.check(L.ds_compare_stft(_lib.ptr(a), _lib.ptr(b), B, Na, Nb, s0, s1, max_lag, _lib.ptr(lag_out),
+                                 _lib.ptr(_compare_windows(dev)), _lib.ptr(_twiddle(dev)), _lib.ptr(scratch), nbytes, st))
+    out = {"lag": lag_out, "rho": rho,
+           "si_sdr_db": torch.empty(B, device=dev, dtype=torch.float64), "snr_db": torch.empty(B, device=dev, dtype=torch.float64),
+           "sc": torch.empty(B, 3, device=dev, dtype=torch.float64), "logmag": torch.empty(B, 3, device=dev, dtype=torch.float64)}
+    _lib.check(L.ds_compare_finish(B, s0, s1, max_lag, _lib.ptr(sums), _lib.ptr(scratch), nbytes, _lib.ptr(out["si_sdr_db"]),
+                                   _lib.ptr(out["snr_db"]), _lib.ptr(out["sc"]), _lib.ptr(out["logmag"]), st))
+    if rate == COMPARE_MEL_RATE:
+        key = ("mel", dev.type, dev.index)
+        if key not in _COMPARE_TABLES:
+            basis = mel_filterbank(COMPARE_MEL_RATE, N_FFT, 80)
+            _COMPARE_TABLES[key] = (hann_window(N_FFT).to(dev), basis.to(dev), row_ranges(basis).to(dev))
+        window, basis, krange = _COMPARE_TABLES[key]
+        pad = (N_FFT - HOP) // 2
+        idx = torch.arange(s0, s1, device=dev)[None, :] + lag_out[:, None].long()       # the cut of a, by the device's own lag
+        cut = torch.where((idx >= 0) & (idx < Na), a.gather(1, idx.clamp(0, Na - 1)), torch.zeros((), device=dev))
+        ma = wave_to_mel(cut, window, basis, krange, pad=pad)
+        mb = wave_to_mel(b[:, s0:s1].contiguous(), window, basis, krange, pad=pad)
+        out["mel_l1"] = torch.empty(B, device=dev, dtype=torch.float64)
+        _lib.check(L.ds_compare_l1(_lib.ptr(ma), _lib.ptr(mb), B, ma.shape[1] * ma.shape[2], _lib.ptr(out["mel_l1"]), st))
     return out
 
 

@@ -967,6 +967,55 @@ class Diffsound:
         batch = dict(self._batch(text, caption_ids, seed), audio=audio, audio_rate=audio_rate)
         return self.model.score_content(batch, timesteps=timesteps, draws=draws)
 
+    # ---- two waveforms side by side (audio.compare) -------------------------------------------------------
+    @staticmethod
+    def _rows_at_22k(item, rate, device):
+        """recordings as the drivers take them (or a driver's own f32[B,1,T] output) -> f32[B, T'] at 22 050 Hz on the device, rows
+        zero-extended to the longest"""
+        if torch.is_tensor(item) and item.dim() == 3 and item.shape[1] == 1:
+            item = item[:, 0]
+        rows, _ = recording_at_rate(item, rate, VOCODER_RATE, device)
+        return rows.float().contiguous()
+
+    @torch.no_grad()
+    def compare_audio(self, a, b, audio_rate=None, **kw):
+        """b, the waveforms under test, against their references a: each a device tensor f32[B, T] (or a driver's f32[B, 1, T]),
+        host arrays or `.wav` paths, as the other drivers take recordings; audio_rate the sample rate of both (one or one per clip,
+        None = 22 050 Hz / the files' own; two tensors at different rates: audio.resample one first).  Both are brought to 22 050 Hz on the
+        device (audio.resample; a clip already there is not touched) and handed to audio.compare with the remaining keywords
+        (max_lag, lag, region -- in samples at 22 050 Hz) -> its dict of device tensors: lag, rho, si_sdr_db, snr_db, sc,
+        logmag, mel_l1.  Rows of different length are zero-extended to the longest: the region is one for the whole batch
+        (per-row lengths are not built), so name a region that every row fills.  What these numbers say about a trained model
+        is unmeasured; on seeded weights they measure the code."""
+        from . import audio
+        if "rate" in kw:
+            raise ValueError("compare_audio compares at 22 050 Hz: give the inputs' rate as audio_rate")
+        device = next(self.model.parameters()).device
+        rows_a = self._rows_at_22k(a, audio_rate, device)
+        rows_b = self._rows_at_22k(b, audio_rate, device)
+        return audio.compare(rows_a, rows_b, rate=VOCODER_RATE, **kw)
+
+    @torch.no_grad()
+    def round_trip(self, audio, audio_rate=None, max_lag=2048):
+        """What the codec and the vocoder do to a recording: audio / audio_rate as in generate_sample_from_audio -> its 5 x 53
+        tokens (prepare_content) -> decode -> vocoder, nothing sampled -> (mel01 f32[B,80,848], wave f32[B,1,217088], tokens,
+        report).  report = audio.compare of the rendering against the recording at 22 050 Hz, the lag searched over
+        RECORDING_OFFSET +- max_lag (the search is centred on the alignment the code defines, so it lies inside for any
+        max_lag) over the default region; report['lag'] is the full lag, RECORDING_OFFSET where the definition holds.  Needs a
+        vocoder (ValueError without).  How lossy the round trip is with TRAINED weights is unmeasured: no checkpoint is in
+        the tree; on seeded weights the report measures the code, not a model."""
+        from . import audio as A
+        if self.vocoder is None:
+            raise ValueError("round_trip needs a vocoder: there is no waveform to compare")
+        content = self.model.prepare_content({"audio": audio, "audio_rate": audio_rate})
+        mel01, wave, tokens = self._render(_Request(None, None, None), content["content_token"], content["content_quant"].shape)
+        rec = self._rows_at_22k(audio, audio_rate, wave.device)
+        if rec.shape[1] <= RECORDING_OFFSET:
+            raise ValueError("the recording holds %d samples at 22 050 Hz: too short to compare" % rec.shape[1])
+        report = A.compare(rec[:, RECORDING_OFFSET:].contiguous(), wave[:, 0].contiguous(), max_lag=max_lag, rate=VOCODER_RATE)
+        report["lag"] = report["lag"] + RECORDING_OFFSET
+        return mel01, wave, tokens, report
+
     @torch.no_grad()
     def generate_best_of(self, cond, n, score_timesteps=None, truncation_rate=0.85, fast=False, caption_ids=None, seed=None,
                          sample_rate=None, guidance_scale=None, negative_text=None, purity_steps=None, purity_weight=0.0,
